@@ -6,11 +6,19 @@ BASELINE.json config 3) on N GPUs of one node, one process per GPU over RCCL.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  `value` = images of all ranks / max-over-ranks time of the K
-timed steps (inputs are generated on the device inside the step, as in the reference loop).
-Extra objects: `roofline` (conv_igemm kernels, HIP events on the launch stream, in a separate
-instrumented pass over the same step) and `cpu_baseline` (the CPU oracle timed on the host
-cores, rank 0, N=1 only, bounded sample).  Also reports G-synthesis ms/img (second half of the
-BASELINE metric) as `synthesis_ms_per_img`.
+timed steps (inputs are generated on the device inside the step, as in the reference loop);
+`ms_per_step` = that time / K.  A plain run does only that: set-up, one priming step, W warm-up
+steps, the K timed steps.
+
+--full adds what takes runs of its own (each still switchable off by its --no-* flag):
+`extras` (batch 2 eager and as hipGraph replay, the serial loop, eval-mode G), G-synthesis ms/img
+(second half of the BASELINE metric) as `synthesis_ms_per_img`, `roofline` (conv kernels, HIP
+events on the launch stream, in a separate instrumented pass over the same step) and
+`cpu_baseline` (the CPU oracle timed on the host cores, rank 0, N=1 only, bounded sample).
+
+--dump-outputs DIR writes what EAlignStep.step returns in the last timed iteration when the last
+two timed iterations run again after the timed steps, from the encoder's seeded weights in
+deterministic mode, as DIR/<name>.npy (see main() for why, dump_outputs() for the format).
 """
 import argparse
 import json
@@ -49,7 +57,31 @@ def parse():
     ap.add_argument("--no-synthesis", action="store_true", help="skip the synthesis-only timing (used by tools/pmc_traffic.sh so that "
                     "the profiled conv launches are exactly those of the training steps)")
     ap.add_argument("--cpu-size", type=int, default=1024, help="image size of the bounded CPU-oracle sample")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run the extras, the synthesis timing, the roofline pass and the CPU "
+                    "baseline (the --no-* flags above apply only here); a plain run times the headline step alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the step returns in the last timed iteration, rerun with the one "
+                    "before it from the encoder's seeded weights in deterministic mode, as DIR/<name>.npy (float32)")
+    a = ap.parse_args()
+    if a.dump_outputs and a.graph:
+        ap.error("--dump-outputs runs the dumped iterations as eager steps: not with --graph")
+    if not a.full:
+        a.no_extras = a.no_synthesis = a.no_roofline = a.no_cpu_baseline = True
+    return a
+
+
+def dump_outputs(out_dir, res, limit=64 << 20):
+    """The arrays of `res` (the dict EAlignStep.step returns) as out_dir/<name>.npy in float32, at most `limit` bytes in
+    all.  An array larger than its share of `limit` is written as a fixed sample of its flattened elements: indices drawn from a
+    generator seeded with 0, sorted, so that two builds of the project write the same elements of the same inputs."""
+    import numpy as np
+    arrs = {k: v.detach() for k, v in sorted(res.items()) if torch.is_tensor(v)}
+    cap = (limit // 4) // max(len(arrs), 1)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrs.items():
+        if t.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def cpu_baseline(img_size, start_features, batch=2, timed=3):
@@ -154,6 +186,8 @@ def main():
         G, Gm, E, LP = build_models_sg1(a.img_size, a.start_features, a.dtype, dev, seed=0)
         st = EAlignStep(G, E, LP, batch_size=a.batch, mapping=Gm)
         gname = f"StyleGAN1-{a.img_size} Gs+Gm"
+    # --dump-outputs: the encoder's seeded weights, the state the dumped iterations start from (see below)
+    e_init = {k: v.detach().clone() for k, v in E.state_dict().items()} if a.dump_outputs else None
 
     def sync():
         if world > 1:
@@ -184,6 +218,35 @@ def main():
     dt, step_stats = timed_steps(run, a.warmup, a.steps, sync)
     if not a.graph:
         st.cancel_prefetch()            # (the pass the last timed step issued for an iteration this run does not make)
+    if a.dump_outputs:
+        # The timed steps' own results do not repeat from run to run: in the default mode the encoder's instance-norm statistics
+        # and gradient sums end in f32 atomics, whose order flips bf16 roundings (and leaky-relu slopes at the kink), and Adam
+        # (beta_1 = 0) carries that into the weights.  Two runs of one build, same arguments, last timed step, max |a - b| / max |a|:
+        # w2 8.6e-4 / imgs2 1.4e-2 / loss 1.5e-3 after one timed step, 3.1e-3 / 3.0e-2 / 5.1e-3 after 16; the same with or without
+        # the prefetch and side streams.  So the last two timed iterations run again through the same step(), from the encoder's
+        # seeded weights and a fresh optimizer, in the library's deterministic mode (the same reductions ending in a fixed order,
+        # ops.set_deterministic): the results of the second come from weights the first one's backward passes and optimizer updates
+        # changed, and they repeat bit for bit.  The encoder's weights, the optimizer's state, the generator's buffers (w_avg) and the mode are put back.
+        keep_e = {k: v.detach().clone() for k, v in E.state_dict().items()}
+        keep_opt = {p: {"step": v["step"], "exp_avg_sq": v["exp_avg_sq"].clone()} for p, v in st.opt.state.items()}
+        keep_buf = [(b, b.clone()) for m in ((G, Gm) if a.mtype == 1 else (G,)) for b in m.buffers()]
+        was_det = ops.is_deterministic()
+        E.load_state_dict(e_init)
+        st.opt.state.clear()
+        ops.set_deterministic(True)
+        for it in (a.warmup + a.steps - 2, a.warmup + a.steps - 1):
+            res = st.step(it)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, res)
+        ops.set_deterministic(was_det)
+        E.load_state_dict(keep_e)
+        st.opt.state.clear()
+        st.opt.state.update(keep_opt)
+        with torch.no_grad():
+            for b, v in keep_buf:
+                b.copy_(v)
+        del e_init, keep_e, keep_opt, keep_buf, res
+        sync()
     if world > 1:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -36,7 +36,12 @@ def test_oracle_reproduces_the_reference_classes(tag):
     np.testing.assert_allclose(grad.numpy(), g["gradient_" + tag], rtol=1e-4, atol=1e-9)
     np.testing.assert_allclose(m.numpy(), g["mask_" + tag], rtol=1e-4, atol=1e-5)
     np.testing.assert_allclose(GR.grad_cam_pp(sd, imgs, None, plain=True)[0].numpy(), g["mask_plain_" + tag], rtol=1e-4, atol=1e-5)
-    np.testing.assert_allclose(GR.guided_backprop(sd, imgs).numpy(), g["gbp_" + tag], rtol=1e-4, atol=1e-9)
+    # the golden holds the float32 rounding of the CPU conv kernels that wrote it (the float64 value lies up to 7e-9 from it) and
+    # another CPU's kernels sum in another order: the absolute floor is 2 ulps of the largest element, and the relative L2
+    # error bounds the whole array at float32 resolution
+    gbp, want = GR.guided_backprop(sd, imgs).numpy(), g["gbp_" + tag]
+    np.testing.assert_allclose(gbp, want, rtol=1e-4, atol=2.0 ** -22 * np.abs(want).max())
+    assert np.linalg.norm(gbp - want) <= 1e-6 * np.linalg.norm(want)
     h, c = GR.mask2cam(torch.tensor(g["mask_" + tag]).double(), imgs)
     np.testing.assert_allclose(h.numpy(), g["heat_" + tag], atol=1e-6)
     np.testing.assert_allclose(c.numpy(), g["cam_" + tag], atol=1e-5)
