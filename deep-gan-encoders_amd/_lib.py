@@ -180,6 +180,11 @@ SIGNATURES = {
     "dge_up_pp_supported": [_I, _I, _I, _I, _I, _I],
     "dge_pack_up_pp": [_P, _P, _I, _I, _P, _P, _F, _I, _P],
     "dge_up_pp": [_P, _P, C.c_longlong, _P, _P, _I, _P, _P, _F, _F, _I, _I, _I, _I, _I, _I, _P],
+    "dge_latent_pnorm_fwd": [_P, _P, _P, C.c_long, _I, _P],
+    "dge_latent_pnorm_bwd": [_P, _P, _P, _P, C.c_long, _I, _F, _P],
+    "dge_wplus_lerp": [_P, _P, _I, _F, _P, _I, _I, _I, _P],
+    "dge_wplus_lerp_bwd": [_P, _F, _P, C.c_long, _I, _P],
+    "dge_embed_track": [_P, _P, _P, C.c_long, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
 }
 
 _lib = None

@@ -92,8 +92,21 @@ def blur_encoder_forward(E, img, noises=None, save=False):
     return ops.nhwc_to_nchw(x), torch.stack(ws, dim=1), saved
 
 
-def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False):
-    """-> (gradients for E.parameters() in registration order, image gradient [B,3,R,R] or None)."""
+def _linear_dgrad(lin, g_w):
+    """Data part of _linear_backward alone (same launch): w = musig @ W^T + b -> g_musig [B,2C]."""
+    B = g_w.shape[0]
+    W = lin.weight.detach()
+    gms = torch.empty((B, W.shape[1]), dtype=torch.float32, device=g_w.device)
+    ops.linear_t(g_w, W, gms, ldx=g_w.stride(0), B=B)
+    return gms
+
+
+def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=True):
+    """-> (gradients for E.parameters() in registration order, image gradient [B,3,R,R] or None).
+    params=False (frozen encoder: the W+ inversion mode of embedding_v2.py): the data gradient alone.  No weight-gradient
+    launch runs (conv_wgrad, the dense weight gradients, fromrgb_bwd) and the side reductions that only feed parameter
+    gradients are dropped; the data path is the same launches in the same order, so the image gradient is the same bits.
+    Every parameter gradient is None."""
     cache = E.__dict__.setdefault("_pack_cache", {})
     dev = g_w.device
     L = E.layer_count
@@ -114,32 +127,37 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False):
         last = not blk.has_last_conv
         has3 = Cc != C2
         g_w2, g_w1 = g_w[:, 2 * (L - 1 - j)], g_w[:, 2 * (L - 1 - j) + 1]
-        gms2 = _linear_backward(blk.inver_mod2, g_w2, rec["musig2"], grads, pre + "inver_mod2")
-        gms1 = _linear_backward(blk.inver_mod1, g_w1, rec["musig1"], grads, pre + "inver_mod1")
+        if params:
+            gms2 = _linear_backward(blk.inver_mod2, g_w2, rec["musig2"], grads, pre + "inver_mod2")
+            gms1 = _linear_backward(blk.inver_mod1, g_w1, rec["musig1"], grads, pre + "inver_mod1")
+        else:
+            gms2, gms1 = _linear_dgrad(blk.inver_mod2, g_w2), _linear_dgrad(blk.inver_mod1, g_w1)
         x, x1 = rec["x"], rec["x1"]
         extra, extra_pool, extra_scale = None, False, 1.0
         if not last:
             if g_out is None:
                 raise RuntimeError("non-final encoder block without an output gradient")
-            red2 = ops.zeros((C2, 3 if has3 else 2), dev)      # {bias_2, noise_weight_2 [, sum g_out -> conv_3.bias]}
+            red2 = ops.zeros((C2, 3 if has3 else 2), dev) if params else None   # {bias_2, noise_weight_2 [, sum g_out -> conv_3.bias]}
             if blk.fused_scale:
                 g_t = ops.act_bwd(g_out, rec["a2"], rec["n2"], pool=False, scale=0.111, red=red2)      # lrelu' at half resolution
                 g_c2 = ops.nearest_up2(g_t, 0.25)                                                  # adjoint of the 2x2 average
             else:
                 g_c2 = ops.act_bwd(g_out, rec["a2"], rec["n2"], pool=True, scale=0.111 * 0.25, red=red2)
-            grads[pre + "bias_2"] = red2[:, 0].reshape(1, C2, 1, 1)
-            grads[pre + "noise_weight_2"] = red2[:, 1].reshape(1, C2, 1, 1)
-            gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
-            ops.conv_wgrad(g_c2, rec["y2"], gW2)
-            grads[pre + "conv_2.weight"] = gW2
+            if params:
+                grads[pre + "bias_2"] = red2[:, 0].reshape(1, C2, 1, 1)
+                grads[pre + "noise_weight_2"] = red2[:, 1].reshape(1, C2, 1, 1)
+                gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
+                ops.conv_wgrad(g_c2, rec["y2"], gW2)
+                grads[pre + "conv_2.weight"] = gW2
             g_y2b = ops.conv2d(g_c2, _packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3)
             g_y2 = ops.blur_noise_act(g_y2b, None, None, None, blur=True, act=False)                 # Blur is self-adjoint
             dots2 = ops.dot_stats(g_y2, x1)
             if has3:
-                grads[pre + "conv_3.bias"] = red2[:, 2] * 0.889
-                gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
-                ops.conv_wgrad(g_out, rec["xp"], gW3)
-                grads[pre + "conv_3.weight"] = ops.scale_(gW3, 0.889)
+                if params:
+                    grads[pre + "conv_3.bias"] = red2[:, 2] * 0.889
+                    gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
+                    ops.conv_wgrad(g_out, rec["xp"], gW3)
+                    grads[pre + "conv_3.weight"] = ops.scale_(gW3, 0.889)
                 extra = ops.conv2d(g_out, _packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, gain=0.889)
                 extra_pool, extra_scale = True, 0.25
             else:
@@ -152,21 +170,23 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False):
             else:
                 g_y2, dots2 = None, None
         coef2 = ops.in_bwd_coef(dots2, gms2, rec["musig2"], rec["sc2"], rec["sh2"], N)
-        red1 = ops.zeros((Cc, 2), dev)
+        red1 = ops.zeros((Cc, 2), dev) if params else None
         g_pre1 = ops.in_bwd(g_y2, x1, coef2, noise=rec["n1"], act=True, red=red1)
-        grads[pre + "bias_1"] = red1[:, 0].reshape(1, Cc, 1, 1)
-        grads[pre + "noise_weight_1"] = red1[:, 1].reshape(1, Cc, 1, 1)
-        gW1 = ops.zeros(tuple(blk.conv_1.weight.shape), dev)
-        ops.conv_wgrad(g_pre1, x, gW1, rec["sc1"], rec["sh1"])
-        grads[pre + "conv_1.weight"] = gW1
+        if params:
+            grads[pre + "bias_1"] = red1[:, 0].reshape(1, Cc, 1, 1)
+            grads[pre + "noise_weight_1"] = red1[:, 1].reshape(1, Cc, 1, 1)
+            gW1 = ops.zeros(tuple(blk.conv_1.weight.shape), dev)
+            ops.conv_wgrad(g_pre1, x, gW1, rec["sc1"], rec["sh1"])
+            grads[pre + "conv_1.weight"] = gW1
         dots1 = ops.zeros((B, Cc, 2), dev)
         g_y1 = ops.conv2d(g_pre1, _packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
         coef1 = ops.in_bwd_coef(dots1, gms1, rec["musig1"], rec["sc1"], rec["sh1"], N)
         g_out = ops.in_bwd(g_y1, x, coef1, extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
-    fr = ops.fromrgb_bwd(g_out, saved["x0"], saved["img"].float())
-    C0 = E.startf
-    grads["FromRGB.from_rgb.weight"] = fr[:, :3].reshape(C0, 3, 1, 1)
-    grads["FromRGB.from_rgb.bias"] = fr[:, 3]
+    if params:
+        fr = ops.fromrgb_bwd(g_out, saved["x0"], saved["img"].float())
+        C0 = E.startf
+        grads["FromRGB.from_rgb.weight"] = fr[:, :3].reshape(C0, 3, 1, 1)
+        grads["FromRGB.from_rgb.bias"] = fr[:, 3]
     g_img = ops.fromrgb_dgrad(g_out, saved["x0"], E.FromRGB.from_rgb.weight.detach()) if need_img else None
     out = []
     for name, p in E.named_parameters():
@@ -191,7 +211,11 @@ class BlurEncoderFunction(torch.autograd.Function):
         B = ctx.saved_acts["img"].shape[0]
         if g_w is None:
             g_w = torch.zeros((B, 2 * ctx.E.layer_count, ctx.E.latent_size), dtype=torch.float32, device=ctx.saved_acts["img"].device)
-        grads, g_img = blur_encoder_backward(ctx.E, ctx.saved_acts, g_w.float().contiguous(), g_x, need_img=ctx.need_img)
+        frozen = not any(ctx.needs_input_grad[3:])      # no encoder parameter requires a gradient: data gradient only
+        grads, g_img = blur_encoder_backward(ctx.E, ctx.saved_acts, g_w.float().contiguous(), g_x, need_img=ctx.need_img,
+                                             params=not frozen)
+        if frozen:
+            return (None, g_img, None) + (None,) * len(grads)
         if _DIRECT_ACCUMULATE:
             accumulate_param_grads(ctx.E, grads)
             return (None, g_img, None) + (None,) * len(grads)

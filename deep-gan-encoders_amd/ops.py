@@ -1222,3 +1222,61 @@ def upconv_fir(x, w_packed, cout, in_scale=None, out_scale=None, bias=None, bias
     else:
         launch()
     return y
+
+
+# ------------------------------------------------------------------ inversion loop (embedding_v2.py)
+TRACK_ARM_AT, TRACK_ARM_AFTER = 0, 1        # include/dge_hip.h DGE_TRACK_ARM_*
+
+
+def latent_pnorm(w, p=2, out=None, out_l2=None):
+    """||w||_p over the whole tensor (Tensor.norm(p), integer p >= 1) -> device scalar []; `out_l2` (optional [] / [1] f32) also
+    receives ||w||_2.  Deterministic: one workgroup, fixed-order reduction."""
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=w.device)
+    check(lib().dge_latent_pnorm_fwd(_f32(w.contiguous()), _p(out), _f32(out_l2), w.numel(), int(p), _stream()), "dge_latent_pnorm_fwd")
+    return out
+
+
+def latent_l2(w, out=None):
+    """||w||_2 only -> device scalar []."""
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=w.device)
+    check(lib().dge_latent_pnorm_fwd(_f32(w.contiguous()), None, _p(out), w.numel(), 2, _stream()), "dge_latent_pnorm_fwd")
+    return out
+
+
+def latent_pnorm_bwd(w, norm, g, p=2, beta=1.0, gout=None):
+    """g += beta * gout * d||w||_p/dw (in place; g f32 contiguous, shape of w); 0 where the norm is 0."""
+    check(lib().dge_latent_pnorm_bwd(_f32(w.contiguous()), _f32(norm), _f32(gout), _f32(g), w.numel(), int(p), float(beta), _stream()),
+          "dge_latent_pnorm_bwd")
+    return g
+
+
+def wplus_lerp(w, avg, psi, out=None):
+    """w [B,L,D]; avg [D] or [L,D] -> avg + psi*(w - avg) [B,L,D]"""
+    B, L, D = w.shape
+    if out is None:
+        out = torch.empty((B, L, D), dtype=torch.float32, device=w.device)
+    stride = D if avg.numel() == L * D else 0
+    check(lib().dge_wplus_lerp(_f32(w.contiguous()), _f32(avg.contiguous()), stride, float(psi), _p(out), B, L, D, _stream()),
+          "dge_wplus_lerp")
+    return out
+
+
+def wplus_lerp_bwd(g, psi, out=None, accumulate=False):
+    """-> psi*g (accumulate: out += psi*g)"""
+    g = g.float().contiguous()
+    if out is None:
+        out = torch.empty_like(g)
+    check(lib().dge_wplus_lerp_bwd(_p(g), float(psi), _f32(out), g.numel(), 1 if accumulate else 0, _stream()), "dge_wplus_lerp_bwd")
+    return out
+
+
+def embed_track(loss, norm, w, istate, fstate, best_loss_w, best_norm_w, events, arm_rule, arm_iter, loss_hyst, norm_hyst):
+    """One tracker update (include/dge_hip.h dge_embed_track): device scalars in, device state updated; no host sync."""
+    if istate.dtype != torch.int32:
+        raise DgeError("embed_track: istate must be int32")
+    cap = events.shape[0]
+    check(lib().dge_embed_track(_f32(loss), _f32(norm), _f32(w.contiguous()), w.numel(), _p(istate), _f32(fstate), _f32(best_loss_w),
+                                _f32(best_norm_w), _f32(events), int(cap), int(arm_rule), int(arm_iter), float(loss_hyst),
+                                float(norm_hyst), _stream()), "dge_embed_track")

@@ -602,6 +602,29 @@ int dge_mask2cam_blocks(int HW);
 int dge_mask2cam(const float* mask, const float* img, const int* lut, float* heat, float* cam, float* part, float* coef, int B,
                  int HW, dge_stream_t stream);
 
+/* ---- inversion loop (embedding_v2.py; reference embedding_v2_styleGAN1.py / embedding_v2_styleGAN2.py) ----------------- */
+/* out[0] = ||w||_p = (sum |w|^p)^(1/p) over all n values (Tensor.norm(p), integer p >= 1), out_l2[0] = ||w||_2; either may be
+ * NULL.  One workgroup, fixed-order tree: the same bits every run. */
+int dge_latent_pnorm_fwd(const float* w, float* out, float* out_l2, long n, int p, dge_stream_t stream);
+/* g += beta * gout[0] * sign(w)|w|^(p-1) / norm[0]^(p-1) (gout NULL: 1); 0 where norm[0] == 0 */
+int dge_latent_pnorm_bwd(const float* w, const float* norm, const float* gout, float* g, long n, int p, float beta,
+                         dge_stream_t stream);
+/* out[b,l,:] = avg[l*avg_stride + :] + psi*(w[b,l,:] - avg[...]) on [B,L,D] (truncation trick on every row of a W+ code;
+ * avg_stride 0: avg [D], D: avg [L,D]) */
+int dge_wplus_lerp(const float* w, const float* avg, int avg_stride, float psi, float* out, int B, int L, int D, dge_stream_t stream);
+/* gw = psi*g (accumulate != 0: gw += psi*g) */
+int dge_wplus_lerp_bwd(const float* g, float psi, float* gw, long n, int accumulate, dge_stream_t stream);
+/* Best-loss / best-norm trackers of one iteration, from device scalars only (loss, norm = ||w||_2) and the latent w [n].
+ * istate int[4] = (iteration, events written, events dropped, armed), fstate float[2] = (min_loss, min_norm); the kernel
+ * advances the iteration.  Arming: DGE_TRACK_ARM_AT (at iteration arm_iter min_loss := loss, checks from there on) or
+ * DGE_TRACK_ARM_AFTER (checks for iteration > arm_iter).  min_loss > loss*loss_hyst -> event (it, 0, loss, norm), best_loss_w := w;
+ * norm_hyst > 0 and min_norm > norm*norm_hyst -> event (it, 1, loss, norm), best_norm_w := w.  events float[cap][4] is a ring. */
+#define DGE_TRACK_ARM_AT 0
+#define DGE_TRACK_ARM_AFTER 1
+int dge_embed_track(const float* loss, const float* norm, const float* w, long n, int* istate, float* fstate, float* best_loss_w,
+                    float* best_norm_w, float* events, int cap, int arm_rule, int arm_iter, float loss_hyst, float norm_hyst,
+                    dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1241,6 +1241,139 @@ def gen_latent_fixtures():
 
 SECTIONS["latent"] = gen_latent_fixtures
 
+def gen_embed_v2():
+    """Two iterations of the reference's v2 inversion loop body (embedding_v2_styleGAN1.py:82-131, embedding_v2_styleGAN2.py:86-149) for
+    StyleGAN1 / StyleGAN2 x encoder / W+ optimisation, batch 1, 64x64, restated with the decisions of embedding_v2.py's docstring:
+    all three image windows carry gradient, StyleGAN1 encodes imgs2 before the phase-1 step and StyleGAN2 after it, W-mode
+    StyleGAN1 const2 is a constant, W-mode StyleGAN2 has no const term, the StyleGAN2 generator is synthesis(avg + 0.7*(w - avg))
+    with its fixed noise.  Every noise tensor is captured (names embed_v2.<case>.it<k>.noise<i>)."""
+    import warnings
+    import model.stylegan1.net as SG1
+    import model.E.E_Blur as EB
+    from model.stylegan2_generator import StyleGAN2Generator
+    import training_utils as TU
+    from model.utils.custom_adam import LREQAdam
+    from oracle import lpips_ref as LR
+    from tests.helpers import s2_shapes
+
+    L = 5
+    LP = LR.seeded_params(0)
+    lp = lambda a, b: LR.lpips(LP, a, b)
+    imgs1 = torch.tanh(R.randn("embed_v2.img", (1, 3, 64, 64), 73, 0.8))
+    out = {"imgs1": imgs1}
+    for gen in ("sg1", "sg2"):
+        for mode in ("E", "W"):
+            tag = f"{gen}_{mode}"
+            if gen == "sg1":
+                Gs = SG1.Generator(startf=16, maxf=64, layer_count=L, latent_size=512, channels=3)
+                sd = R.fill_encoder(shapes_of(Gs.state_dict()), seed=43)
+                for k in sd:
+                    if k.endswith("blur.weight"):
+                        sd[k] = Gs.state_dict()[k].clone()
+                    if k == "const":
+                        sd[k] = R.randn("sg1step.const", tuple(sd[k].shape), 43)
+                Gs.load_state_dict(sd)
+                gfun = lambda w: Gs.forward(w, L - 1)
+                beta = 1e-3
+            else:
+                G2 = StyleGAN2Generator(64, fmaps_base=2048, fmaps_max=128)
+                G2.load_state_dict(R.fill_s2(s2_shapes(64, fmaps_base=2048, fmaps_max=128), seed=11))
+                G2.eval()
+                for p_ in G2.parameters():
+                    p_.requires_grad_(False)
+                avg = G2.truncation.w_avg
+                gfun = lambda w: G2.synthesis(avg + 0.7 * (w - avg), randomize_noise=False)["image"]
+                beta = 3e-4
+            E = EB.BE(startf=16, maxf=64, layer_count=L)
+            esd = R.fill_encoder(shapes_of(E.state_dict()), seed=71)
+            for k in esd:
+                if k.endswith("blur.weight"):
+                    esd[k] = E.state_dict()[k].clone()
+            E.load_state_dict(esd)
+            const2 = w1 = None
+            if mode == "E":
+                opt = LREQAdam([{"params": E.parameters()}], lr=0.005, betas=(0.0, 0.99), weight_decay=0)
+            else:
+                if gen == "sg1":
+                    with _NoiseFeeder(f"embed_v2.{tag}.init", 2) as nf:
+                        c0, w0 = E(imgs1)
+                    out[f"{tag}_init_noise_shapes"] = np.array([list(s_) for s_ in nf.log])
+                    const2, w1 = c0.detach(), w0.detach()
+                else:
+                    w1 = R.randn(f"embed_v2.{tag}.w0", (1, 2 * L, 512), 5)
+                w1.requires_grad = True
+                out[f"{tag}_w0"] = w1.detach().clone()
+                opt = LREQAdam([{"params": w1}], lr=0.005, betas=(0.0, 0.99), weight_decay=0)
+            for it in range(2):
+                pre = f"{tag}_it{it}"
+                with _NoiseFeeder(f"embed_v2.{tag}.it{it}", 2) as nf, warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    split = []
+                    if mode == "E":
+                        const2, w1 = E(imgs1)
+                    split.append(nf.i)
+                    imgs2 = gfun(w1)
+                    split.append(nf.i)
+                    if gen == "sg1":
+                        const3, w2 = E(imgs2)
+                    loss_imgs, _ = TU.space_loss(imgs1, imgs2, lpips_model=lp)
+                    m1 = imgs1[:, :, :, imgs1.shape[3] // 8:-imgs1.shape[3] // 8]
+                    m2 = imgs2[:, :, :, imgs2.shape[3] // 8:-imgs2.shape[3] // 8]
+                    loss_medium, _ = TU.space_loss(m1, m2, lpips_model=lp)
+                    o = imgs1.shape[2] // 8 + imgs1.shape[2] // 32
+                    loss_small, _ = TU.space_loss(imgs1[:, :, o:-o, o:-o], imgs2[:, :, o:-o, o:-o], lpips_model=lp)
+                    opt.zero_grad()
+                    loss_msiv = loss_imgs + loss_medium * 0.125 * 3 + loss_small * 0.125 * 5
+                    loss_msiv.backward(retain_graph=True)
+                    if mode == "E":
+                        out[f"{pre}_grad1:decode_block.0.conv_1.weight"] = E.decode_block[0].conv_1.weight.grad.clone()
+                        out[f"{pre}_grad1:decode_block.2.inver_mod1.bias"] = E.decode_block[2].inver_mod1.bias.grad.clone()
+                        out[f"{pre}_grad1:FromRGB.from_rgb.weight"] = E.FromRGB.from_rgb.weight.grad.clone()
+                    else:
+                        out[f"{pre}_grad1:w1"] = w1.grad.clone()
+                    opt.step()
+                    if gen == "sg2":
+                        const3, w2 = E(imgs2)
+                    split.append(nf.i)
+                    loss_w, _ = TU.space_loss(w1, w2, image_space=False)
+                    lat = loss_w
+                    loss_c1 = torch.tensor(0.0)
+                    if const2 is not None:
+                        loss_c1, _ = TU.space_loss(const2, const3, image_space=False)
+                        lat = loss_w + loss_c1
+                    nrm = w1.norm(p=2)
+                    loss_mslv = lat * 0.01 + nrm * beta
+                    opt.zero_grad()
+                    loss_mslv.backward()
+                    if mode == "E":
+                        out[f"{pre}_grad2:decode_block.0.conv_1.weight"] = E.decode_block[0].conv_1.weight.grad.clone()
+                        out[f"{pre}_grad2:decode_block.2.inver_mod1.bias"] = E.decode_block[2].inver_mod1.bias.grad.clone()
+                        out[f"{pre}_grad2:FromRGB.from_rgb.weight"] = E.FromRGB.from_rgb.weight.grad.clone()
+                    else:
+                        out[f"{pre}_grad2:w1"] = w1.grad.clone()
+                    opt.step()
+                if it == 0:
+                    out[f"{tag}_noise_shapes"] = np.array([list(s_) for s_ in nf.log])
+                    out[f"{tag}_noise_split"] = np.array(split)
+                out[f"{pre}_w1"] = w1.detach().clone()
+                out[f"{pre}_w2"] = w2.detach().clone()
+                if it == 0:             # (iteration 1 is pinned by w1 / w2 / the losses: keeps the file under 1 MiB)
+                    out[f"{pre}_imgs2"] = imgs2.detach().clone()
+                out[f"{pre}_const3"] = const3.detach().clone()
+                if const2 is not None:
+                    out[f"{pre}_const2"] = const2.detach().clone()
+                out[f"{pre}_losses"] = np.array([float(loss_msiv.detach()), float(loss_imgs), float(loss_medium), float(loss_small), float(loss_w),
+                                                 float(loss_c1), float(nrm), float(loss_mslv)])
+                if mode == "E":
+                    ck = R.checksum({k: v for k, v in E.state_dict().items() if not k.endswith("blur.weight")})
+                else:
+                    ck = R.checksum({"w1": w1.detach()})
+                out[f"{pre}_param_checksum"] = np.array(ck)
+    save_npz("embed_v2.npz", **out)
+
+
+SECTIONS["embed_v2"] = gen_embed_v2
+
 if __name__ == "__main__":
     todo = sys.argv[1:] or list(SECTIONS)
     for s_ in todo:
