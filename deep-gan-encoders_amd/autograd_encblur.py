@@ -36,7 +36,8 @@ def blur_encoder_forward(E, img, noises=None, save=False):
     dt = _dt(E.compute_dtype)
     dev = img.device
     B, _, R, _ = img.shape
-    if noises is None:
+    noise, heads = getattr(E, "noise", True), getattr(E, "heads", True)       # E_Blur_Z (BlurBEZ): neither
+    if noises is None and noise:
         noises = blur_noises(E, B, R, dev)
     cache = E.__dict__.setdefault("_pack_cache", {})
     zeros = lambda c: ops.zeros((B, c, 2), dev)
@@ -50,27 +51,34 @@ def blur_encoder_forward(E, img, noises=None, save=False):
         last = not blk.has_last_conv
         has3 = Cc != C2
         musig1, sc1, sh1 = ops.stats_finalize(stats, H * H)
-        w1 = ops.linear(musig1, blk.inver_mod1.weight.detach(), blk.inver_mod1.bias.detach())
-        n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
+        w1 = ops.linear(musig1, blk.inver_mod1.weight.detach(), blk.inver_mod1.bias.detach()) if heads else None
+        n1 = nw1 = None
+        if noise:
+            n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
+            nw1 = blk.noise_weight_1.detach().reshape(-1)
         st1 = zeros(Cc)
         x1 = ops.conv2d(x, _packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
-                        noise_w=blk.noise_weight_1.detach().reshape(-1), bias=blk.bias_1.detach().reshape(-1),
-                        act=ops.ACT_LRELU, stats=st1)
+                        noise_w=nw1, bias=blk.bias_1.detach().reshape(-1), act=ops.ACT_LRELU, stats=st1)
         musig2, sc2, sh2 = ops.stats_finalize(st1, H * H)
-        w2 = ops.linear(musig2, blk.inver_mod2.weight.detach(), blk.inver_mod2.bias.detach())
+        w2 = ops.linear(musig2, blk.inver_mod2.weight.detach(), blk.inver_mod2.bias.detach()) if heads else None
         rec = dict(x=x, musig1=musig1, sc1=sc1, sh1=sh1, n1=n1, x1=x1, musig2=musig2, sc2=sc2, sh2=sh2) if save else None
         nstats = zeros(C2) if not last else None
         if not last:
             y2 = ops.blur_noise_act(ops.blend(x1, sc=sc2, sh=sh2), None, None, None, blur=True, act=False)   # blur(IN2(x1))
             wpk = _packed(cache, blk.conv_2, dt, ops.PACK_FWD, H)
-            n2 = noises[ni]; ni += 1
-            nw2, b2 = blk.noise_weight_2.detach().reshape(-1), blk.bias_2.detach().reshape(-1)
+            n2 = nw2 = None
+            if noise:
+                n2 = noises[ni]; ni += 1
+                nw2 = blk.noise_weight_2.detach().reshape(-1)
+            b2 = blk.bias_2.detach().reshape(-1)
             if blk.fused_scale:        # conv(s2, transform_kernel) == pool(conv); noise/bias/lrelu at half resolution
-                n2 = n2.reshape(B, H // 2, H // 2).contiguous()
+                if noise:
+                    n2 = n2.reshape(B, H // 2, H // 2).contiguous()
                 t = ops.blend(ops.conv2d(y2, wpk, C2, 3), pool=True)
                 a2 = x2 = ops.blur_noise_act(t, n2, nw2, b2, blur=False)
             else:
-                n2 = n2.reshape(B, H, H).contiguous()
+                if noise:
+                    n2 = n2.reshape(B, H, H).contiguous()
                 a2 = ops.conv2d(y2, wpk, C2, 3, noise=n2, noise_w=nw2, bias=b2, act=ops.ACT_LRELU)
                 x2 = ops.blend(a2, pool=True)
             xp = ops.blend(x, pool=True)
@@ -89,7 +97,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
             saved["blocks"].append(rec)
         ws = [w2, w1] + ws
         x, stats = out, nstats
-    return ops.nhwc_to_nchw(x), torch.stack(ws, dim=1), saved
+    return ops.nhwc_to_nchw(x), (torch.stack(ws, dim=1) if heads else None), saved
 
 
 def _linear_dgrad(lin, g_w):
@@ -106,11 +114,14 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
     params=False (frozen encoder: the W+ inversion mode of embedding_v2.py): the data gradient alone.  No weight-gradient
     launch runs (conv_wgrad, the dense weight gradients, fromrgb_bwd) and the side reductions that only feed parameter
     gradients are dropped; the data path is the same launches in the same order, so the image gradient is the same bits.
-    Every parameter gradient is None."""
+    Every parameter gradient is None.
+    An encoder without heads (E.heads False, E_Blur_Z) takes g_w=None: the statistics gradient fed to in_bwd_coef is then zero.
+    Without noise (E.noise False) no noise-weight gradient is formed."""
     cache = E.__dict__.setdefault("_pack_cache", {})
-    dev = g_w.device
+    noise, heads = getattr(E, "noise", True), getattr(E, "heads", True)
+    dev = saved["img"].device
     L = E.layer_count
-    B = g_w.shape[0]
+    B = saved["img"].shape[0]
     grads = {}
     R = saved["img"].shape[2]
     dt = ops.dtype_of(saved["x0"])
@@ -126,11 +137,14 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
         N = H * H
         last = not blk.has_last_conv
         has3 = Cc != C2
-        g_w2, g_w1 = g_w[:, 2 * (L - 1 - j)], g_w[:, 2 * (L - 1 - j) + 1]
-        if params:
+        if not heads:
+            gms2 = gms1 = None
+        elif params:
+            g_w2, g_w1 = g_w[:, 2 * (L - 1 - j)], g_w[:, 2 * (L - 1 - j) + 1]
             gms2 = _linear_backward(blk.inver_mod2, g_w2, rec["musig2"], grads, pre + "inver_mod2")
             gms1 = _linear_backward(blk.inver_mod1, g_w1, rec["musig1"], grads, pre + "inver_mod1")
         else:
+            g_w2, g_w1 = g_w[:, 2 * (L - 1 - j)], g_w[:, 2 * (L - 1 - j) + 1]
             gms2, gms1 = _linear_dgrad(blk.inver_mod2, g_w2), _linear_dgrad(blk.inver_mod1, g_w1)
         x, x1 = rec["x"], rec["x1"]
         extra, extra_pool, extra_scale = None, False, 1.0
@@ -145,7 +159,8 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
                 g_c2 = ops.act_bwd(g_out, rec["a2"], rec["n2"], pool=True, scale=0.111 * 0.25, red=red2)
             if params:
                 grads[pre + "bias_2"] = red2[:, 0].reshape(1, C2, 1, 1)
-                grads[pre + "noise_weight_2"] = red2[:, 1].reshape(1, C2, 1, 1)
+                if noise:
+                    grads[pre + "noise_weight_2"] = red2[:, 1].reshape(1, C2, 1, 1)
                 gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
                 ops.conv_wgrad(g_c2, rec["y2"], gW2)
                 grads[pre + "conv_2.weight"] = gW2
@@ -174,7 +189,8 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
         g_pre1 = ops.in_bwd(g_y2, x1, coef2, noise=rec["n1"], act=True, red=red1)
         if params:
             grads[pre + "bias_1"] = red1[:, 0].reshape(1, Cc, 1, 1)
-            grads[pre + "noise_weight_1"] = red1[:, 1].reshape(1, Cc, 1, 1)
+            if noise:
+                grads[pre + "noise_weight_1"] = red1[:, 1].reshape(1, Cc, 1, 1)
             gW1 = ops.zeros(tuple(blk.conv_1.weight.shape), dev)
             ops.conv_wgrad(g_pre1, x, gW1, rec["sc1"], rec["sh1"])
             grads[pre + "conv_1.weight"] = gW1
@@ -220,6 +236,65 @@ class BlurEncoderFunction(torch.autograd.Function):
             accumulate_param_grads(ctx.E, grads)
             return (None, g_img, None) + (None,) * len(grads)
         return (None, g_img, None) + tuple(grads)
+
+
+def _out_z_window(E, xo):
+    """out_z = Conv2d(512, 512, 3, stride 2, padding 0) on the [B, 512, 4, 4] trunk output (E_Blur_Z.py:102,137) reads the top-left
+    3x3 window only and produces one pixel: a dense layer over that window, flattened (c, kh, kw) as the weight is."""
+    B, Cc, H, W = xo.shape
+    if H != 4 or W != 4:
+        raise ValueError(f"E_Blur_Z: out_z maps a 4x4 trunk output to 1x1; this encoder/input size gives {H}x{W}")
+    return xo[:, :, :3, :3].contiguous().view(B, Cc * 9)
+
+
+class BlurZEncoderFunction(torch.autograd.Function):
+    """E_Blur_Z.BE: the E_Blur trunk without noise and heads (blur_encoder_forward / _backward) -> out_z -> z [B, 512, 1, 1].
+    out_z runs on the existing dense kernels over the gathered 3x3 window (dge_linear forward, dge_linear_t data gradient,
+    dge_dense_wgrad weight / bias gradient): at 1x1 output the convolution is exactly that matrix product, [B, 4608] x [4608, 512],
+    and B <= 8 rows give a conv kernel nothing to tile.  Rows / columns 3 of the trunk output get zero gradient, as in the
+    reference.  The backward reads out_z's weight as it is then (the reference's second backward runs on weights the first
+    optimizer step already changed)."""
+
+    @staticmethod
+    def forward(ctx, E, img, *params):
+        need = any(ctx.needs_input_grad[1:])
+        xo, _, saved = blur_encoder_forward(E, img.detach(), None, save=need)
+        win = _out_z_window(E, xo)
+        oz = E.out_z
+        z = ops.linear(win, oz.weight.detach().reshape(oz.weight.shape[0], -1), oz.bias.detach())
+        ctx.E, ctx.saved_acts, ctx.win, ctx.C = E, saved, win, xo.shape[1]
+        ctx.need_img = ctx.needs_input_grad[1]
+        return z.view(z.shape[0], z.shape[1], 1, 1)
+
+    @staticmethod
+    def backward(ctx, g_z):
+        if ctx.saved_acts is None:
+            raise RuntimeError("E_Blur_Z forward ran without saved activations")
+        E, win, Cc = ctx.E, ctx.win, ctx.C
+        B = win.shape[0]
+        oz = E.out_z
+        Wz = oz.weight.detach().reshape(oz.weight.shape[0], -1)
+        g = g_z.float().reshape(B, -1).contiguous()
+        g_win = torch.empty_like(win)
+        ops.linear_t(g, Wz, g_win)
+        g_x = torch.zeros((B, Cc, 4, 4), dtype=torch.float32, device=g.device)
+        g_x[:, :, :3, :3] = g_win.view(B, Cc, 3, 3)
+        frozen = not any(ctx.needs_input_grad[2:])
+        grads, g_img = blur_encoder_backward(E, ctx.saved_acts, None, g_x, need_img=ctx.need_img, params=not frozen)
+        if frozen:
+            return (None, g_img) + (None,) * len(grads)
+        gW = torch.empty_like(oz.weight)
+        gb = torch.empty_like(oz.bias)
+        ops.dense_wgrad(g, win, gW.view(Wz.shape), gb)
+        for k, (name, _) in enumerate(E.named_parameters()):
+            if name == "out_z.weight":
+                grads[k] = gW
+            elif name == "out_z.bias":
+                grads[k] = gb
+        if _DIRECT_ACCUMULATE:
+            accumulate_param_grads(E, grads)
+            return (None, g_img) + (None,) * len(grads)
+        return (None, g_img) + tuple(grads)
 
 
 import os as _os

@@ -544,8 +544,8 @@ def build_models(img_size=1024, start_features=16, compute_dtype="bf16", device=
     return G, E, LP
 
 
-def build_models_sg1(img_size=256, start_features=64, compute_dtype="bf16", device="cuda", lpips=True, seed=0):
-    """Models of BASELINE config 2 (StyleGAN1, E_align_s2.py:27-46) with seeded random-init weights."""
+def build_models_sg1(img_size=256, start_features=64, compute_dtype="bf16", device="cuda", lpips=True, seed=0, encoder=True):
+    """Models of BASELINE config 2 (StyleGAN1, E_align_s2.py:27-46) with seeded random-init weights (encoder=False: E is None)."""
     from .stylegan1 import Generator, Mapping
     from .encoder import BE
     from .lpips import LPIPS
@@ -560,7 +560,7 @@ def build_models_sg1(img_size=256, start_features=64, compute_dtype="bf16", devi
             if "noise_weight" in name:
                 p.fill_(0.05)
     Gm.buffer1 = torch.randn(2 * L, 512) * 0.1
-    E = BE(startf=start_features, maxf=512, layer_count=L, compute_dtype=compute_dtype).to(device)
+    E = BE(startf=start_features, maxf=512, layer_count=L, compute_dtype=compute_dtype).to(device) if encoder else None
     LP = LPIPS(compute_dtype=compute_dtype).to(device) if lpips else None
     return Gs, Gm, E, LP
 
@@ -614,12 +614,13 @@ def load_lpips_weights(LP, vgg_weights=None, lin_weights=None, allow_standin=Fal
     return LP
 
 
-def load_models(args, device="cuda", lpips=True):
+def load_models(args, device="cuda", lpips=True, encoder=True):
     """Models + checkpoints of one --mtype, shared by `train` and the inference entry points (infer.main).  The three
     checkpoint containers of the reference: mtype 2 / 3 a dict holding `generator_smooth` (or `generator`)
     (E_align_s2.py:51-55, :67-77); mtype 1 a DIRECTORY with Gs_dict.pth, Gm_dict.pth and center_tensor.pt (:30-35);
     mtype 4 a bare state_dict next to --config_dir (:79-86); the encoder is a bare state_dict (--checkpoint_dir_E).
-    Everything is read with map_location='cpu' and moved by load_state_dict.  Returns (G, Gm | None, E, LP | None)."""
+    Everything is read with map_location='cpu' and moved by load_state_dict.  Returns (G, Gm | None, E, LP | None).
+    encoder=False (--mtype 1 only; callers with an encoder of their own): no E is built, E is None."""
     cd = getattr(args, "compute_dtype", "bf16")
     small = {k: getattr(args, k) for k in ("fmaps_base", "fmaps_max", "enc_maxf") if getattr(args, k, None) is not None}
     if args.mtype == 2:
@@ -629,7 +630,7 @@ def load_models(args, device="cuda", lpips=True):
             ckpt = torch.load(args.checkpoint_dir_GAN, map_location="cpu")
             G.load_state_dict(ckpt["generator_smooth"] if "generator_smooth" in ckpt else ckpt["generator"])
     elif args.mtype == 1:
-        G, Gm, E, LP = build_models_sg1(args.img_size, args.start_features, cd, device=device, lpips=lpips)
+        G, Gm, E, LP = build_models_sg1(args.img_size, args.start_features, cd, device=device, lpips=lpips, encoder=encoder)
         if args.checkpoint_dir_GAN:                 # E_align_s2.py:30-35: a directory holding the three files
             G.load_state_dict(torch.load(args.checkpoint_dir_GAN + "Gs_dict.pth", map_location="cpu"))
             Gm.load_state_dict(torch.load(args.checkpoint_dir_GAN + "Gm_dict.pth", map_location="cpu"))
@@ -649,7 +650,7 @@ def load_models(args, device="cuda", lpips=True):
             G.load_state_dict(torch.load(args.checkpoint_dir_GAN, map_location="cpu"))
     else:
         raise ValueError("--mtype must be 1 (StyleGAN1), 2 (StyleGAN2), 3 (PGGAN) or 4 (BigGAN)")
-    if getattr(args, "checkpoint_dir_E", None) is not None:
+    if E is not None and getattr(args, "checkpoint_dir_E", None) is not None:
         E.load_state_dict(torch.load(args.checkpoint_dir_E, map_location="cpu"))
     return G, Gm, E, LP
 

@@ -67,6 +67,70 @@ class BlurBE(nn.Module):
         return BlurEncoderFunction.apply(self, img, noises, *list(self.parameters()))
 
 
+# ----------------------------------------------------------------------------------- E_Blur_Z
+class BlurBEZBlock(nn.Module):
+    """E_Blur_Z.BEBlock (model/E/Ablation_Study/E_Blur_Z.py:17-89): BlurBEBlock without noise weights and inver_mod heads."""
+
+    def __init__(self, inputs, outputs, latent_size, has_last_conv=True, fused_scale=True):
+        super().__init__()
+        self.has_last_conv, self.fused_scale, self.inputs, self.outputs = has_last_conv, fused_scale, inputs, outputs
+        self.bias_1 = nn.Parameter(torch.zeros(1, inputs, 1, 1))
+        self.conv_1 = ln.Conv2d(inputs, inputs, 3, 1, 1, bias=False)
+        self.bias_2 = nn.Parameter(torch.zeros(1, outputs, 1, 1))
+        self.blur = Blur(inputs)
+        if has_last_conv:
+            self.conv_2 = ln.Conv2d(inputs, outputs, 3, 1, 1, bias=False)     # stride 2 is realised as conv + pool (see module doc)
+        if inputs != outputs:
+            self.conv_3 = ln.Conv2d(inputs, outputs, 1, 1, 0)
+
+
+class _OutZ(nn.Module):
+    """ln.Conv2d(512, 512, 3, 2): stride 2, padding 0, bias, implicit lreq (weight used as stored, tagged for LREQAdam)."""
+
+    def __init__(self, inputs, outputs, k=3):
+        super().__init__()
+        std = np.sqrt(2.0) / np.sqrt(k * k * inputs)
+        self.weight = nn.Parameter(torch.randn(outputs, inputs, k, k) * std)
+        setattr(self.weight, "lr_equalization_coef", std)
+        self.bias = nn.Parameter(torch.zeros(outputs))
+        setattr(self.bias, "lr_equalization_coef", 1.0)
+
+
+class BlurBEZ(nn.Module):
+    """E_Blur_Z.BE (model/E/Ablation_Study/E_Blur_Z.py:92-138, the encoder of ablation_utils/1.E_align_z.py): the E_Blur trunk
+    without noise and heads, then out_z = Conv2d(512, 512, 3, 2) maps the 4x4 trunk output to the Z code [B, 512, 1, 1].
+    forward -> (z, tensor(0)), differentiable w.r.t. every parameter and the image (autograd_encblur.BlurZEncoderFunction)."""
+
+    noise = False
+    heads = False
+
+    def __init__(self, startf=16, maxf=512, layer_count=9, latent_size=512, channels=3, compute_dtype="bf16"):
+        super().__init__()
+        _dt(compute_dtype)
+        last_in = min(maxf, startf * 2 ** (layer_count - 1))
+        last_out = min(maxf, startf * 2 ** layer_count)
+        if last_in != last_out:
+            raise ValueError(f"E_Blur_Z: the last block must not change width (startf*2^(layer_count-1) = {startf * 2 ** (layer_count - 1)} "
+                             f"< maxf = {maxf}): the reference's 0.111*x + 0.889*conv_3(residual) cannot broadcast there")
+        if last_out != 512:
+            raise ValueError(f"E_Blur_Z: out_z is Conv2d(512, 512, 3, 2), so the last block must output 512 channels (got {last_out})")
+        self.maxf, self.startf, self.latent_size, self.layer_count, self.compute_dtype = maxf, startf, latent_size, layer_count, compute_dtype
+        self.decode_block = nn.ModuleList()
+        self.FromRGB = FromRGB(channels, startf)
+        self.out_z = _OutZ(512, 512)
+        inputs, outputs, resolution = startf, startf * 2, 1024
+        for i in range(layer_count):
+            self.decode_block.append(BlurBEZBlock(inputs, outputs, latent_size, i + 1 != layer_count, fused_scale=resolution >= 128))
+            inputs, outputs = min(maxf, inputs * 2), min(maxf, outputs * 2)
+            resolution /= 2
+
+    def forward(self, img, block_num=9):
+        if block_num != 9:
+            raise ValueError("progressive block_num != 9 is not used by the reference's scripts")
+        from .autograd_encblur import BlurZEncoderFunction
+        return BlurZEncoderFunction.apply(self, img, *list(self.parameters())), torch.tensor(0)
+
+
 # ----------------------------------------------------------------------------------- E_PG
 class _AffineIN(nn.Module):
     def __init__(self, c):

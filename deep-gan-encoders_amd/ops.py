@@ -293,16 +293,48 @@ def linear(x, w, bias=None, wscale=1.0, bscale=1.0, add=0.0, act=ACT_NONE, gain=
     return out
 
 
-def dense_chain(x, layers, pixelnorm=False, eps=1e-8):
-    """x [B, I] f32 through a chain of up to 8 dense layers in one launch (dge_dense_chain; bit-identical to the per-layer linear()
-    calls).  layers: objects with weight [O, I], bias, wscale, bscale, additional_bias, act, gain (DenseBlock)."""
+def _dense_layers(layers):
     from ._lib import DenseLayer
-    B = x.shape[0]
     arr = (DenseLayer * len(layers))()
     for e, L in zip(arr, layers):
         e.w, e.bias = _p(L.weight.detach()), _p(L.bias.detach())
         e.O, e.I = L.weight.shape
         e.wscale, e.bscale, e.add, e.act, e.gain = float(L.wscale), float(L.bscale), float(L.additional_bias), int(L.act), float(L.gain)
+    return arr
+
+
+def mapping_bwd(z, layers, g, coefs=None, acts=None, pixelnorm=True, eps=1e-8):
+    """Data gradient of w+ = lerp(avg, broadcast_L(chain(z)), coefs) in one launch (dge_mapping_bwd): z [B, I] f32, g = dL/dw+
+    [B, L, O] f32, coefs [L] f32 or None (plain broadcast), acts: the forward's layer outputs ([B, O_l] each; the leaky-relu masks
+    are read off them) or None (the launch recomputes the forward) -> dz [B, I].  The same bits every run."""
+    B, L = g.shape[0], g.shape[1]
+    if not z.is_cuda or z.stride(1) != 1:
+        raise DgeError("mapping_bwd: z must be a CUDA tensor with unit inner stride")
+    if z.shape[1] != layers[0].weight.shape[1] or z.shape[0] != B:
+        raise DgeError(f"mapping_bwd: z {tuple(z.shape)} does not match B = {B}, first layer width {layers[0].weight.shape[1]}")
+    g = g.float().contiguous()
+    if g.shape[2] != layers[-1].weight.shape[0]:
+        raise DgeError(f"mapping_bwd: gradient width {g.shape[2]} != last layer width {layers[-1].weight.shape[0]}")
+    if coefs is not None and coefs.numel() != L:
+        raise DgeError(f"mapping_bwd: {coefs.numel()} coefficients for {L} rows")
+    arr = arr_p = None
+    if acts is not None:
+        if len(acts) != len(layers) or any(tuple(a.shape) != (B, Ly.weight.shape[0]) for a, Ly in zip(acts, layers)):
+            raise DgeError("mapping_bwd: acts must hold one [B, O_l] output per layer")
+        arr = (C.c_void_p * len(acts))(*[_f32(a).value for a in acts])
+        arr_p = C.cast(arr, C.c_void_p)
+    dz = torch.empty((B, z.shape[1]), dtype=torch.float32, device=z.device)
+    check(lib().dge_mapping_bwd(_f32(z), z.stride(0), _dense_layers(layers), len(layers), arr_p, _p(g), L,
+                                _f32(None if coefs is None else coefs.contiguous()), _p(dz), dz.stride(0), B, 1 if pixelnorm else 0,
+                                float(eps), _stream()), "dge_mapping_bwd")
+    return dz
+
+
+def dense_chain(x, layers, pixelnorm=False, eps=1e-8):
+    """x [B, I] f32 through a chain of up to 8 dense layers in one launch (dge_dense_chain; bit-identical to the per-layer linear()
+    calls).  layers: objects with weight [O, I], bias, wscale, bscale, additional_bias, act, gain (DenseBlock)."""
+    B = x.shape[0]
+    arr = _dense_layers(layers)
     y = torch.empty((B, layers[-1].weight.shape[0]), dtype=torch.float32, device=x.device)
     if not x.is_cuda or x.stride(1) != 1:
         raise DgeError("dense_chain: x must be a CUDA tensor with unit inner stride")

@@ -133,23 +133,79 @@ class Mapping(nn.Module):
             inputs = outputs
         self.buffer1 = trunc_tensor          # plain attribute: not part of the state_dict (reference :452)
 
+    def chain(self):
+        """The 8 dense layers as dge_dense_chain / dge_mapping_bwd entries (implicit lreq: weights used as stored, lrelu 0.2)."""
+        return [_MappingLayer(getattr(self, "block_%d" % (i + 1)).fc) for i in range(self.mapping_layers)]
+
+    def truncation(self, coefs_m, dev, width):
+        """(centre [L or 1, width], coefs [L]) on `dev`, or None without buffer1.  Device copies are cached: the reference passes
+        CPU tensors every step (E_align_s2.py:35-41,105), re-uploading them would put two synchronising copies into each iteration."""
+        if self.buffer1 is None:
+            return None
+        key = (id(self.buffer1), getattr(self.buffer1, "_version", 0), id(coefs_m), getattr(coefs_m, "_version", 0), str(dev))
+        hit = self.__dict__.get("_trunc_cache")
+        if hit is None or hit[0] != key:
+            coefs = torch.as_tensor(coefs_m, dtype=torch.float32).reshape(-1)
+            if coefs.numel() == 1:
+                coefs = coefs.repeat(self.num_layers)
+            hit = (key, self.buffer1.to(dev).float().reshape(-1, width).contiguous(), coefs.to(dev).contiguous(), self.buffer1, coefs_m)
+            self.__dict__["_trunc_cache"] = hit
+        return hit[1], hit[2]
+
+    def _wplus(self, x, coefs_m):
+        tr = self.truncation(coefs_m, x.device, x.shape[1])
+        if tr is None:
+            return x.view(x.shape[0], 1, -1).repeat(1, self.num_layers, 1)
+        return ops.lerp_layers(x, tr[0], tr[1])
+
+    def activations(self, z):
+        """pixel norm + the 8 dense layers as chip-wide dge_pixelnorm / dge_linear launches (z [B, 512] f32 on the device) ->
+        the output of every layer; the last is w.  (dge_dense_chain would do this in one launch, bit for bit, but its one
+        workgroup per sample is slower at training batches: see the DGE_DENSE_CHAIN note in stylegan2_generator.py.)"""
+        acts = []
+        x = ops.pixelnorm(z)
+        for i in range(self.mapping_layers):
+            fc = getattr(self, "block_%d" % (i + 1)).fc
+            x = ops.linear(x, fc.weight.detach(), fc.bias.detach(), act=ops.ACT_LRELU)
+            acts.append(x)
+        return acts
+
     def forward(self, z, coefs_m=0):
+        """With grad enabled and `z.requires_grad` the result is differentiable w.r.t. z (MappingFunction: the same forward
+        launches, dz from dge_mapping_bwd); no mapping weight gradient is formed."""
+        if torch.is_grad_enabled() and z.requires_grad:
+            return MappingFunction.apply(self, z, coefs_m)
         with torch.no_grad():
             dev = self.block_1.fc.weight.device
-            x = ops.pixelnorm(z.to(dev).float().contiguous())
-            for i in range(self.mapping_layers):
-                fc = getattr(self, "block_%d" % (i + 1)).fc
-                x = ops.linear(x, fc.weight.detach(), fc.bias.detach(), act=ops.ACT_LRELU)
-            if self.buffer1 is None:
-                return x.view(x.shape[0], 1, -1).repeat(1, self.num_layers, 1)
-            # device copies of the truncation centre / coefficients are cached: the reference passes CPU tensors every
-            # step (E_align_s2.py:35-41,105), re-uploading them would put two synchronising copies into each iteration
-            key = (id(self.buffer1), getattr(self.buffer1, "_version", 0), id(coefs_m), getattr(coefs_m, "_version", 0), str(dev))
-            hit = self.__dict__.get("_trunc_cache")
-            if hit is None or hit[0] != key:
-                coefs = torch.as_tensor(coefs_m, dtype=torch.float32).reshape(-1)
-                if coefs.numel() == 1:
-                    coefs = coefs.repeat(self.num_layers)
-                hit = (key, self.buffer1.to(dev).float().reshape(-1, x.shape[1]).contiguous(), coefs.to(dev).contiguous(), self.buffer1, coefs_m)
-                self.__dict__["_trunc_cache"] = hit
-            return ops.lerp_layers(x, hit[1], hit[2])
+            x = self.activations(z.to(dev).float().contiguous())[-1]
+            return self._wplus(x, coefs_m)
+
+
+class _MappingLayer:
+    def __init__(self, fc):
+        self.weight, self.bias = fc.weight, fc.bias
+        self.wscale, self.bscale, self.additional_bias, self.act, self.gain = 1.0, 1.0, 0.0, ops.ACT_LRELU, 1.0
+
+
+class MappingFunction(torch.autograd.Function):
+    """w+ = Mapping(z) with dz from one dge_mapping_bwd launch (pixel norm, 8 dense layers and the lerp / broadcast transposed),
+    which reads the leaky-relu masks off the layer outputs this forward saved.
+    Gradients reach z only: the reference also accumulates the mapping's weight gradients (1.E_align_z.py:63-66 runs Gm with grad),
+    but no optimizer reads them - the same deliberate omission as the generator weight gradients."""
+
+    @staticmethod
+    def forward(ctx, M, z, coefs_m):
+        dev = M.block_1.fc.weight.device
+        z32 = z.detach().to(dev).float().contiguous()
+        acts = M.activations(z32)
+        ctx.M, ctx.coefs_m, ctx.z_dtype, ctx.z_dev = M, coefs_m, z.dtype, z.device
+        ctx.save_for_backward(z32, *acts)
+        return M._wplus(acts[-1], coefs_m)
+
+    @staticmethod
+    def backward(ctx, g):
+        z32, *acts = ctx.saved_tensors
+        M = ctx.M
+        tr = M.truncation(ctx.coefs_m, z32.device, g.shape[2])
+        dz = ops.mapping_bwd(z32, M.chain(), g, coefs=None if tr is None else tr[1], acts=acts)
+        return None, dz.to(device=ctx.z_dev, dtype=ctx.z_dtype), None

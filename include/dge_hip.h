@@ -625,6 +625,15 @@ int dge_embed_track(const float* loss, const float* norm, const float* w, long n
                     float* best_norm_w, float* events, int cap, int arm_rule, int arm_iter, float loss_hyst, float norm_hyst,
                     dge_stream_t stream);
 
+/* ---- Z-space encoder training (e_align_z.py; reference ablation_utils/1.E_align_z.py) --------------------------------------- */
+/* Data gradient of the StyleGAN1 mapping network, w+ = lerp(avg, broadcast_L(chain(pixel_norm(z))), coefs):
+ * dz[b, :I0] = d/dz of sum(g * w+), g [B, L, O_last] contiguous, coefs [L] (NULL: the plain broadcast, every row weighted 1).
+ * `layers` as dge_dense_chain (1 .. 8 layers, widths up to 512 and a multiple of 4, gain > 0); pixelnorm != 0: the chain input
+ * is pixel_norm(z).  acts: n pointers to the layer outputs the forward saved ([B, O_l] contiguous), the leaky-relu masks are
+ * read off them; NULL: the forward is recomputed with dge_dense_chain's arithmetic.  One workgroup per sample, no atomics. */
+int dge_mapping_bwd(const float* z, int ldz, const dge_dense_layer* layers, int n, const float* const* acts, const float* g, int L,
+                    const float* coefs, float* dz, int lddz, int B, int pixelnorm, float eps, dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1374,6 +1374,148 @@ def gen_embed_v2():
 
 SECTIONS["embed_v2"] = gen_embed_v2
 
+def _grad_entries(model, out, full_max=16384):
+    for k, p_ in model.named_parameters():
+        if p_.grad is None:
+            continue
+        g = p_.grad
+        out["norm:" + k] = g.norm()
+        out["grad:" + k] = g if g.numel() <= full_max else g.flatten()[:4096]
+
+
+def gen_mapping_grad():
+    """StyleGAN1 Mapping (model/stylegan1/net.py:441-466) output and the gradient w.r.t. z of a seeded linear functional of it,
+    with the truncation centre (lerp, coefs 0.7 on the first half of the layers, as 1.E_align_z.py:36-40) and without (broadcast)."""
+    import model.stylegan1.net as SG1
+    L = 10
+    Gm = SG1.Mapping(num_layers=L, mapping_layers=8, latent_size=512, dlatent_size=512, mapping_fmaps=512)
+    Gm.load_state_dict({k: R.randn("mapgrad.m." + k, tuple(v.shape), 71, 0.05 if k.endswith("weight") else 0.01)
+                        for k, v in Gm.state_dict().items() if k != "buffer1"})
+    layer_idx = torch.arange(L)[np.newaxis, :, np.newaxis]
+    ones = torch.ones(layer_idx.shape, dtype=torch.float32)
+    coefs = torch.where(layer_idx < L // 2, 0.7 * ones, ones)
+    out = {}
+    for tag, buf in (("", R.randn("mapgrad.buffer1", (L, 512), 72, 0.5)), ("_nobuf", None)):
+        Gm.buffer1 = buf
+        z = R.randn("mapgrad.z", (3, 512), 71).requires_grad_(True)
+        with _LreluTap() as tap:
+            w = Gm(z, coefs_m=coefs)
+        margin = min(float(x.abs().min()) / float(x.abs().max()) for x in tap.inputs)
+        assert margin > 1e-5, margin          # no pre-activation within rounding of the kink
+        gw = R.randn("mapgrad.gw" + tag, tuple(w.shape), 73)
+        (w * gw).sum().backward()
+        out["w" + tag], out["dz" + tag], out["kink_margin" + tag] = w.detach(), z.grad, np.array(margin)
+    save_npz("mapping_grad.npz", **out)
+
+
+SECTIONS["mapping_grad"] = gen_mapping_grad
+
+
+def _encz_model():
+    """E_Blur_Z.BE (model/E/Ablation_Study/E_Blur_Z.py) at startf 32 / maxf 512 / 5 blocks (widths 32 -> 512, the last block at
+    512), seeded parameters with the leaky-relu kinks cleared for a 64^2 input."""
+    import model.E.Ablation_Study.E_Blur_Z as EZ
+    E = EZ.BE(startf=32, maxf=512, layer_count=5)
+    sd = R.fill_encoder(shapes_of(E.state_dict()), seed=81)
+    for k in sd:
+        if k.endswith("blur.weight"):
+            sd[k] = E.state_dict()[k].clone()
+    E.load_state_dict(sd)
+    img = R.randn("ez.img", (2, 3, 64, 64), 81, 0.5)
+    nudged, margin = clear_kinks([lambda: E(img)], *enc_kink_owners(E, "has_last_conv"))
+    return E, img, nudged, margin
+
+
+def gen_encz_grad():
+    """Gradients of E_Blur_Z.BE w.r.t. every parameter and the input image for a seeded linear functional of z."""
+    E, img, nudged, margin = _encz_model()
+    with open(os.path.join(OUT, "encz_keys.json"), "w") as f:
+        json.dump(shapes_of(E.state_dict()), f)
+    img = img.clone().requires_grad_(True)
+    z, _ = E(img)
+    gz = R.randn("ez.gz", tuple(z.shape), 83)
+    loss = (z * gz).sum()
+    loss.backward()
+    out = {"loss": loss.detach(), "g_img": img.grad, "z": z.detach(), "kink_margin": np.array(margin),
+           **{"param:" + k: v for k, v in nudged.items()}}
+    _grad_entries(E, out)
+    save_npz("encz_grad.npz", **out)
+
+
+SECTIONS["encz_grad"] = gen_encz_grad
+
+
+def gen_step_z():
+    """Two iterations of ablation_utils/1.E_align_z.py (:58-92) at reduced size: Gs / Gm / LPIPS as gen_step_sg1 (res 64, 5 blocks),
+    E = the encz_grad encoder.  Every generator noise tensor is captured; E_Blur_Z draws none."""
+    import warnings
+    import model.stylegan1.net as SG1
+    import training_utils as TU
+    from model.utils.custom_adam import LREQAdam
+    from oracle import lpips_ref as LR
+
+    L = 5
+    Gs = SG1.Generator(startf=16, maxf=64, layer_count=L, latent_size=512, channels=3)
+    sd = R.fill_encoder(shapes_of(Gs.state_dict()), seed=43)
+    for k in sd:
+        if k.endswith("blur.weight"):
+            sd[k] = Gs.state_dict()[k].clone()
+        if k == "const":
+            sd[k] = R.randn("sg1step.const", tuple(sd[k].shape), 43)
+    Gs.load_state_dict(sd)
+    Gm = SG1.Mapping(num_layers=2 * L, mapping_layers=8, latent_size=512, dlatent_size=512, mapping_fmaps=512)
+    Gm.load_state_dict({k: R.randn("sg1step.m." + k, tuple(v.shape), 44, 0.05 if k.endswith("weight") else 0.01)
+                        for k, v in Gm.state_dict().items()})
+    Gm.buffer1 = R.randn("sg1step.buffer1", (2 * L, 512), 44, 0.5)
+    layer_idx = torch.arange(2 * L)[np.newaxis, :, np.newaxis]
+    ones = torch.ones(layer_idx.shape, dtype=torch.float32)
+    coefs = torch.where(layer_idx < L, 0.7 * ones, ones)
+    E, _, _, _ = _encz_model()
+    LP = LR.seeded_params(0)
+    lp = lambda a, b: LR.lpips(LP, a, b)
+    opt = LREQAdam([{"params": E.parameters()}], lr=0.0015, betas=(0.0, 0.99), weight_decay=0)
+    out = {}
+    B, lod = 2, L - 1
+    flat = lambda inf: [inf[0][0], inf[0][1], inf[0][2], inf[1], inf[2], inf[3], inf[4]]
+    for it in range(2):
+        z1 = R.randn(f"zstep.z{it}", (B, 512), 1)
+        with _NoiseFeeder(f"zstep.it{it}", 1) as nf:
+            w1 = Gm(z1, coefs_m=coefs)
+            imgs1 = Gs.forward(w1, lod)
+            z2, _ = E(imgs1)
+            z2 = z2.squeeze(-1).squeeze(-1)
+            w2 = Gm(z2, coefs_m=coefs)
+            imgs2 = Gs.forward(w2, lod)
+        if it == 0:
+            out["noise_shapes"] = np.array([list(s_) + [0] * (4 - len(s_)) for s_ in nf.log])
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            l_i, i_i = TU.space_loss(imgs1, imgs2, lpips_model=lp)
+            opt.zero_grad()
+            l_i.backward(retain_graph=True)
+            opt.step()
+            l_c, i_c = TU.space_loss(z1, z2, image_space=False)
+            opt.zero_grad()
+            (l_c * 0.01).backward()
+            opt.step()
+        out[f"it{it}_w1"] = w1.detach()
+        out[f"it{it}_z_c2"] = z2.detach()
+        out[f"it{it}_w2"] = w2.detach()
+        out[f"it{it}_imgs2"] = imgs2.detach()
+        out[f"it{it}_losses"] = np.array([float(l_i.detach()), float(l_c.detach())])
+        out[f"it{it}_info"] = np.array([flat(i_i), flat(i_c)])
+        out[f"it{it}_param_checksum"] = np.array(R.checksum(E.state_dict()))
+        for k in ("decode_block.0.conv_1.weight", "decode_block.0.conv_2.weight", "decode_block.0.conv_3.weight", "decode_block.2.bias_1",
+                  "FromRGB.from_rgb.weight", "out_z.bias"):
+            out[f"it{it}_after_phase2:{k}"] = E.state_dict()[k].clone()
+        w = E.state_dict()["out_z.weight"]
+        out[f"it{it}_after_phase2_head:out_z.weight"] = w.flatten()[:4096].clone()
+        out[f"it{it}_after_phase2_norm:out_z.weight"] = w.norm()
+    save_npz("step_z.npz", **out)
+
+
+SECTIONS["step_z"] = gen_step_z
+
 if __name__ == "__main__":
     todo = sys.argv[1:] or list(SECTIONS)
     for s_ in todo:
