@@ -18,6 +18,7 @@ import torch.distributed as dist
 
 from . import losses
 from .custom_adam import LREQAdam
+from .graph_step import GraphReplay
 
 
 def set_seed(seed):
@@ -144,7 +145,7 @@ def _all_reduce(t, async_op=False):
     return dist.all_reduce(t, op=dist.ReduceOp.SUM, async_op=async_op)
 
 
-class EAlignStep:
+class EAlignStep(GraphReplay):
     def __init__(self, generator, E, lpips_model, lr=0.0015, beta_1=0.0, batch_size=2, z_dim=512,
                  reference_noise=False, exact_ddp=True, mapping=None, stage=2, zero_grad_to_none=True):
         """`generator`: StyleGAN2Generator (mtype 2), the StyleGAN1 synthesis network Gs together with
@@ -267,15 +268,16 @@ class EAlignStep:
         return None if self.exact_ddp else torch.full((1,), 1.0 / self.world, device=self.dev)
 
     # ------------------------------------------------------------------ hipGraph replay of the iteration
-    def capture(self, warmup=2, start=0):
+    def capture(self, warmup=GraphReplay.WARMUP, start=0):
         """Captures one iteration into a hipGraph (single-GPU runs; the ≈1300 launches of a step cost ≈18 ms of host time,
         which bounds the step at the reference's default batch of 2).  Host-side decisions of an iteration become device
         inputs: z (static buffer), the style-mixing mask (StyleGAN2 train mode, same np.random draw order as the
-        reference) and Adam's sqrt(1 - beta2^t) factors.  Encoder / StyleGAN1 noise comes from torch's graph-safe
-        device generator.  `warmup` real iterations run inside this call (plus one eager iteration in front of them in the legacy
-        stage-1 form); the captured iteration itself is only recorded.  The real iterations are numbered `start`, `start` + 1, ...
-        (the number seeds z and the mixing mask, training_utils.py:46-52); `self._g_iter` is the number of the NEXT iteration when
-        this returns - a training loop continues there (train() below) instead of repeating the warm-up's iterations."""
+        reference) and Adam's sqrt(1 - beta2^t) factors.  Encoder / StyleGAN1 noise comes from the project's counter-based
+        generator, whose seed becomes a device scalar (ops.noise_graph_begin).  `warmup` real iterations run inside this call
+        (plus one eager iteration in front of them in the legacy stage-1 form); the captured iteration itself is only recorded.
+        The real iterations are numbered `start`, `start` + 1, ... (the number seeds z and the mixing mask,
+        training_utils.py:46-52); `self.graph_iteration` is the number of the NEXT iteration when this returns - a training loop
+        continues there (train() below) instead of repeating the warm-up's iterations."""
         if self.dist_on:
             raise RuntimeError("hipGraph capture is offered for single-process runs only (collectives are not captured)")
         # Capturing after EAGER steps of the same encoder used to end in a segmentation fault inside capture_end (round 2:
@@ -301,29 +303,12 @@ class EAlignStep:
         # zero_grad form (tick() + step()), where the tick is skipped while no parameter has state yet: one eager iteration
         # first gives every parameter its state, so that every captured / replayed iteration makes the same number of calls
         calls = 2 if (self.stage == 2 or not self.zero_grad_to_none) else 1
-        self._g_iter = int(start)
+        self.graph_iteration = int(start)
         if self.stage == 1 and not self.zero_grad_to_none and not any(len(st) for st in self.opt.state.values()):
-            self.step(self._g_iter)
-            self._g_iter += 1
+            self.step(self.graph_iteration)
+            self.graph_iteration += 1
         self.opt.graph_begin(calls, self.dev)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._graph_inputs(self._g_iter); self._g_iter += 1
-                self.step(0, z=self._g_z)
-        torch.cuda.current_stream().wait_stream(side)
-        from .autograd_enc import prime_pack_tables
-        prime_pack_tables(self.E)
-        self._graph = torch.cuda.CUDAGraph()
-        # the captured iteration is RECORDED, not executed: the host-side counters it advances (Adam's t, the iteration number that
-        # seeds z and the mixing mask) are rolled back, so that the first replay is iteration `warmup` of the sequence
-        snap = self.opt.graph_snapshot()
-        self._graph_inputs(self._g_iter)
-        with torch.cuda.graph(self._graph):
-            self._g_out = self.step(0, z=self._g_z)
-        self.opt.graph_restore(snap)
-        return self._g_out
+        return self._capture(lambda: self.step(0, z=self._g_z), warmup)
 
     def _graph_inputs(self, iteration):
         set_seed(iteration % 30000)
@@ -335,12 +320,9 @@ class EAlignStep:
         self.opt.graph_advance()
 
     def replay(self, iteration=None):
-        it = self._g_iter if iteration is None else iteration
-        self._graph_inputs(it)
-        self._g_iter = it + 1
-        self._graph.replay()
-        self.opt.graph_count_replay()
-        return self._g_out
+        if iteration is not None:
+            self.graph_iteration = iteration
+        return super().replay()
 
     # ------------------------------------------------------------------ one iteration
     def _upload(self, t):
@@ -692,8 +674,9 @@ def train(tensor_writer=None, args=None):
                                     and not getattr(args, "deterministic", False))
     first = 0
     prefetch = not getattr(args, "no_prefetch", False)
-    # capture() runs its warm-up iterations for real (2, one more in the legacy stage-1 form): a run shorter than that stays eager
-    if use_graph and args.iterations <= 4:
+    # what runs for real before the first replay: iteration 0 eagerly (below), capture()'s warm-up iterations and one more eager
+    # iteration in the legacy stage-1 form: a run no longer than that stays eager
+    if use_graph and args.iterations <= 1 + GraphReplay.WARMUP + 1:
         use_graph = False
     if use_graph:
         # iteration 0 runs eagerly: the reference logs its losses and dumps E_model_ep0_iter0.pth right after it
@@ -703,7 +686,7 @@ def train(tensor_writer=None, args=None):
         if getattr(args, "experiment_dir", None):
             torch.save(E.state_dict(), "%s/E_model_ep0_iter0.pth" % args.experiment_dir)
         st.capture(start=1)
-        first = st._g_iter           # capture() ran iterations 1 .. first - 1 for real (its warm-up): the loop continues behind them,
+        first = st.graph_iteration   # capture() ran iterations 1 .. first - 1 for real (its warm-up): the loop continues behind them,
         # so that `--launch graph` and `--launch eager` make the same number of encoder updates on the same z / mask sequence
         print("ep_0_iter_1 .. %d ran inside the graph capture (warm-up)" % (first - 1))
     for iteration in range(first, args.iterations):

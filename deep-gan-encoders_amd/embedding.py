@@ -12,16 +12,16 @@ Every gradient path of the reference is live: through Gs into w1, through the se
 reference it re-uses the graph of a single E(imgs1) call across iterations and fails in the second one, and the CLI flag
 (`type=bool`) cannot be switched off anyway (:190).
 """
-import collections
 import math
 
 import torch
 
 from . import losses
 from .custom_adam import LREQAdam
+from .graph_step import GraphReplay
 
 
-class EmbedStep:
+class EmbedStep(GraphReplay):
     def __init__(self, Gs, E, lpips_model, lr=0.01, beta_1=0.0):
         self.Gs, self.E, self.lpips = Gs, E, lpips_model
         self.opt = LREQAdam([{"params": E.parameters()}], lr=lr, betas=(beta_1, 0.99), weight_decay=0)
@@ -34,13 +34,10 @@ class EmbedStep:
         self.E.load_state_dict(self._ckpt)
         for p in self.E.parameters():
             p._dge_gen = getattr(p, "_dge_gen", 0) + 1           # packed-weight caches key on this counter
-        if getattr(self.opt, "_graph_corr", None) is not None:
-            self.opt.graph_reset()                               # same device addresses: a captured graph stays valid
-        else:
-            self.opt.state = collections.defaultdict(dict)
+        self._reset_opt()
 
     # ------------------------------------------------------------------ hipGraph replay of the iteration
-    def capture(self, imgs1, noises=(None, None, None), warmup=2):
+    def capture(self, imgs1, noises=(None, None, None), warmup=GraphReplay.WARMUP):
         """Captures one iteration (≈1700 kernel launches, all on the current stream through the C ABI) into a hipGraph.
         At batch 1 the eager loop is bound by host launch overhead (31 ms/iteration against ≈8 ms of GPU work at 1024^2);
         `replay()` re-runs the captured iteration on the static input `imgs1` with one graph launch.  The only host-side
@@ -49,53 +46,21 @@ class EmbedStep:
         generator (its seed is a device scalar refreshed per replay) unless static `noises` are given.  `warmup` real iterations run here; the
         captured one is only recorded."""
         from . import ops
-        dev = imgs1.device
         self._g_imgs1 = imgs1.detach().clone()
-        self.opt.graph_begin(2, dev)
-        ops.noise_graph_begin(dev)            # the captured noise kernels read their seed from a device scalar
-        self._noise_it = 0
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._graph_inputs()
-                self.step(self._g_imgs1, noises)
-        torch.cuda.current_stream().wait_stream(side)
-        from .autograd_enc import prime_pack_tables
-        prime_pack_tables(self.E)             # (the all-copies descriptor table must be on the device before the capture)
-        self._graph = torch.cuda.CUDAGraph()
-        snap, nit = self.opt.graph_snapshot(), self._noise_it       # (the captured iteration is recorded, not executed)
-        self._graph_inputs()
-        with torch.cuda.graph(self._graph):
-            self._g_out = self.step(self._g_imgs1, noises)
-        self.opt.graph_restore(snap)
-        self._noise_it = nit
-        return self._g_out
+        self.opt.graph_begin(2, imgs1.device)          # two optimizer calls per iteration
+        ops.noise_graph_begin(imgs1.device)            # the captured noise kernels read their seed from a device scalar
+        self.graph_iteration = 0
+        return self._capture(lambda: self.step(self._g_imgs1, noises), warmup)
 
-    def _graph_inputs(self):
-        """host-side inputs of one captured iteration: Adam's step factors and the noise seed (a new one per iteration)"""
+    def _graph_inputs(self, iteration):
         from . import ops
         self.opt.graph_advance()
-        base = ops.NOISE.seed if getattr(self, "_noise_base", None) is None else self._noise_base
-        self._noise_base = base if base is not None else 0
-        self._noise_it += 1
-        ops.noise_seed(self._noise_base + self._noise_it)
+        ops.noise_graph_seed(iteration)
 
     def set_image(self, imgs1):
         """Makes `imgs1` the image group the captured iteration works on (the graph reads the static buffer capture() cloned
         the FIRST group into; every later group has to be copied there before its replays)."""
-        if getattr(self, "_graph", None) is None:
-            raise RuntimeError("EmbedStep.set_image: no captured iteration (call capture() first)")
-        if tuple(imgs1.shape) != tuple(self._g_imgs1.shape) or imgs1.dtype != self._g_imgs1.dtype or imgs1.device != self._g_imgs1.device:
-            raise ValueError(f"EmbedStep.set_image: the captured iteration works on {tuple(self._g_imgs1.shape)} {self._g_imgs1.dtype} on "
-                             f"{self._g_imgs1.device}, got {tuple(imgs1.shape)} {imgs1.dtype} on {imgs1.device}; re-capture for a new geometry")
-        self._g_imgs1.copy_(imgs1.detach())
-
-    def replay(self):
-        self._graph_inputs()
-        self._graph.replay()
-        self.opt.graph_count_replay()
-        return self._g_out
+        self._set_static("_g_imgs1", imgs1)
 
     def step(self, imgs1, noises=(None, None, None)):
         """One iteration; `noises` = optional (E(imgs1), Gs, E(imgs2)) noise lists for parity runs."""
@@ -122,22 +87,23 @@ class EmbedStep:
         return self.last
 
 
+def select_launch(st, imgs1, launch):
+    """-> (run, done): the callable that runs one iteration on `imgs1`, and how many iterations of the loop ran in here."""
+    if launch != "graph":
+        return (lambda: st.step(imgs1)), 0
+    if st.captured:
+        st.set_image(imgs1)                     # later image groups: into the static input of the captured iteration
+        return st.replay, 0
+    st.capture(imgs1, warmup=1)                 # the warm-up iteration is a real iteration of the loop
+    return st.replay, 1
+
+
 def invert(st, imgs1, iterations=1500, launch="graph"):
     """The inversion loop on one image group (embedding_img.py:74-170: `iterations` two-phase iterations from the encoder
     checkpoint).  launch="graph" (default: the loop runs at batch 1, where the eager iteration is bound by the host's launch rate -
     15-17 ms against 13 ms of GPU work at 1024^2) captures the iteration once and replays it; "eager" runs EmbedStep.step."""
     st.begin_image()
-    done = 0
-    if launch == "graph":
-        if getattr(st, "_graph", None) is None:
-            warm = 1
-            st.capture(imgs1, warmup=warm)          # the warm-up iteration is a real iteration of the loop
-            done = warm
-        else:
-            st.set_image(imgs1)                     # later image groups: into the static input of the captured iteration
-        run = st.replay
-    else:
-        run = lambda: st.step(imgs1)
+    run, done = select_launch(st, imgs1, launch)
     r = st.last
     for _ in range(max(0, iterations - done)):
         r = run()

@@ -32,7 +32,6 @@ Decisions where the reference cannot run as written:
   * --optimizeE parses true / false strictly (the reference's `type=bool` cannot be switched off).
 """
 import argparse
-import collections
 import math
 import os
 
@@ -40,6 +39,8 @@ import torch
 
 from . import losses, ops
 from .custom_adam import LREQAdam
+from .embedding import select_launch
+from .graph_step import GraphReplay
 
 # per-generator defaults (embedding_v2_styleGAN1.py:195-209 + :118,128-131; embedding_v2_styleGAN2.py:214-232 + :136,153-166)
 DEFAULTS = {
@@ -89,7 +90,7 @@ class _WplusLerp(torch.autograd.Function):
         return ops.wplus_lerp_bwd(g, ctx.psi), None, None
 
 
-class LatentEmbedStep:
+class LatentEmbedStep(GraphReplay):
     def __init__(self, G, E, lpips_model, mode="E", generator="sg2", lr=0.005, beta_1=0.0, beta=None, norm_p=2, truncation=None,
                  iterations=None, arm_iter=None, events_cap=256, seed=0):
         if mode not in ("E", "W"):
@@ -153,7 +154,7 @@ class LatentEmbedStep:
             self.E.load_state_dict(self._ckpt)
             for p in self.E.parameters():
                 p._dge_gen = getattr(p, "_dge_gen", 0) + 1
-            self._opt_reset()
+            self._reset_opt()
         else:
             with torch.no_grad():
                 if w_init is not None:
@@ -167,12 +168,12 @@ class LatentEmbedStep:
                     gen = torch.Generator().manual_seed(int(self.seed) + self.group)
                     w0 = torch.randn(shape, generator=gen)
                 if self.w1 is None or tuple(self.w1.shape) != shape or self.w1.device != dev:
-                    if getattr(self, "_graph", None) is not None:
+                    if self.captured:
                         raise ValueError("LatentEmbedStep.begin_image: the captured iteration works on a different W+ shape")
                     self.w1 = torch.zeros(shape, dtype=torch.float32, device=dev, requires_grad=True)
                     self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
                 self.w1.copy_(w0)
-            self._opt_reset()
+            self._reset_opt()
         t = self._track_alloc(shape, dev)
         first = getattr(self, "_track_started", False) is False
         t["istate"].zero_()
@@ -180,12 +181,6 @@ class LatentEmbedStep:
         if first or self.rules["reset_per_group"]:
             t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32))
         self._track_started = True
-
-    def _opt_reset(self):
-        if getattr(self.opt, "_graph_corr", None) is not None:
-            self.opt.graph_reset()
-        else:
-            self.opt.state = collections.defaultdict(dict)
 
     # ------------------------------------------------------------------ one iteration
     def _generate(self, w1, noises):
@@ -241,58 +236,34 @@ class LatentEmbedStep:
         return self.last
 
     # ------------------------------------------------------------------ hipGraph replay of the iteration
-    def capture(self, imgs1, noises=(None, None, None), warmup=2):
-        """As EmbedStep.capture: `warmup` real iterations, then one recorded (not executed) iteration.  Adam's step factors come
+    def capture(self, imgs1, noises=(None, None, None), warmup=GraphReplay.WARMUP):
+        """`warmup` real iterations, then one recorded (not executed) iteration (GraphReplay._capture).  Adam's step factors come
         through graph_advance, the noise seed is a device scalar; in W mode the graph updates the static leaf w1 in place.
         begin_image() must have run for the group."""
-        dev = imgs1.device
         self._g_imgs1 = imgs1.detach().clone()
-        self.opt.graph_begin(2, dev)
-        ops.noise_graph_begin(dev)
-        self._noise_it = 0
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._graph_inputs()
-                self.step(self._g_imgs1, noises)
-            # results of the last executed iteration (the captured one below is only recorded)
-            warm = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.last.items()} if warmup else {}
-        torch.cuda.current_stream().wait_stream(side)
-        from .autograd_enc import prime_pack_tables
-        prime_pack_tables(self.E)
-        self._graph = torch.cuda.CUDAGraph()
-        snap, nit = self.opt.graph_snapshot(), self._noise_it
-        self._graph_inputs()
-        with torch.cuda.graph(self._graph):
-            self._g_out = self.step(self._g_imgs1, noises)
-        self.opt.graph_restore(snap)
-        self._noise_it = nit
-        self.last = warm
-        return self._g_out
+        self.opt.graph_begin(2, imgs1.device)          # two optimizer calls per iteration
+        ops.noise_graph_begin(imgs1.device)
+        self.graph_iteration = 0
+        warm = {}
 
-    def _graph_inputs(self):
+        def keep_last():    # results of the last executed iteration (the captured one is only recorded)
+            if warmup:
+                warm.update({k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.last.items()})
+        out = self._capture(lambda: self.step(self._g_imgs1, noises), warmup, after_warmup=keep_last)
+        self.last = warm
+        return out
+
+    def _graph_inputs(self, iteration):
         self.opt.graph_advance()
-        base = ops.NOISE.seed if getattr(self, "_noise_base", None) is None else self._noise_base
-        self._noise_base = base if base is not None else 0
-        self._noise_it += 1
-        ops.noise_seed(self._noise_base + self._noise_it)
+        ops.noise_graph_seed(iteration)
 
     def set_image(self, imgs1):
         """Copies a new image group into the static input of the captured iteration (call begin_image() for the group too)."""
-        if getattr(self, "_graph", None) is None:
-            raise RuntimeError("LatentEmbedStep.set_image: no captured iteration (call capture() first)")
-        if tuple(imgs1.shape) != tuple(self._g_imgs1.shape) or imgs1.dtype != self._g_imgs1.dtype or imgs1.device != self._g_imgs1.device:
-            raise ValueError(f"LatentEmbedStep.set_image: the captured iteration works on {tuple(self._g_imgs1.shape)} {self._g_imgs1.dtype} "
-                             f"on {self._g_imgs1.device}, got {tuple(imgs1.shape)} {imgs1.dtype} on {imgs1.device}")
-        self._g_imgs1.copy_(imgs1.detach())
+        self._set_static("_g_imgs1", imgs1)
 
     def replay(self):
-        self._graph_inputs()
-        self._graph.replay()
-        self.opt.graph_count_replay()
-        self.last = self._g_out
-        return self._g_out
+        self.last = super().replay()
+        return self.last
 
     # ------------------------------------------------------------------ tracker read-out (one host read)
     def tracker(self):
@@ -333,18 +304,9 @@ def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=Non
     per-row w1) are written - one host read per chunk - and, at the end, the trackers' files.  Returns the last result dict with
     the tracker read-out under "tracker"."""
     st.begin_image(imgs1, w_init=w_init)
-    done = 0
-    if launch == "graph":
-        if getattr(st, "_graph", None) is None:
-            st.capture(imgs1, warmup=1)
-            done = 1
-        else:
-            st.set_image(imgs1)
-        run = st.replay
-    elif launch == "eager":
-        run = lambda: st.step(imgs1)
-    else:
+    if launch not in ("graph", "eager"):
         raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
+    run, done = select_launch(st, imgs1, launch)
     r = st.last
 
     def dump(i, r):

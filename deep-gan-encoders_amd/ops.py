@@ -91,7 +91,7 @@ class _Noise:
     rank's slice of the global-batch tensor [world*B, ...], so N ranks x B reproduce one process at batch N*B exactly."""
 
     def __init__(self):
-        self.seed, self.counter, self.rank, self.world, self.seed_dev = None, 0, 0, 1, None
+        self.seed, self.counter, self.rank, self.world, self.seed_dev, self.graph_base = None, 0, 0, 1, None, 0
 
 
 NOISE = _Noise()
@@ -112,8 +112,16 @@ def noise_dp(rank, world):
 def noise_graph_begin(device):
     """hipGraph mode: from now on the kernels read the seed from a device scalar that noise_seed() refreshes before each replay."""
     NOISE.seed_dev = torch.zeros(1, dtype=torch.int64, device=device)
+    NOISE.graph_base = NOISE.seed or 0
     if NOISE.seed is not None:
         noise_seed(NOISE.seed)
+
+
+def noise_graph_seed(iteration):
+    """hipGraph mode, for loops that do not seed their iterations themselves: a new seed per iteration, counted from the seed that
+    was in force at noise_graph_begin.  A function of the iteration number alone: an iteration that is recorded, not executed,
+    leaves nothing to roll back."""
+    noise_seed(NOISE.graph_base + iteration + 1)
 
 
 def randn_rows(shapes, device):

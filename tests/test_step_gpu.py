@@ -407,7 +407,7 @@ def test_graph_replay_of_stage1_equals_eager_iterations(legacy):
     # eager twin: the same z sequence - capture numbers every real iteration it runs (the legacy form's eager pre-iteration
     # included) consecutively from 0 and the replays continue behind them
     seq = list(range(ntot))
-    assert b._g_iter == ntot
+    assert b.graph_iteration == ntot
     for it in seq:
         a.step(it)
     assert len(seq) == ntot
@@ -737,8 +737,8 @@ FULLSIZE_STEP_BOUNDS = {
 
 
 def test_train_loop_makes_the_same_updates_in_graph_and_eager_launch_modes(capsys):
-    """e_align.train() (E_align_s2.py:102-221 as a loop): `--launch graph` runs its warm-up iterations inside capture() as REAL
-    iterations 0, 1 and continues the loop behind them, so that both launch modes make the same number of encoder updates
+    """e_align.train() (E_align_s2.py:102-221 as a loop): `--launch graph` runs iteration 0 eagerly, its warm-up iterations inside
+    capture(start=1) as REAL iterations 1, 2 and continues the loop behind them, so that both launch modes make the same number of encoder updates
     (2 optimizer calls per iteration) on the same z / style-mixing sequence.  The first iteration draws no encoder noise that
     matters yet (noise weights start at zero), so w_avg after the run - a function of the z sequence only - must agree."""
     from dge_amd import e_align
@@ -751,7 +751,7 @@ def test_train_loop_makes_the_same_updates_in_graph_and_eager_launch_modes(capsy
         t = max(s["step"] for s in st.opt.state.values() if len(s))
         out[mode] = (int(t), st.G.truncation.w_avg.detach().cpu().clone())
         if mode == "graph":
-            assert st._g_iter == 5
+            assert st.graph_iteration == 5
     assert out["eager"][0] == out["graph"][0] == 10, (out["eager"][0], out["graph"][0])
     # w_avg: EMA over the batch mean of mapping(z_it), it = 0 .. 4 (stylegan2_generator.py:177-181) - identical z sequence in both modes
     assert relerr(out["graph"][1], out["eager"][1].numpy()) < 1e-5
