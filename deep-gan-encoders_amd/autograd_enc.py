@@ -4,74 +4,7 @@ import torch
 
 from . import ops
 from .stylegan2_generator import _dt
-
-
-def _ver(w):
-    return (w._version, w.data_ptr(), getattr(w, "_dge_gen", 0))
-
-
-def _is_bwd_mode(mode):
-    return (mode & 0xff) in (ops.PACK_DGRAD, ops.PACK_UPFOLD_DGRAD, ops.PACK_SG1_UP_DGRAD, ops.PACK_UPT2D_DGRAD)
-
-
-def _stale(cache, only_bwd=False):
-    return [(k, e) for k, e in cache.items() if isinstance(k, tuple) and len(k) == 3 and isinstance(e, list) and _ver(e[2]) != e[0]
-            and (not only_bwd or _is_bwd_mode(k[1]))]
-
-
-def _refresh(cache, stale, which):
-    """One launch for all of `stale`; a descriptor table (device scratch) per kind of refresh, so that the two alternating sets of
-    a step (everything / data-gradient copies only) each find their table already uploaded (a hipGraph capture cannot upload)."""
-    key = ("_pack_scratch", which)
-    cache[key] = ops.pack_conv_weights_multi([(e[2].detach(), k[1], k[2], 1.0, e[1]) for k, e in stale], cache.get(key))
-    for k, e in stale:
-        e[0] = _ver(e[2])
-
-
-def refresh_packs(module):
-    """Refreshes every stale packed copy of the module's conv weights now (on the current stream): EAlignStep runs this beside the
-    generator's first pass at the start of an iteration instead of in front of the encoder's first conv."""
-    cache = module.__dict__.get("_pack_cache")
-    if cache:
-        stale = _stale(cache)
-        if stale:
-            _refresh(cache, stale, "all")
-
-
-def prime_pack_tables(module):
-    """EAlignStep.capture, between the eager warm-up and the capture: uploads the descriptor table of the all-copies refresh (a
-    capture cannot upload; a single warm-up iteration has only used the data-gradient table) and leaves every copy marked stale,
-    so that the captured iteration re-packs exactly as a steady-state iteration does."""
-    cache = module.__dict__.get("_pack_cache")
-    if cache:
-        stale = _stale(cache)
-        if stale:
-            _refresh(cache, stale, "all")
-            for _, e in stale:
-                e[0] = None
-
-
-def _packed(cache, conv, dtype, mode, hw=None):
-    """Packed copy of a conv weight, rebuilt when the parameter was updated in place.  An optimizer step makes EVERY copy of
-    the module stale at once: the first stale hit of a FORWARD copy refreshes all of them in one launch
-    (ops.pack_conv_weights_multi) - in place, the consumers of the old values are earlier on the same stream; the first stale
-    hit of a data-gradient copy (the second backward of an E_align step, after the first optimizer step) refreshes the
-    data-gradient copies only - the forward copies would be stale again before their next use.  `hw`: resolution the conv runs
-    at (the low-resolution blocks keep their copies in fragment order for csrc/conv_small.hip)."""
-    w = conv.weight
-    if hw is not None:
-        mode = ops.pack_mode_for(w, mode, hw, hw, dtype)
-    key = (id(w), mode, dtype)
-    ver = _ver(w)
-    hit = cache.get(key)
-    if hit is not None and hit[0] == ver:
-        return hit[1]
-    if hit is None:
-        cache[key] = [ver, ops.pack_conv_weight(w, mode, dtype, 1.0), w]
-        return cache[key][1]
-    bwd = _is_bwd_mode(mode)
-    _refresh(cache, _stale(cache, only_bwd=bwd), "bwd" if bwd else "all")
-    return cache[key][1]
+from .weight_cache import pack_cache, packed
 
 
 def draw_noises(E, B, R, device):
@@ -122,6 +55,32 @@ def heads_layout(E, B, dev):
     return lay
 
 
+# ------------------------------------------------------------------ tails shared by the hand-written backwards of the family
+def linear_backward(lin, gy, x, grads, name, params=True):
+    """Backward of the dense layer y = x @ W^T + b: returns g_x [B, I] (ops.linear_t); with `params`, the weight / bias gradients
+    (ops.dense_wgrad) go into grads[name + ".weight" / ".bias"].  params=False: the data gradient alone (frozen encoder)."""
+    W = lin.weight.detach()
+    gx = torch.empty((gy.shape[0], W.shape[1]), dtype=torch.float32, device=gy.device)
+    ops.linear_t(gy, W, gx)
+    if params:
+        gw, gb = torch.empty_like(W), torch.empty_like(lin.bias)
+        ops.dense_wgrad(gy, x, gw, gb)
+        grads[name + ".weight"], grads[name + ".bias"] = gw, gb
+    return gx
+
+
+def fromrgb_param_grads(E, saved, g_out, grads):
+    """FromRGB parameter gradients from the gradient of its output (ops.fromrgb_bwd, [C, 4] form)."""
+    fr = ops.fromrgb_bwd(g_out, saved["x0"], saved["img"].float())
+    grads["FromRGB.from_rgb.weight"] = fr[:, :3].reshape(E.startf, 3, 1, 1)
+    grads["FromRGB.from_rgb.bias"] = fr[:, 3]
+
+
+def grads_in_order(E, grads):
+    """`grads` (by parameter name) in E.named_parameters() order: contiguous, or None where there is no gradient."""
+    return [g.contiguous() if g is not None else None for g in (grads.get(name) for name, _ in E.named_parameters())]
+
+
 def encoder_forward(E, img, noises=None, save=False):
     """BE.forward (reference model/E/E.py:122-136) + BEBlock.forward (:50-85)."""
     dt = _dt(E.compute_dtype)
@@ -129,7 +88,7 @@ def encoder_forward(E, img, noises=None, save=False):
     B, _, R, _ = img.shape
     if noises is None:
         noises = draw_noises(E, B, R, dev)
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     zeros = lambda c: ops.SlotStats(B, c, dev)        # statistics slots are added by stats_finalize itself
     fr = E.FromRGB.from_rgb
     stats = zeros(E.startf)
@@ -158,7 +117,7 @@ def encoder_forward(E, img, noises=None, save=False):
         musig1, sc1, sh1 = ops.stats_finalize(stats, H * H, musig_out=ms_slot(2 * j))
         n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
         st1 = zeros(Cc)
-        x1 = ops.conv2d(x, _packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
+        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
                         noise_w=blk.noise_weight_1.detach().reshape(-1), bias=blk.bias_1.detach().reshape(-1),
                         act=ops.ACT_LRELU, stats=st1)
         musig2, sc2, sh2 = ops.stats_finalize(st1, H * H, musig_out=ms_slot(2 * j + 1))
@@ -174,15 +133,15 @@ def encoder_forward(E, img, noises=None, save=False):
             # full-resolution activation (537 MB at block 0) is neither written nor read back by a pooling pass
             pooled = has3 and ops.conv_pool_supported(B, H, H, Cc, C2, 3, dt)
             if pooled:
-                r2 = ops.conv2d(x1, _packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, pool_out=True, pool_mask=save, **c2args)
+                r2 = ops.conv2d(x1, packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, pool_out=True, pool_mask=save, **c2args)
                 x2, m2 = r2 if save else (r2, None)
             else:
-                a2 = ops.conv2d(x1, _packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, **c2args)
+                a2 = ops.conv2d(x1, packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, **c2args)
             if has3:
                 if not pooled:
                     x2, m2 = ops.blend(a2, pool=True, mask=True) if save else (ops.blend(a2, pool=True), None)
                 xp = ops.blend(x, pool=True)
-                out = ops.conv2d(xp, _packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(),
+                out = ops.conv2d(xp, packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(),
                                  gain=0.889, addend=x2, add_scale=0.111, stats=nstats)
             else:
                 xp = ops.blend(x, pool=True, alpha=0.889)
@@ -196,7 +155,7 @@ def encoder_forward(E, img, noises=None, save=False):
         else:
             if has3:
                 y2 = ops.blend(x1, sc=sc2, sh=sh2)
-                out = ops.conv2d(x, _packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(),
+                out = ops.conv2d(x, packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(),
                                  gain=0.889, addend=y2, add_scale=0.111)
             else:
                 out = ops.blend(x1, z=x, sc=sc2, sh=sh2, alpha=0.111, beta=0.889)

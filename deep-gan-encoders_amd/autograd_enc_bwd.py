@@ -6,26 +6,14 @@ encoder's const output in a loss that is back-propagated).  Weights are re-packe
 already updated by LREQAdam together with the activations saved before the update - the
 reference's behaviour.
 """
+import os
+
 import torch
 
 from . import ops
-from .autograd_enc import _packed, heads_layout
+from .autograd_enc import grads_in_order, heads_layout, linear_backward
+from .weight_cache import pack_cache, packed
 
-
-def _linear_backward(lin, g_w, musig, grads, name):
-    """w = musig @ W^T + b  ->  g_musig [B,2C]; parameter gradients into `grads`."""
-    B = g_w.shape[0]
-    W = lin.weight.detach()
-    gms = torch.empty((B, W.shape[1]), dtype=torch.float32, device=g_w.device)
-    ops.linear_t(g_w, W, gms, ldx=g_w.stride(0), B=B)
-    gw = torch.empty_like(W)
-    gb = torch.empty_like(lin.bias)
-    ops.dense_wgrad(g_w, musig, gw, gb)
-    grads[name + ".weight"], grads[name + ".bias"] = gw, gb
-    return gms
-
-
-import os
 FUSE_IN_BWD = not os.environ.get("DGE_NO_FUSED_IN_BWD")
 
 
@@ -34,7 +22,7 @@ def encoder_backward(E, saved, g_w):
     produces none, e.g. the last block's noise_weight_2 / bias_2)."""
     if saved is None:
         raise RuntimeError("encoder forward ran without saved activations")
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     dev = g_w.device
     L = E.layer_count
     B = g_w.shape[0]
@@ -82,8 +70,8 @@ def encoder_backward(E, saved, g_w):
         if heads is not None:
             gms2, gms1 = heads(2 * j + 1, pre + "inver_mod2"), heads(2 * j, pre + "inver_mod1")
         else:
-            gms2 = _linear_backward(blk.inver_mod2, g_w2, rec["musig2"], grads, pre + "inver_mod2")
-            gms1 = _linear_backward(blk.inver_mod1, g_w1, rec["musig1"], grads, pre + "inver_mod1")
+            gms2 = linear_backward(blk.inver_mod2, g_w2, rec["musig2"], grads, pre + "inver_mod2")
+            gms1 = linear_backward(blk.inver_mod1, g_w1, rec["musig1"], grads, pre + "inver_mod1")
         x, x1 = rec["x"], rec["x1"]
         extra, extra_pool, extra_scale = None, False, 1.0
         fuse2 = False
@@ -106,13 +94,13 @@ def encoder_backward(E, saved, g_w):
                 ops.conv_wgrad(g_pre2, x1, gW2, rec["sc2"], rec["sh2"])
             grads[pre + "conv_2.weight"] = gW2
             if not fuse2:
-                g_y2 = ops.conv2d(g_pre2, _packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
+                g_y2 = ops.conv2d(g_pre2, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
             if has3:
                 post.append(lambda n=pre + "conv_3.bias", t=red2[2]: grads.__setitem__(n, t * 0.889))
                 gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
                 ops.conv_wgrad(g_out, rec["xp"], gW3)
                 grads[pre + "conv_3.weight"] = ops.scale_(gW3, 0.889)
-                extra = ops.conv2d(g_out, _packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, gain=0.889)
+                extra = ops.conv2d(g_out, packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, gain=0.889)
                 extra_pool, extra_scale = True, 0.25
             else:
                 extra, extra_pool, extra_scale = g_out, True, 0.889 * 0.25
@@ -124,7 +112,7 @@ def encoder_backward(E, saved, g_w):
         red1 = ops.zeros((2, Cc), dev)
         if fuse2:
             redp = ops.SlotStats(B, Cc, dev)
-            g_pre1 = ops.conv2d(g_pre2, _packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, dot_src=x1,
+            g_pre1 = ops.conv2d(g_pre2, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, dot_src=x1,
                                 in_bwd=dict(coef=ops.in_bwd_coef(*coef2), noise=rec["n1"].reshape(B, H, H), red=redp))
             ops._sum_planar(redp.buf.view(-1, Cc, 2), red1, later)
         else:
@@ -148,15 +136,15 @@ def encoder_backward(E, saved, g_w):
         coef1 = (dots1, gms1, rec["musig1"], rec["sc1"], rec["sh1"], N)
         if fuse_fr:
             frh = ops.SlotStats(B, Cc, dev)
-            ops.conv2d(g_pre1, _packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, dot_src=x, out=x.new_empty((1, 1, 1, 1)),
+            ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, dot_src=x, out=x.new_empty((1, 1, 1, 1)),
                        in_bwd=dict(coef=ops.in_bwd_coef(*coef1), fr=frh, img4=saved["img4"], extra=extra if extra_pool else None,
                                    extra_scale=extra_scale))
             fr = ops._sum_planar(frh.buf.view(-1, Cc, 4), torch.empty((4, Cc), dtype=torch.float32, device=dev), later)
         elif fuse_x:
-            g_out = ops.conv2d(g_pre1, _packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, dot_src=x,
+            g_out = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, dot_src=x,
                                in_bwd=dict(coef=ops.in_bwd_coef(*coef1), extra=extra, extra_scale=extra_scale))
         else:
-            g_y1 = ops.conv2d(g_pre1, _packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
+            g_y1 = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
         if fuse_fr or fuse_x:
             pass
         elif j == 0 and Cc <= 512:
@@ -178,8 +166,4 @@ def encoder_backward(E, saved, g_w):
     C0 = E.startf
     grads["FromRGB.from_rgb.weight"] = fr[:3].t().reshape(C0, 3, 1, 1)
     grads["FromRGB.from_rgb.bias"] = fr[3]
-    out = []
-    for name, p in E.named_parameters():
-        g = grads.get(name)
-        out.append(g.contiguous() if g is not None else None)
-    return out
+    return grads_in_order(E, grads)

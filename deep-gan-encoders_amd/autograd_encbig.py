@@ -15,9 +15,10 @@ import os
 import torch
 
 from . import ops
-from .autograd_enc import _packed, draw_noises
+from .autograd_enc import draw_noises, fromrgb_param_grads, grads_in_order, linear_backward
 from .biggan_generator import sn_weight_grad, sn_prepare, sn_cbn_linears
 from .stylegan2_generator import _dt
+from .weight_cache import pack_cache, packed
 
 
 def big_encoder_forward(E, img, cond_vector, noises=None, save=False, truncation=0.4):
@@ -28,7 +29,7 @@ def big_encoder_forward(E, img, cond_vector, noises=None, save=False, truncation
     cond = cond_vector.detach().float().contiguous()
     if noises is None:
         noises = draw_noises(E, B, R, dev)
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     if "_sn_skip" not in E.__dict__:
         # the last block stops after conv_1 (E_BIG.py:146-152): its batch_norm_2 / batch_norm_3 are never called by the reference
         last = len(E.decode_block) - 1
@@ -43,7 +44,7 @@ def big_encoder_forward(E, img, cond_vector, noises=None, save=False, truncation
         c1 = {} if save else None
         a1, b1 = blk.batch_norm_1.affine(truncation, cond, training, c1)
         n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        x1 = ops.conv2d(x, _packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=a1, in_shift=b1, noise=n1,
+        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=a1, in_shift=b1, noise=n1,
                         noise_w=blk.noise_weight_1.detach().reshape(-1), bias=blk.bias_1.detach().reshape(-1), act=ops.ACT_LRELU)
         rec = dict(x=x, a1=a1, b1=b1, c1=c1, n1=n1, x1=x1) if save else None
         if not blk.has_second_conv:
@@ -54,13 +55,13 @@ def big_encoder_forward(E, img, cond_vector, noises=None, save=False, truncation
         c2 = {} if save else None
         a2, b2 = blk.batch_norm_2.affine(truncation, cond, training, c2)
         n2 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        x2 = ops.conv2d(x1, _packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, in_scale=a2, in_shift=b2, noise=n2,
+        x2 = ops.conv2d(x1, packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, in_scale=a2, in_shift=b2, noise=n2,
                         noise_w=blk.noise_weight_2.detach().reshape(-1), bias=blk.bias_2.detach().reshape(-1), act=ops.ACT_LRELU)
         xp = ops.blend(x, pool=True)                                  # avg_pool2d of the block input (residual branch)
         if Cc != C2:
             c3 = {} if save else None
             a3, b3 = blk.batch_norm_3.affine(truncation, cond, training, c3)
-            resp = ops.conv2d(xp, _packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, in_scale=a3, in_shift=b3, bias=blk.conv_3.bias.detach())
+            resp = ops.conv2d(xp, packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, in_scale=a3, in_shift=b3, bias=blk.conv_3.bias.detach())
             x2 = ops.blur_noise_act(x2, None, None, None, blur=False)          # the second leaky_relu of E_BIG.py:163
         else:
             a3 = b3 = c3 = None
@@ -167,7 +168,7 @@ def _affine_coef(a):
 def big_encoder_backward(E, saved, g_z, g_cv=None):
     if saved is None:
         raise RuntimeError("E_BIG forward ran without saved activations")
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     dev = g_z.device
     B = g_z.shape[0]
     R = saved["img"].shape[2]
@@ -175,19 +176,10 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
     cond = saved["cond"]
     grads = {}
     pend = []          # conditional-batch-norm parameter gradients: recorded per norm, run grouped behind the block loop
-
-    def lin_bwd(lin, gy, x, name):
-        W = lin.weight.detach()
-        gx = torch.empty_like(x)
-        ops.linear_t(gy, W, gx)
-        gw, gb = torch.empty_like(W), torch.empty_like(lin.bias)
-        ops.dense_wgrad(gy, x, gw, gb)
-        grads[name + ".weight"], grads[name + ".bias"] = gw, gb
-        return gx
-    g_cvt = lin_bwd(E.new_final_2, g_z.float().contiguous(), saved["c_v"], "new_final_2")
+    g_cvt = linear_backward(E.new_final_2, g_z.float().contiguous(), saved["c_v"], grads, "new_final_2")
     if g_cv is not None:
         g_cvt = g_cvt + g_cv.float()
-    g_flat = lin_bwd(E.new_final_1, g_cvt.contiguous(), saved["flat"], "new_final_1")
+    g_flat = linear_backward(E.new_final_1, g_cvt.contiguous(), saved["flat"], grads, "new_final_1")
     L = len(saved["blocks"])
     C_last = E.decode_block[L - 1].inputs
     g_out = ops.nchw_to_nhwc(g_flat.view(B, C_last, R >> (L - 1), R >> (L - 1)), B, dt)
@@ -210,7 +202,7 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
             ops.conv_wgrad(g_pre2, x1, gW2, rec["a2"], rec["b2"])
             grads[pre + "conv_2.weight"] = gW2
             dots2 = ops.zeros((B, Cc, 2), dev)
-            g_u2 = ops.conv2d(g_pre2, _packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
+            g_u2 = ops.conv2d(g_pre2, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
             _cbn_param_grads(blk.batch_norm_2, rec["c2"], dots2, cond, grads, pre + "batch_norm_2", pend)
             g_pre1 = ops.in_bwd(g_u2, x1, _affine_coef(rec["a2"]), noise=rec["n1"], act=True, red=red1)
             if has3:
@@ -220,7 +212,7 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
                 ops.conv_wgrad(g_out, xp, gW3, rec["a3"], rec["b3"])
                 grads[pre + "conv_3.weight"] = gW3
                 dots3 = ops.zeros((B, Cc, 2), dev)
-                g_u3 = ops.conv2d(g_out, _packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, stats=dots3, dot_src=xp)
+                g_u3 = ops.conv2d(g_out, packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, stats=dots3, dot_src=xp)
                 _cbn_param_grads(blk.batch_norm_3, rec["c3"], dots3, cond, grads, pre + "batch_norm_3", pend)
                 extra = ops.in_bwd(g_u3, xp, _affine_coef(rec["a3"]))          # a3 * g at the pooled resolution
             else:
@@ -234,19 +226,12 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
         ops.conv_wgrad(g_pre1, x, gW1, rec["a1"], rec["b1"])
         grads[pre + "conv_1.weight"] = gW1
         dots1 = ops.zeros((B, Cc, 2), dev)
-        g_u1 = ops.conv2d(g_pre1, _packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
+        g_u1 = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
         _cbn_param_grads(blk.batch_norm_1, rec["c1"], dots1, cond, grads, pre + "batch_norm_1", pend)
         g_out = ops.in_bwd(g_u1, x, _affine_coef(rec["a1"]), extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
     _cbn_param_grads_flush(pend, cond, grads)
-    fr = ops.fromrgb_bwd(g_out, saved["x0"], saved["img"].float())
-    C0 = E.startf
-    grads["FromRGB.from_rgb.weight"] = fr[:, :3].reshape(C0, 3, 1, 1)
-    grads["FromRGB.from_rgb.bias"] = fr[:, 3]
-    out = []
-    for name, _ in E.named_parameters():
-        g = grads.get(name)
-        out.append(g.contiguous() if g is not None else None)
-    return out
+    fromrgb_param_grads(E, saved, g_out, grads)
+    return grads_in_order(E, grads)
 
 
 class BigEncoderFunction(torch.autograd.Function):

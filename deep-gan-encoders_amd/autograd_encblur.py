@@ -13,9 +13,9 @@ out = 0.111*x2 + 0.889*(conv_3)(avg_pool(x)).  Last block: out = 0.111*IN2(x1) +
 import torch
 
 from . import ops
-from .autograd_enc import _packed, draw_noises
-from .autograd_enc_bwd import _linear_backward
+from .autograd_enc import draw_noises, fromrgb_param_grads, grads_in_order, linear_backward
 from .stylegan2_generator import _dt
+from .weight_cache import pack_cache, packed
 
 
 def blur_noises(E, B, R, dev):
@@ -39,7 +39,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
     noise, heads = getattr(E, "noise", True), getattr(E, "heads", True)       # E_Blur_Z (BlurBEZ): neither
     if noises is None and noise:
         noises = blur_noises(E, B, R, dev)
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     zeros = lambda c: ops.zeros((B, c, 2), dev)
     fr = E.FromRGB.from_rgb
     stats = zeros(E.startf)
@@ -57,7 +57,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
             n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
             nw1 = blk.noise_weight_1.detach().reshape(-1)
         st1 = zeros(Cc)
-        x1 = ops.conv2d(x, _packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
+        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
                         noise_w=nw1, bias=blk.bias_1.detach().reshape(-1), act=ops.ACT_LRELU, stats=st1)
         musig2, sc2, sh2 = ops.stats_finalize(st1, H * H)
         w2 = ops.linear(musig2, blk.inver_mod2.weight.detach(), blk.inver_mod2.bias.detach()) if heads else None
@@ -65,7 +65,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
         nstats = zeros(C2) if not last else None
         if not last:
             y2 = ops.blur_noise_act(ops.blend(x1, sc=sc2, sh=sh2), None, None, None, blur=True, act=False)   # blur(IN2(x1))
-            wpk = _packed(cache, blk.conv_2, dt, ops.PACK_FWD, H)
+            wpk = packed(cache, blk.conv_2, dt, ops.PACK_FWD, H)
             n2 = nw2 = None
             if noise:
                 n2 = noises[ni]; ni += 1
@@ -83,7 +83,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
                 x2 = ops.blend(a2, pool=True)
             xp = ops.blend(x, pool=True)
             if has3:
-                out = ops.conv2d(xp, _packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(),
+                out = ops.conv2d(xp, packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(),
                                  gain=0.889, addend=x2, add_scale=0.111, stats=nstats)
             else:
                 out = ops.blend(x2, z=xp, alpha=0.111, beta=0.889, stats=nstats)
@@ -100,15 +100,6 @@ def blur_encoder_forward(E, img, noises=None, save=False):
     return ops.nhwc_to_nchw(x), (torch.stack(ws, dim=1) if heads else None), saved
 
 
-def _linear_dgrad(lin, g_w):
-    """Data part of _linear_backward alone (same launch): w = musig @ W^T + b -> g_musig [B,2C]."""
-    B = g_w.shape[0]
-    W = lin.weight.detach()
-    gms = torch.empty((B, W.shape[1]), dtype=torch.float32, device=g_w.device)
-    ops.linear_t(g_w, W, gms, ldx=g_w.stride(0), B=B)
-    return gms
-
-
 def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=True):
     """-> (gradients for E.parameters() in registration order, image gradient [B,3,R,R] or None).
     params=False (frozen encoder: the W+ inversion mode of embedding_v2.py): the data gradient alone.  No weight-gradient
@@ -117,7 +108,7 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
     Every parameter gradient is None.
     An encoder without heads (E.heads False, E_Blur_Z) takes g_w=None: the statistics gradient fed to in_bwd_coef is then zero.
     Without noise (E.noise False) no noise-weight gradient is formed."""
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     noise, heads = getattr(E, "noise", True), getattr(E, "heads", True)
     dev = saved["img"].device
     L = E.layer_count
@@ -139,13 +130,10 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
         has3 = Cc != C2
         if not heads:
             gms2 = gms1 = None
-        elif params:
-            g_w2, g_w1 = g_w[:, 2 * (L - 1 - j)], g_w[:, 2 * (L - 1 - j) + 1]
-            gms2 = _linear_backward(blk.inver_mod2, g_w2, rec["musig2"], grads, pre + "inver_mod2")
-            gms1 = _linear_backward(blk.inver_mod1, g_w1, rec["musig1"], grads, pre + "inver_mod1")
         else:
             g_w2, g_w1 = g_w[:, 2 * (L - 1 - j)], g_w[:, 2 * (L - 1 - j) + 1]
-            gms2, gms1 = _linear_dgrad(blk.inver_mod2, g_w2), _linear_dgrad(blk.inver_mod1, g_w1)
+            gms2 = linear_backward(blk.inver_mod2, g_w2, rec["musig2"], grads, pre + "inver_mod2", params)
+            gms1 = linear_backward(blk.inver_mod1, g_w1, rec["musig1"], grads, pre + "inver_mod1", params)
         x, x1 = rec["x"], rec["x1"]
         extra, extra_pool, extra_scale = None, False, 1.0
         if not last:
@@ -164,7 +152,7 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
                 gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
                 ops.conv_wgrad(g_c2, rec["y2"], gW2)
                 grads[pre + "conv_2.weight"] = gW2
-            g_y2b = ops.conv2d(g_c2, _packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3)
+            g_y2b = ops.conv2d(g_c2, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3)
             g_y2 = ops.blur_noise_act(g_y2b, None, None, None, blur=True, act=False)                 # Blur is self-adjoint
             dots2 = ops.dot_stats(g_y2, x1)
             if has3:
@@ -173,7 +161,7 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
                     gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
                     ops.conv_wgrad(g_out, rec["xp"], gW3)
                     grads[pre + "conv_3.weight"] = ops.scale_(gW3, 0.889)
-                extra = ops.conv2d(g_out, _packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, gain=0.889)
+                extra = ops.conv2d(g_out, packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, gain=0.889)
                 extra_pool, extra_scale = True, 0.25
             else:
                 extra, extra_pool, extra_scale = g_out, True, 0.889 * 0.25
@@ -195,20 +183,13 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
             ops.conv_wgrad(g_pre1, x, gW1, rec["sc1"], rec["sh1"])
             grads[pre + "conv_1.weight"] = gW1
         dots1 = ops.zeros((B, Cc, 2), dev)
-        g_y1 = ops.conv2d(g_pre1, _packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
+        g_y1 = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
         coef1 = ops.in_bwd_coef(dots1, gms1, rec["musig1"], rec["sc1"], rec["sh1"], N)
         g_out = ops.in_bwd(g_y1, x, coef1, extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
     if params:
-        fr = ops.fromrgb_bwd(g_out, saved["x0"], saved["img"].float())
-        C0 = E.startf
-        grads["FromRGB.from_rgb.weight"] = fr[:, :3].reshape(C0, 3, 1, 1)
-        grads["FromRGB.from_rgb.bias"] = fr[:, 3]
+        fromrgb_param_grads(E, saved, g_out, grads)
     g_img = ops.fromrgb_dgrad(g_out, saved["x0"], E.FromRGB.from_rgb.weight.detach()) if need_img else None
-    out = []
-    for name, p in E.named_parameters():
-        g = grads.get(name)
-        out.append(g.contiguous() if g is not None else None)
-    return out, g_img
+    return grads_in_order(E, grads), g_img
 
 
 class BlurEncoderFunction(torch.autograd.Function):

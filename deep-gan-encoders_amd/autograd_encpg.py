@@ -13,8 +13,9 @@ gradients summed over the batch are the gamma / beta gradients.
 import torch
 
 from . import ops
-from .autograd_enc import _packed, draw_noises
+from .autograd_enc import draw_noises, fromrgb_param_grads, grads_in_order, linear_backward
 from .stylegan2_generator import _dt
+from .weight_cache import pack_cache, packed
 
 
 def pg_encoder_forward(E, img, noises=None, save=False):
@@ -23,7 +24,7 @@ def pg_encoder_forward(E, img, noises=None, save=False):
     B, _, R, _ = img.shape
     if noises is None:
         noises = draw_noises(E, B, R, dev)
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     zeros = lambda c: ops.zeros((B, c, 2), dev)
     fr = E.FromRGB.from_rgb
     stats = zeros(E.startf)
@@ -35,7 +36,7 @@ def pg_encoder_forward(E, img, noises=None, save=False):
         musig1, sc1, sh1 = ops.stats_finalize(stats, H * H)
         st1 = zeros(Cc)
         n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        x1 = ops.conv2d(x, _packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
+        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
                         noise_w=blk.noise_weight_1.detach().reshape(-1), bias=blk.bias_1.detach().reshape(-1),
                         act=ops.ACT_LRELU, stats=st1)
         rec = dict(x=x, musig1=musig1, sc1=sc1, sh1=sh1, n1=n1, x1=x1) if save else None
@@ -46,11 +47,11 @@ def pg_encoder_forward(E, img, noises=None, save=False):
             break
         musig2, sc2, sh2 = ops.stats_finalize(st1, H * H)
         n2 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        pre2 = ops.conv2d(x1, _packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, in_scale=sc2, in_shift=sh2, noise=n2,
+        pre2 = ops.conv2d(x1, packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, in_scale=sc2, in_shift=sh2, noise=n2,
                           noise_w=blk.noise_weight_2.detach().reshape(-1), bias=blk.bias_2.detach().reshape(-1))
         if Cc != C2:
             st3 = zeros(C2)
-            r3 = ops.conv2d(x, _packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(), stats=st3)
+            r3 = ops.conv2d(x, packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(), stats=st3)
             _, sc3, sh3 = ops.stats_finalize(st3, H * H)
             g, bta = blk.instance_norm_3.weight.detach(), blk.instance_norm_3.bias.detach()
             s = ops.blend(r3, z=pre2, sc=(sc3 * g).contiguous(), sh=(sh3 * g + bta).contiguous(), alpha=1.0, beta=1.0)
@@ -78,21 +79,13 @@ def pg_encoder_backward(E, saved, g_z):
     """Gradients for E.parameters() in registration order."""
     if saved is None:
         raise RuntimeError("E_PG forward ran without saved activations")
-    cache = E.__dict__.setdefault("_pack_cache", {})
+    cache = pack_cache(E)
     dev = g_z.device
     B = g_z.shape[0]
     R = saved["img"].shape[2]
     dt = ops.dtype_of(saved["x0"])
     grads = {}
-    # head: z = flat @ W^T + b
-    W = E.new_final.weight.detach()
-    flat = saved["flat"]
-    g_z = g_z.float().contiguous()
-    g_flat = torch.empty_like(flat)
-    ops.linear_t(g_z, W, g_flat)
-    gw, gb = torch.empty_like(W), torch.empty_like(E.new_final.bias)
-    ops.dense_wgrad(g_z, flat, gw, gb)
-    grads["new_final.weight"], grads["new_final.bias"] = gw, gb
+    g_flat = linear_backward(E.new_final, g_z.float().contiguous(), saved["flat"], grads, "new_final")     # head: z = flat @ W^T + b
     L = len(saved["blocks"])
     C_last = E.decode_block[L - 1].inputs
     g_out = ops.nchw_to_nhwc(g_flat.view(B, C_last, R >> (L - 1), R >> (L - 1)), B, dt)
@@ -115,7 +108,7 @@ def pg_encoder_backward(E, saved, g_z):
             ops.conv_wgrad(g_s, x1, gW2, rec["sc2"], rec["sh2"])
             grads[pre + "conv_2.weight"] = gW2
             dots2 = ops.zeros((B, Cc, 2), dev)
-            g_y2 = ops.conv2d(g_s, _packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
+            g_y2 = ops.conv2d(g_s, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
             coef2 = ops.in_bwd_coef(dots2, None, rec["musig2"], rec["sc2"], rec["sh2"], N)
             g_pre1 = ops.in_bwd(g_y2, x1, coef2, noise=rec["n1"], act=True, red=red1)
             if has3:
@@ -129,7 +122,7 @@ def pg_encoder_backward(E, saved, g_z):
                 gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
                 ops.conv_wgrad(g_r3, x, gW3)
                 grads[pre + "conv_3.weight"] = gW3
-                extra = ops.conv2d(g_r3, _packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1)
+                extra = ops.conv2d(g_r3, packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1)
             else:
                 extra = g_s
         else:
@@ -141,18 +134,11 @@ def pg_encoder_backward(E, saved, g_z):
         ops.conv_wgrad(g_pre1, x, gW1, rec["sc1"], rec["sh1"])
         grads[pre + "conv_1.weight"] = gW1
         dots1 = ops.zeros((B, Cc, 2), dev)
-        g_y1 = ops.conv2d(g_pre1, _packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
+        g_y1 = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
         coef1 = ops.in_bwd_coef(dots1, None, rec["musig1"], rec["sc1"], rec["sh1"], N)
         g_out = ops.in_bwd(g_y1, x, coef1, extra=extra, extra_pool=False, extra_scale=1.0)
-    fr = ops.fromrgb_bwd(g_out, saved["x0"], saved["img"].float())
-    C0 = E.startf
-    grads["FromRGB.from_rgb.weight"] = fr[:, :3].reshape(C0, 3, 1, 1)
-    grads["FromRGB.from_rgb.bias"] = fr[:, 3]
-    out = []
-    for name, _ in E.named_parameters():
-        g = grads.get(name)
-        out.append(g.contiguous() if g is not None else None)
-    return out
+    fromrgb_param_grads(E, saved, g_out, grads)
+    return grads_in_order(E, grads)
 
 
 class PGEncoderFunction(torch.autograd.Function):

@@ -8,6 +8,7 @@ import torch
 
 from . import ops
 from .stylegan2_generator import _dt
+from .weight_cache import lookup, store, version
 
 
 def _layer_fwd(L, x, w_row, randomize_noise):
@@ -29,7 +30,7 @@ def _style_tables(mod, B, dt):
     so that every style vector and demodulation factor of a pass comes from two launches (dge_linear_rows, dge_demod_rows)."""
     nl = mod.num_layers
     groups = [(getattr(mod, f"layer{i}"), i) for i in range(nl - 1)] + [(getattr(mod, f"output{k}"), 2 * k + 1) for k in range(nl // 2)]
-    key = (B, str(dt)) + tuple((p._version, p.data_ptr()) for L, _ in groups for p in (L.style.weight, L.style.bias, L.weight))
+    key = (B, str(dt)) + tuple(version(p) for L, _ in groups for p in (L.style.weight, L.style.bias, L.weight))
     hit = mod.__dict__.get("_style_tab")
     if hit is not None and hit[0] == key:
         return hit[1]
@@ -141,12 +142,8 @@ def _dgrad_weight(L, dtype):
         mode = ops.PACK_UPT2D_DGRAD
     else:
         mode = ops.pack_mode_for(L.weight, ops.PACK_UPFOLD_DGRAD if L.up else ops.PACK_DGRAD, hg, hg, dtype)
-    key = ("dg", dtype, mode, L.weight._version, L.weight.data_ptr(), getattr(L.weight, "_dge_gen", 0))
-    c = L._cache.get("dg")
-    if c is None or c[0] != key:
-        c = (key, ops.pack_conv_weight(L.weight, mode, dtype, L.wscale))
-        L._cache["dg"] = c
-    return c[1]
+    c = lookup(L._cache, ("dg", dtype, mode), L.weight)
+    return c if c is not None else store(L._cache, ("dg", dtype, mode), L.weight, ops.pack_conv_weight(L.weight, mode, dtype, L.wscale))
 
 
 def _pp_dgrad(L, B, hg, dtype):
@@ -162,13 +159,11 @@ def _dgrad_weight_pp(L, d, t2d=False):
     if not L.up:
         return ops.pack_conv_pp(L.weight, L.wscale, in_scale=d, dgrad=True)
     name = "dgpp_t2d" if t2d else "dgpp"
-    key = (name, L.weight._version, L.weight.data_ptr(), getattr(L.weight, "_dge_gen", 0))
-    c = L._cache.get(name)
-    if c is None or c[0] != key:
+    c = lookup(L._cache, name, L.weight)
+    if c is None:
         rows = ops.pack_conv_weight(L.weight, ops.PACK_UPT2D_DGRAD if t2d else ops.PACK_UPFOLD_DGRAD, ops.F32, L.wscale)
-        c = (key, ops.pack_conv_pp_rows(rows, L.in_c, t2d=True) if t2d else rows)
-        L._cache[name] = c
-    return c[1] if t2d else ops.pack_conv_pp_rows(c[1], L.in_c, in_scale=d, in_period=L.out_c)
+        c = store(L._cache, name, L.weight, ops.pack_conv_pp_rows(rows, L.in_c, t2d=True) if t2d else rows)
+    return c if t2d else ops.pack_conv_pp_rows(c, L.in_c, in_scale=d, in_period=L.out_c)
 
 
 def synthesis_backward(mod, wp, saved, g_image):

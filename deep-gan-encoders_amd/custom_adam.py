@@ -6,6 +6,7 @@ import math
 import torch
 from torch.optim.optimizer import Optimizer
 
+from . import weight_cache
 from ._lib import lib, check
 from .ops import _stream
 
@@ -101,10 +102,9 @@ class LREQAdam(Optimizer):
                     if p.dtype != torch.float32:
                         raise RuntimeError("LREQAdam.tick: float32 parameters only")
                     p.grad = z[:p.numel()].view_as(p) if len(self.state.get(p, {})) else None
-                gens = [(p, getattr(p, "_dge_gen", 0)) for p in group["params"]]
+                valid = weight_cache.save(group["params"])
                 self.step()
-                for p, gen in gens:          # no value changed: the packed weight copies stay valid (step() marks them stale)
-                    p._dge_gen = gen
+                weight_cache.restore(valid)     # no value changed: the packed weight copies stay valid (step() marks them stale)
             finally:
                 for p, g in saved:
                     p.grad = g
@@ -139,15 +139,15 @@ class LREQAdam(Optimizer):
                     step_size *= p.lr_equalization_coef
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 keep.append(g)
-                # the kernel writes through the raw pointer (like the reference's p.data update, it does not touch
-                # autograd's version counter): bump our own generation so packed weight copies are rebuilt
-                p._dge_gen = getattr(p, "_dge_gen", 0) + 1
-                ps.append(p.data_ptr()); gs.append(g.data_ptr()); vs.append(state["exp_avg_sq"].data_ptr())
+                ps.append(p); gs.append(g.data_ptr()); vs.append(state["exp_avg_sq"].data_ptr())
                 ns.append(p.numel()); steps.append(step_size)
             n = len(ps)
             if n == 0:
                 continue
-            PA = (C.c_void_p * n)(*ps); GA = (C.c_void_p * n)(*gs); VA = (C.c_void_p * n)(*vs)
+            # the kernel writes through the raw pointer (like the reference's p.data update, it does not touch autograd's
+            # version counter): every derived copy of these weights is stale
+            weight_cache.written(ps)
+            PA = (C.c_void_p * n)(*[p.data_ptr() for p in ps]); GA = (C.c_void_p * n)(*gs); VA = (C.c_void_p * n)(*vs)
             NA = (C.c_long * n)(*ns); SA = (C.c_float * n)(*steps)
             gsc = C.c_void_p(grad_scale.data_ptr()) if grad_scale is not None else None
             smul = None

@@ -19,6 +19,7 @@ import torch.distributed as dist
 from . import losses
 from .custom_adam import LREQAdam
 from .graph_step import GraphReplay
+from .weight_cache import pack_cache, refresh_packs
 
 
 def set_seed(seed):
@@ -416,9 +417,8 @@ class EAlignStep(GraphReplay):
         # the re-pack of the encoder's conv weights (stale since the last optimizer step) beside the generator's first pass:
         # an HBM-bound copy next to small-grid low-resolution layers; joined in front of the encoder
         pack_side = None
-        if (self.dev.type == "cuda" and _SIDE_STREAMS and _PACK_STREAM and not ops.is_deterministic() and E.__dict__.get("_pack_cache")
+        if (self.dev.type == "cuda" and _SIDE_STREAMS and _PACK_STREAM and not ops.is_deterministic() and pack_cache(E, create=False)
                 and (B * imgs_px(G) >= (4 << 20) or torch.cuda.is_current_stream_capturing())):
-            from .autograd_enc import refresh_packs
             if getattr(self, "_pack_stream", None) is None:
                 self._pack_stream = torch.cuda.Stream(device=self.dev)
             pack_side, main = self._pack_stream, torch.cuda.current_stream(self.dev)

@@ -16,7 +16,7 @@ import math
 
 import torch
 
-from . import losses
+from . import losses, weight_cache
 from .custom_adam import LREQAdam
 from .graph_step import GraphReplay
 
@@ -32,8 +32,7 @@ class EmbedStep(GraphReplay):
     def begin_image(self):
         """embedding_img.py:82-83: reload the encoder checkpoint and clear the optimizer state for every image group."""
         self.E.load_state_dict(self._ckpt)
-        for p in self.E.parameters():
-            p._dge_gen = getattr(p, "_dge_gen", 0) + 1           # packed-weight caches key on this counter
+        weight_cache.written(self.E.parameters())        # (load_state_dict copies under no_grad; the packed copies key on this too)
         self._reset_opt()
 
     # ------------------------------------------------------------------ hipGraph replay of the iteration

@@ -37,7 +37,7 @@ import os
 
 import torch
 
-from . import losses, ops
+from . import losses, ops, weight_cache
 from .custom_adam import LREQAdam
 from .embedding import select_launch
 from .graph_step import GraphReplay
@@ -152,8 +152,7 @@ class LatentEmbedStep(GraphReplay):
         shape = (B, self._num_rows(), 512)
         if self.mode == "E":
             self.E.load_state_dict(self._ckpt)
-            for p in self.E.parameters():
-                p._dge_gen = getattr(p, "_dge_gen", 0) + 1
+            weight_cache.written(self.E.parameters())
             self._reset_opt()
         else:
             with torch.no_grad():

@@ -18,7 +18,6 @@ from torch import nn
 
 from . import lreq as ln
 from . import ops
-from .autograd_enc import _packed, draw_noises
 from .encoder import FromRGB
 from .stylegan1 import Blur
 from .stylegan2_generator import _dt

@@ -29,6 +29,7 @@ from . import ops
 from ._lib import lib, check, DgeError
 from .ops import _f32, _p, _stream
 from .stylegan2_generator import _dt
+from .weight_cache import lookup, store
 
 VGG16_WIDTHS = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M", 512, 512, 512, "M")
 _CPAD = 16      # first conv: 3 input channels padded to one 16-channel K chunk
@@ -89,17 +90,15 @@ class VGG16(nn.Module):
     def _packed(self, idx, dt, mode):
         conv = getattr(self.features, str(idx))
         key = (idx, dt, mode)
-        ver = (conv.weight._version, conv.weight.data_ptr())
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != ver:
+        hit = lookup(self._cache, key, conv.weight)
+        if hit is None:
             w = conv.weight.detach()
             if w.shape[1] == 3:                   # pad Cin 3 -> 16 with zeros
                 wp = torch.zeros((w.shape[0], _CPAD, 3, 3), dtype=torch.float32, device=w.device)
                 wp[:, :3] = w
                 w = wp
-            hit = (ver, ops.pack_conv_weight(w, mode, dt, 1.0))
-            self._cache[key] = hit
-        return hit[1]
+            hit = store(self._cache, key, conv.weight, ops.pack_conv_weight(w, mode, dt, 1.0))
+        return hit
 
     # ------------------------------------------------------------------ forward
     def run(self, inputs):

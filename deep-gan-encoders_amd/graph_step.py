@@ -39,7 +39,7 @@ class GraphReplay:
             if after_warmup is not None:
                 after_warmup()
         torch.cuda.current_stream().wait_stream(side)
-        from .autograd_enc import prime_pack_tables
+        from .weight_cache import prime_pack_tables
         prime_pack_tables(self.E)           # (the all-copies descriptor table must be on the device before the capture)
         graph = torch.cuda.CUDAGraph()
         # the captured iteration is RECORDED, not executed: `graph_iteration` does not move and the counters its step() calls

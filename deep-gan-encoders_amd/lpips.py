@@ -17,6 +17,7 @@ from . import ops
 from ._lib import lib, check
 from .ops import _f32, _p, _stream
 from .stylegan2_generator import _dt
+from .weight_cache import lookup, store, version
 
 _VGG = [(3, 64), (64, 64), "M", (64, 128), (128, 128), "M", (128, 256), (256, 256), (256, 256), "M",
         (256, 512), (512, 512), (512, 512), "M", (512, 512), (512, 512), (512, 512)]
@@ -115,33 +116,27 @@ class LPIPS(nn.Module):
         if hw is not None and ci > 0:       # conv5_x on the cropped images run on the low-resolution kernel: fragment-ordered copy
             mode = ops.pack_mode_for(conv.weight, mode, hw[0], hw[1], dt)
         key = (ci, dt, mode)
-        ver = (conv.weight._version, conv.weight.data_ptr(), getattr(conv.weight, "_dge_gen", 0))
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != ver:
+        hit = lookup(self._cache, key, conv.weight)
+        if hit is None:
             w = conv.weight.detach()
             if ci == 0:                 # pad Cin 3 -> 16 with zeros
                 wp = torch.zeros((w.shape[0], _CPAD, 3, 3), dtype=torch.float32, device=w.device)
                 wp[:, :3] = w
                 w = wp
-            hit = (ver, ops.pack_conv_weight(w, mode, dt, 1.0))
-            self._cache[key] = hit
-        return hit[1]
+            hit = store(self._cache, key, conv.weight, ops.pack_conv_weight(w, mode, dt, 1.0))
+        return hit
 
     def _packed_pp(self, ci):
         """shared weight image of conv ci for ops.conv_pp (cached on the weight's version)"""
         w = self.convs[ci].weight
-        ver = (w._version, w.data_ptr())
-        hit = self._cache.get(("pp", ci))
-        if hit is None or hit[0] != ver:
-            hit = (ver, ops.pack_conv_pp(w.detach().float(), 1.0))
-            self._cache[("pp", ci)] = hit
-        return hit[1]
+        hit = lookup(self._cache, ("pp", ci), w)
+        return hit if hit is not None else store(self._cache, ("pp", ci), w, ops.pack_conv_pp(w.detach().float(), 1.0))
 
     def _scaling_host(self):
         """Host copies of the ScalingLayer constants (kernel arguments); read back from the device only when the
         buffers change -- a .tolist() per call would put a device synchronisation into every loss evaluation."""
         sl = self.scaling_layer
-        key = (sl.shift._version, sl.shift.data_ptr(), sl.scale._version, sl.scale.data_ptr())
+        key = (version(sl.shift), version(sl.scale))
         hit = self._cache.get("scaling")
         if hit is None or hit[0] != key:
             hit = (key, (C.c_float * 3)(*sl.shift.flatten().tolist()), (C.c_float * 3)(*sl.scale.flatten().tolist()))

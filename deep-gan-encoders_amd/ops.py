@@ -202,12 +202,15 @@ def small_conv(H, W, kdim, nvalid, ksize=3, in_s2d=False, in_up2=False, dtype=BF
                                                int(bool(in_up2)), int(dtype)))
 
 
+def _pack_io(w, mode):
+    """(cout, cin) of the conv whose parameter w is (ConvTranspose2d parameter layout [Cin, Cout, k, k] for the SG1 up modes)"""
+    return (w.shape[1], w.shape[0]) if (mode & 0xff) in (PACK_SG1_UP, PACK_SG1_UP_DGRAD) else (w.shape[0], w.shape[1])
+
+
 def pack_dims(w, mode):
     """(nvalid, kdim) of the packed copy of w [Cout,Cin,k,k] in pack mode `mode`"""
-    cout, cin = w.shape[0], w.shape[1]
+    cout, cin = _pack_io(w, mode)
     mode &= 0xff
-    if mode in (PACK_SG1_UP, PACK_SG1_UP_DGRAD):
-        cin, cout = cout, cin
     nvalid = 4 * cout if mode in (PACK_UPFOLD, PACK_SG1_UP) else (cin if mode in (PACK_DGRAD, PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD) else cout)
     kdim = cout if mode == PACK_DGRAD else (4 * cout if mode in (PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD) else cin)
     return nvalid, kdim
@@ -223,17 +226,12 @@ def pack_mode_for(w, mode, H, W, dtype):
 def pack_conv_weight(w, mode=PACK_FWD, dtype=BF16, scale=1.0):
     """w: [Cout,Cin,k,k] f32 (reference layout) -> packed [k*k, Npad, K] tensor of `dtype`; with `mode | PACK_FRAG` the same values in
     MFMA-fragment order (the tensor carries `_dge_frag = True`, which conv2d hands on as dge_conv_desc.w_layout)."""
-    frag = bool(mode & PACK_FRAG)
-    mode_full, mode = mode, mode & 0xff
-    cout, cin, k, _ = w.shape
-    if mode in (PACK_SG1_UP, PACK_SG1_UP_DGRAD):          # ConvTranspose2d parameter layout [Cin, Cout, k, k]
-        cin, cout = cout, cin
-    nvalid = 4 * cout if mode in (PACK_UPFOLD, PACK_SG1_UP) else (cin if mode in (PACK_DGRAD, PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD) else cout)
-    kdim = cout if mode == PACK_DGRAD else (4 * cout if mode in (PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD) else cin)
+    (cout, cin), k = _pack_io(w, mode), w.shape[2]
+    nvalid, kdim = pack_dims(w, mode)
     out = torch.empty((k * k, packed_n(nvalid), kdim), dtype=tdtype(dtype), device=w.device)
-    check(lib().dge_pack_conv_weight(_f32(w.detach().contiguous()), _p(out), cout, cin, k, mode_full, dtype, float(scale),
+    check(lib().dge_pack_conv_weight(_f32(w.detach().contiguous()), _p(out), cout, cin, k, mode, dtype, float(scale),
                                      _stream()), "dge_pack_conv_weight")
-    if frag:
+    if mode & PACK_FRAG:
         out._dge_frag = True
     return out
 
@@ -259,9 +257,7 @@ def pack_conv_weights_multi(entries, scratch=None):
         return scratch
     rows = []
     for (w, mode, dtype, scale, out) in entries:
-        cout, cin, k, _ = w.shape
-        if (mode & 0xff) in (PACK_SG1_UP, PACK_SG1_UP_DGRAD):
-            cin, cout = cout, cin
+        (cout, cin), k = _pack_io(w, mode), w.shape[2]
         if not (w.is_cuda and w.is_contiguous() and w.dtype == torch.float32):
             raise DgeError("pack_conv_weights_multi: weights must be contiguous f32 device tensors")
         rows += [w.data_ptr(), out.data_ptr(), cout | (cin << 32), k | (mode << 32), dtype,

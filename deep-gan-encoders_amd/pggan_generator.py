@@ -13,6 +13,7 @@ from torch import nn
 
 from . import ops
 from .stylegan2_generator import _dt
+from .weight_cache import lookup, store
 
 _RESOLUTIONS_ALLOWED = [8, 16, 32, 64, 128, 256, 512, 1024]
 _INIT_RES = 4
@@ -31,23 +32,12 @@ class ConvBlock(nn.Module):
         self.act = ops.ACT_LRELU if activation_type == "lrelu" else ops.ACT_NONE
         self._cache = {}
 
-    def packed_dgrad(self, dtype):
-        w = self.weight
-        ver = (dtype, w._version, w.data_ptr(), getattr(w, "_dge_gen", 0))
-        hit = self._cache.get("wd")
-        if hit is None or hit[0] != ver:
-            hit = (ver, ops.pack_conv_weight(w, ops.PACK_DGRAD, dtype, self.wscale))
-            self._cache["wd"] = hit
-        return hit[1]
-
-    def packed(self, dtype):
-        w = self.weight
-        ver = (dtype, w._version, w.data_ptr(), getattr(w, "_dge_gen", 0))
-        hit = self._cache.get("w")
-        if hit is None or hit[0] != ver:
-            hit = (ver, ops.pack_conv_weight(w, ops.PACK_FWD, dtype, self.wscale))
-            self._cache["w"] = hit
-        return hit[1]
+    def packed(self, dtype, mode=ops.PACK_FWD):
+        key = (mode, dtype)
+        hit = lookup(self._cache, key, self.weight)
+        if hit is None:
+            hit = store(self._cache, key, self.weight, ops.pack_conv_weight(self.weight, mode, dtype, self.wscale))
+        return hit
 
 
 class PGGANGenerator(nn.Module):
@@ -76,7 +66,6 @@ class PGGANGenerator(nn.Module):
             self.add_module(f"layer{2 * k + 1}", ConvBlock(self.get_nf(res), self.get_nf(res)))
             self.add_module(f"output{k}", ConvBlock(self.get_nf(res), image_channels, kernel_size=1, padding=0,
                                                     wscale_gain=1.0, activation_type="linear"))
-        self._dense0 = None
 
     def get_nf(self, res):
         return min(self.fmaps_base // res, self.fmaps_max)
@@ -84,11 +73,11 @@ class PGGANGenerator(nn.Module):
     def _dense0_weight(self):
         """layer0 is conv2d(4x4, pad 3) on a 1x1 input == a dense layer: out[(y,x),o] = sum_c z_c W[o,c,3-y,3-x]."""
         L = self.layer0
-        ver = (L.weight._version, L.weight.data_ptr(), getattr(L.weight, "_dge_gen", 0))
-        if self._dense0 is None or self._dense0[0] != ver:
+        hit = lookup(L._cache, "dense0", L.weight)
+        if hit is None:
             w = L.weight.detach().flip(2, 3).permute(2, 3, 0, 1).reshape(16 * L.out_c, L.in_c).contiguous()
-            self._dense0 = (ver, w, L.bias.detach().repeat(16).contiguous())
-        return self._dense0[1], self._dense0[2]
+            hit = store(L._cache, "dense0", L.weight, (w, L.bias.detach().repeat(16).contiguous()))
+        return hit
 
     def forward(self, z, label=None, lod=None, **_unused_kwargs):
         if z.ndim != 2 or z.shape[1] != self.z_space_dim:
@@ -142,7 +131,7 @@ class PGGANGenerator(nn.Module):
         g = ops.pixelnorm_nhwc_bwd(g_xn, saved["x_last"])
         for L, x_in, y, up in reversed(saved["convs"]):
             g_pre = ops.act_bwd(g, y, None, pool=False, scale=1.0) if L.act == ops.ACT_LRELU else g
-            g_xn = ops.conv2d(g_pre, L.packed_dgrad(dt), L.in_c, 3)
+            g_xn = ops.conv2d(g_pre, L.packed(dt, ops.PACK_DGRAD), L.in_c, 3)
             if up:
                 g_xn, _ = ops.nearest_up2_bwd(g_xn)
             g = ops.pixelnorm_nhwc_bwd(g_xn, x_in)

@@ -19,6 +19,7 @@ from torch import nn
 from . import lreq as ln
 from . import ops
 from .stylegan2_generator import _dt
+from .weight_cache import lookup, store
 
 
 class Blur(nn.Module):
@@ -63,12 +64,8 @@ class DecodeBlock(nn.Module):
         if hw is not None:
             mode = ops.pack_mode_for(w, mode, hw, hw, dtype)
         key = (id(conv), mode, dtype)
-        ver = (w._version, w.data_ptr(), getattr(w, "_dge_gen", 0))
-        hit = self._cache.get(key)
-        if hit is None or hit[0] != ver:
-            hit = (ver, ops.pack_conv_weight(w, mode, dtype, 1.0))
-            self._cache[key] = hit
-        return hit[1]
+        hit = lookup(self._cache, key, w)
+        return hit if hit is not None else store(self._cache, key, w, ops.pack_conv_weight(w, mode, dtype, 1.0))
 
 
 class ToRGB(nn.Module):

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .weight_cache import lookup, store
 
 __all__ = ["StyleGAN2Generator"]
 
@@ -161,17 +162,15 @@ class ModulateConvBlock(nn.Module):
 
     # -- derived weights, rebuilt only when the parameter changes ---------------------------
     def _prepared(self, dtype):
-        key = (dtype, self.weight._version, self.weight.data_ptr(), getattr(self.weight, "_dge_gen", 0))
-        c = self._cache.get("w")
-        if c is None or c[0] != key:
+        c = lookup(self._cache, ("w", dtype), self.weight)
+        if c is None:
             mode = ops.PACK_UPFOLD if self.up else ops.PACK_FWD
             hin = self.res // 2 if self.up else self.res         # the low-resolution layers get fragment-ordered weights (conv_small)
             packed = ops.pack_conv_weight(self.weight, ops.pack_mode_for(self.weight, mode, hin, hin, dtype), dtype, self.wscale) \
                 if self.ksize == 3 else None
             wsq = ops.weight_sumsq(self.weight, self.wscale) if self.demodulate else None
-            c = (key, packed, wsq)
-            self._cache["w"] = c
-        return c[1], c[2]
+            c = store(self._cache, ("w", dtype), self.weight, (packed, wsq))
+        return c
 
     def _prepared_up(self, dtype):
         """[9 units][Cout][Cin] weights of the phase-form up kernel (ops.upconv_fir), or None when the layer shape is not
@@ -181,12 +180,8 @@ class ModulateConvBlock(nn.Module):
         if (not self.up or self.res < 32 or os.environ.get("DGE_UP_FOLDED") == "1"
                 or not ops.upconv_supported(self.in_c, self.out_c, dtype)):
             return None
-        key = (dtype, self.weight._version, self.weight.data_ptr(), getattr(self.weight, "_dge_gen", 0))
-        c = self._cache.get("wu")
-        if c is None or c[0] != key:
-            c = (key, ops.pack_upconv_weight(self.weight, dtype, self.wscale))
-            self._cache["wu"] = c
-        return c[1]
+        c = lookup(self._cache, ("wu", dtype), self.weight)
+        return c if c is not None else store(self._cache, ("wu", dtype), self.weight, ops.pack_upconv_weight(self.weight, dtype, self.wscale))
 
     def conv(self, x, s, d, noise, dt, rgb=None):
         """The modulated conv proper (:898-921) on NHWC activations: shared-weight form with s / d as prologue / epilogue scales.
