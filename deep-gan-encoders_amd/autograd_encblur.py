@@ -15,7 +15,7 @@ import torch
 from . import ops
 from .autograd_enc import draw_noises, fromrgb_param_grads, grads_in_order, linear_backward
 from .stylegan2_generator import _dt
-from .weight_cache import pack_cache, packed
+from .weight_cache import pack_cache, packed, version
 
 
 def blur_noises(E, B, R, dev):
@@ -89,6 +89,11 @@ def blur_encoder_forward(E, img, noises=None, save=False):
                 out = ops.blend(x2, z=xp, alpha=0.111, beta=0.889, stats=nstats)
             if save:
                 rec.update(y2=y2, n2=n2, a2=a2, xp=xp if has3 else None)
+                if blk.fused_scale and E.__dict__.get("_conv2_dgrad_at_forward"):
+                    # the reference's strided conv_2 convolves with a tensor DERIVED from the weight at forward time
+                    # (transform_kernel, model/utils/lreq.py:145-147), which autograd saves: its data gradient keeps reading the
+                    # forward's values after an optimizer step, while every other layer (implicit lreq) reads the live parameter
+                    rec["w2_fwd"] = (version(blk.conv_2.weight), blk.conv_2.weight.detach().clone())
         else:
             if has3:
                 raise NotImplementedError("E_Blur: last block with a channel change is not reachable with maxf-clamped widths")
@@ -152,7 +157,12 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
                 gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
                 ops.conv_wgrad(g_c2, rec["y2"], gW2)
                 grads[pre + "conv_2.weight"] = gW2
-            g_y2b = ops.conv2d(g_c2, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3)
+            snap = rec.get("w2_fwd")
+            if snap is not None and snap[0] != version(blk.conv_2.weight):      # written since the forward: the forward's values
+                w2pk = ops.pack_conv_weight(snap[1], ops.pack_mode_for(snap[1], ops.PACK_DGRAD, H, H, dt), dt, 1.0)
+            else:
+                w2pk = packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H)
+            g_y2b = ops.conv2d(g_c2, w2pk, Cc, 3)
             g_y2 = ops.blur_noise_act(g_y2b, None, None, None, blur=True, act=False)                 # Blur is self-adjoint
             dots2 = ops.dot_stats(g_y2, x1)
             if has3:

@@ -423,6 +423,67 @@ __global__ __launch_bounds__(256) void space_loss_bwd3_v4_kernel(const float* __
     *(float4*)(g + off) = make_float4(tot[0], tot[1], tot[2], tot[3]);
 }
 
+// ------------------------------------------------------------------ the window gradients kept apart (per-loss encoder updates)
+// The case-2 training loop (ablation_utils/8.E_align_x_AT1_AT2.py:70-117) makes one optimizer step per window loss, so it needs
+// weight[k] * d space_loss(window k)/db as K separate images, not their sum.  One pass over a and b; output k is written over the
+// WHOLE image (zeros outside window k): no memset in front, no atomics, the same bits in both reduction modes.  The per-element
+// expression is space_loss_bwd_kernel's, term by term (a window's image equals that kernel's output on a zeroed image).
+struct Split3 { float* g[3]; };
+__device__ __forceinline__ float split_elem(float av, float bv, const float* __restrict__ sums, const float* __restrict__ gp, int bc,
+                                            int y, int x, int h, int w, int k, float n, float wgt) {
+    const float na = sqrtf(sums[2]), nb = sqrtf(sums[3]);
+    float v = 10.f * (bv - av) / n + 3.f * (-av / (na * nb) + sums[1] * bv / (na * nb * nb * nb));
+    if (gp) {
+        const float rk = 1.f / (float)k;
+        const int oh = div_small(h, k, rk), ow = div_small(w, k, rk), qy = div_small(y, k, rk), qx = div_small(x, k, rk);
+        if (qy < oh && qx < ow) v += gp[((size_t)bc * oh + qy) * ow + qx] / (float)(k * k);
+    }
+    v *= wgt;
+    return v;
+}
+__global__ void space_loss_bwd_split_kernel(const float* __restrict__ a, const float* __restrict__ b, Split3 out,
+                                            int BC, int H, int W, Win3 wn, Bwd3 q) {
+    const long tot = (long)BC * H * W;
+    const long idx = blockIdx.x * 256L + threadIdx.x;
+    if (idx >= tot) return;
+    const int gx = idx % W; const long r = idx / W; const int gy = r % H; const int bc = r / H;
+    const float av = a[idx], bv = b[idx];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (k >= wn.n || q.wgt[k] == 0.f || !out.g[k]) continue;
+        const int ly = gy - wn.y0[k], lx = gx - wn.x0[k];
+        float v = 0.f;
+        if ((unsigned)ly < (unsigned)wn.h[k] && (unsigned)lx < (unsigned)wn.w[k])
+            v = split_elem(av, bv, q.sums[k], q.gp[k], bc, ly, lx, wn.h[k], wn.w[k], q.k[k], q.n[k], q.wgt[k]);
+        out.g[k][idx] = v;
+    }
+}
+// four consecutive pixels of a row per thread, (row, plane) from the grid (W a multiple of 4; H, W < 2^22): 16-byte loads and stores
+__global__ __launch_bounds__(256) void space_loss_bwd_split_v4_kernel(const float* __restrict__ a, const float* __restrict__ b, Split3 out,
+                                                                      int H, int W, Win3 wn, Bwd3 q) {
+    const int gx = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (gx >= W) return;
+    const int bc = blockIdx.z, gy = blockIdx.y;
+    const size_t off = ((size_t)bc * H + gy) * W + gx;
+    const float4 a4 = *(const float4*)(a + off), b4 = *(const float4*)(b + off);
+    const float av[4] = {a4.x, a4.y, a4.z, a4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        if (k >= wn.n || q.wgt[k] == 0.f || !out.g[k]) continue;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        const int ly = gy - wn.y0[k];
+        if ((unsigned)ly < (unsigned)wn.h[k]) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int lx = gx + e - wn.x0[k];
+                if ((unsigned)lx < (unsigned)wn.w[k])
+                    v[e] = split_elem(av[e], bv[e], q.sums[k], q.gp[k], bc, ly, lx, wn.h[k], wn.w[k], q.k[k], q.n[k], q.wgt[k]);
+            }
+        }
+        *(float4*)(out.g[k] + off) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+}
+
 // =================================================================== C ABI
 static Gauss11 gauss11() {
     Gauss11 G; float s = 0.f;
@@ -508,6 +569,35 @@ extern "C" int dge_space_loss_bwd3(const float* a, const float* b, const float* 
     else
         hipLaunchKernelGGL(space_loss_bwd3_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a, b, g, BC, H, W, wn, q);
     DGE_LAUNCH_CHECK("space_loss_bwd3");
+    return 0;
+}
+
+// dge_space_loss_bwd3 with the windows' gradients kept apart: g[k] ([BC,H,W], every element WRITTEN) = weight[k] * (window k's gradient)
+// inside window k and 0 outside.  weight[k] = 0 or g[k] = NULL skips window k.  No atomics: the same kernel in both reduction modes.
+extern "C" int dge_space_loss_bwd_split(const float* a, const float* b, const float* const* sums7, const float* const* g_pooled,
+                                        float* const* g, int BC, int H, int W, const int* wins, const int* ks, const float* n,
+                                        const float* weight, int nwin, hipStream_t s) {
+    Win3 wn;
+    if (win3_from(wins, nwin, H, W, wn)) return -1;
+    DGE_CHECK(a && b && sums7 && g && ks && n && weight && BC >= 1 && H >= 1 && W >= 1 && H < (1 << 22) && W < (1 << 22),
+              "space_loss_bwd_split: bad arguments");
+    Bwd3 q; Split3 out;
+    for (int k = 0; k < 3; k++) {
+        const int j = k < nwin ? k : 0;
+        q.sums[k] = sums7[j]; q.gp[k] = g_pooled ? g_pooled[j] : nullptr; q.k[k] = ks[j]; q.n[k] = n[j]; q.wgt[k] = k < nwin ? weight[j] : 0.f;
+        out.g[k] = k < nwin ? g[j] : nullptr;
+        DGE_CHECK(q.sums[k] && q.k[k] >= 1 && q.n[k] > 0.f, "space_loss_bwd_split: bad window %d", k);
+        DGE_CHECK(!q.gp[k] || (wn.h[k] / q.k[k] >= 1 && wn.w[k] / q.k[k] >= 1), "space_loss_bwd_split: window %d smaller than its pooling factor", k);
+    }
+    if (W % 4 == 0 && H <= 65535 && BC <= 65535) {
+        hipLaunchKernelGGL(space_loss_bwd_split_v4_kernel, dim3((unsigned)((W / 4 + 255) / 256), H, BC), dim3(256), 0, s, a, b, out, H, W, wn, q);
+        dge_note_kernel("space_loss_bwd_split_v4");
+    } else {
+        const long tot = (long)BC * H * W;
+        hipLaunchKernelGGL(space_loss_bwd_split_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a, b, out, BC, H, W, wn, q);
+        dge_note_kernel("space_loss_bwd_split");
+    }
+    DGE_LAUNCH_CHECK("space_loss_bwd_split");
     return 0;
 }
 

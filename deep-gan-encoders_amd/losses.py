@@ -122,10 +122,12 @@ def _side_streams(dev, n):
     return have[:n]
 
 
-def _space_loss_windows3(a, b, wins, lpips_model, weights, g, need, gb=None):
+def _space_loss_windows3(a, b, wins, lpips_model, weights, g, need, gb=None, g_split=None):
     """The three nested attention windows of image_loss_tsa with every image pass merged (dge_loss_reduce3, dge_crop_pool_multi,
     dge_space_loss_bwd3): `g` (or None) is WRITTEN with the weighted sum of the windows' gradients; need[i] False leaves window i
-    out of the gradient.  Same arithmetic as _window_reduce / _window_finish per window."""
+    out of the gradient.  Same arithmetic as _window_reduce / _window_finish per window.
+    `g_split` (image_losses_split; `g` is None then): one full-size image or None per window, each WRITTEN with its own window's
+    weighted gradient (dge_space_loss_bwd_split) instead of the sum."""
     import ctypes as C
     B, Cc, H, W = a.shape
     dev = a.device
@@ -165,7 +167,7 @@ def _space_loss_windows3(a, b, wins, lpips_model, weights, g, need, gb=None):
         y0, x0, h, w = win
         ap, bp, k = aps[i], bps[i], ks[i]
         hp, wp = h // k, w // k
-        ng = g is not None and need[i]
+        ng = (g is not None or g_split is not None) and need[i]
         strm = side[i - 1] if (fork and i > 0) else None
         if strm is not None:
             strm.wait_stream(main)
@@ -213,6 +215,52 @@ def _space_loss_windows3(a, b, wins, lpips_model, weights, g, need, gb=None):
         ww = (C.c_float * nw)(*[float(weights[i]) if sts[i]["ng"] else 0.0 for i in range(nw)])
         kk = (C.c_int * nw)(*ks)
         check(L.dge_space_loss_bwd3(_f32(a), _f32(b), sp, gpp, _p(g), B * Cc, H, W, wflat, kk, nn, ww, nw, _stream()), "dge_space_loss_bwd3")
+    if g_split is not None:
+        _bwd_split(a, b, wins, [pack[i, 0:8] for i in range(nw)], gps, ks, [st["n"] for st in sts],
+                   [float(weights[i]) if sts[i]["ng"] else 0.0 for i in range(nw)], g_split)
+    return outs
+
+
+def _bwd_split(a, b, wins, sums, gps, ks, ns, wts, outs):
+    """One dge_space_loss_bwd_split launch: outs[k] (or None) is WRITTEN with wts[k] * (window k's gradient), zeros outside it."""
+    import ctypes as C
+    if all(t is None for t in outs):
+        return
+    B, Cc, H, W = a.shape
+    nw = len(wins)
+    ptrs = lambda ts: (C.c_void_p * nw)(*[(t.data_ptr() if t is not None else None) for t in ts])
+    wflat = (C.c_int * (4 * nw))(*[int(v) for win in wins for v in win])
+    check(lib().dge_space_loss_bwd_split(_f32(a), _f32(b), ptrs(sums), ptrs(gps), ptrs(outs), B * Cc, H, W, wflat, (C.c_int * nw)(*ks),
+                                         (C.c_float * nw)(*ns), (C.c_float * nw)(*wts), nw, _stream()), "dge_space_loss_bwd_split")
+    if ops.KERNEL_LOG is not None:
+        from ._lib import last_kernel
+        ops.KERNEL_LOG.append((last_kernel(), _stream()))
+
+
+def _space_loss_windows_split(a, b, wins, lpips_model, weights, g_split, gb=None):
+    """_space_loss_windows3 with g_split in deterministic mode: the per-window reductions of _window_reduce (dge_loss_reduce3 is
+    not offered there), the pooled gradients of _window_finish, then the same single dge_space_loss_bwd_split launch."""
+    B, Cc = a.shape[:2]
+    L = lib()
+    world = gb.world if gb is not None else 1
+    pack = ops.zeros((len(wins), _PK), a.device)
+    sts = [_window_reduce(a, b, win, True, lpips_model, g_split[i] is not None, pack[i], world) for i, win in enumerate(wins)]
+    if gb is not None:
+        gb.reduce(pack)
+    outs, gps = [], []
+    for i, st in enumerate(sts):
+        gp = None
+        if g_split[i] is not None:
+            bp = st["bp"]
+            gp = torch.empty_like(bp)
+            check(L.dge_ssim_bwd(_p(st["ap"]), _p(bp), _p(st["dmap"]), _p(gp), B * Cc, bp.shape[2], bp.shape[3], -1.0 / st["npool"], 0,
+                                 _stream()), "dge_ssim_bwd")
+            if st["g_lp"] is not None:
+                check(L.dge_axpy_scalar(_p(st["g_lp"]), None, _p(gp), gp.numel(), 2.0 / world, 1, _stream()), "dge_axpy_scalar")
+        gps.append(gp)
+        outs.append(_window_finish(a, b, st, True, weights[i], None, False, world))
+    _bwd_split(a, b, wins, [pack[i, 0:8] for i in range(len(wins))], gps, [st["k"] for st in sts], [st["n"] for st in sts],
+               [float(weights[i]) if g_split[i] is not None else 0.0 for i in range(len(wins))], g_split)
     return outs
 
 
@@ -276,6 +324,30 @@ def image_loss_tsa(imgs1, imgs2, lpips_model=None, weights=(1.0, 5.0, 9.0), glob
     if need:
         loss = _ScaledGrad.apply(imgs2, loss, g)
     return loss, info
+
+
+def image_losses_split(imgs1, imgs2, lpips_model=None, weights=(1.0, 5.0, 9.0), windows=(True, True, True), global_batch=None):
+    """The three image losses of the per-loss-update loop (ablation_utils/8.E_align_x_AT1_AT2.py:72-101), each with a gradient of
+    its own: returns ([loss_imgs, 5*loss_medium, 9*loss_small], info [3,8] as image_loss_tsa).  One evaluation serves all three:
+    the reductions, crops, SSIM and LPIPS passes are image_loss_tsa's, and one dge_space_loss_bwd_split launch writes the three
+    gradient images.  windows[k] False: loss k is a plain value (its info row is kept), no gradient work is done for it.
+    No host synchronisation."""
+    a = imgs1.detach().float().contiguous()
+    b = imgs2.detach().float().contiguous()
+    need = imgs2.requires_grad and torch.is_grad_enabled()
+    wins = attention_windows(a.shape[2], a.shape[3])
+    want = [bool(need and windows[i]) for i in range(3)]
+    gs = [torch.empty_like(b) if want[i] else None for i in range(3)]
+    if not ops.is_deterministic():
+        infos = _space_loss_windows3(a, b, wins, lpips_model, weights, None, want, gb=global_batch, g_split=gs)
+    else:
+        infos = _space_loss_windows_split(a, b, wins, lpips_model, weights, gs, gb=global_batch)
+    info = torch.stack(infos)
+    out = []
+    for i in range(3):
+        loss = info[i, 0] * float(weights[i])
+        out.append(_ScaledGrad.apply(imgs2, loss, gs[i]) if want[i] else loss)
+    return out, info
 
 
 def space_loss(imgs1, imgs2, image_space=True, lpips_model=None, global_batch=None):

@@ -276,6 +276,13 @@ int dge_crop_pool_multi(const float* const* src, float* const* dst, const int* w
                         dge_stream_t stream);
 int dge_space_loss_bwd3(const float* a, const float* b, const float* const* sums7, const float* const* g_pooled, float* g, int BC, int H,
                         int W, const int* wins, const int* ks, const float* n, const float* weight, int nwin, dge_stream_t stream);
+/* dge_space_loss_bwd3 with the windows' gradients kept APART (one optimizer step per window loss, dge_amd.e_align_case2): g = nwin
+ * pointers to [BC,H,W] images; image k is WRITTEN everywhere: weight[k] * (gradient of window k) inside window k, 0 outside (no
+ * memset, no atomics: the same bits in both reduction modes).  weight[k] = 0 or g[k] = NULL skips window k.  The per-element
+ * arithmetic is dge_space_loss_bwd's.  dge_last_kernel: "space_loss_bwd_split_v4" (W % 4 == 0) or "space_loss_bwd_split". */
+int dge_space_loss_bwd_split(const float* a, const float* b, const float* const* sums7, const float* const* g_pooled, float* const* g,
+                             int BC, int H, int W, const int* wins, const int* ks, const float* n, const float* weight, int nwin,
+                             dge_stream_t stream);
 /* y (+)= x * scalar[0] * extra  (scalar may be NULL) */
 int dge_axpy_scalar(const float* x, const float* scalar, float* y, long n, float extra, int accumulate, dge_stream_t stream);
 

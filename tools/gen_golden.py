@@ -1516,6 +1516,171 @@ def gen_step_z():
 
 SECTIONS["step_z"] = gen_step_z
 
+# --------------------------------------------------------------------------- case 2: one optimizer step per loss, E_Blur
+_CASE2_KEYS = ("decode_block.0.conv_1.weight", "decode_block.3.conv_2.weight", "decode_block.4.inver_mod2.weight",
+               "decode_block.1.bias_1", "FromRGB.from_rgb.weight")
+_CASE2_HEAD = 2048          # larger tensors are stored as their first _CASE2_HEAD elements (flattened)
+
+
+def _case2_run(kind, phases, latent, scale, dtype, full):
+    """Two iterations of the REFERENCE's per-loss-update loop (8.E_align_x_AT1_AT2.py:56-117 for kind 'sg1', the mtype-2 branch of
+    Cat256/E_align_case_2.py:102-228 for 's2') with E_Blur.BE at reduced size, in `dtype`.  The loop body below is the scripts'
+    call sequence on the imported reference modules; `phases` / `latent` select the steps a script lower on the ladder keeps."""
+    import warnings
+    import model.E.E_Blur as EB
+    import training_utils as TU
+    from model.utils.custom_adam import LREQAdam
+    from oracle import lpips_ref as LR
+
+    B, L = 2, 5
+    cast = lambda t: t.to(dtype) if torch.is_floating_point(t) else t
+    if kind == "sg1":
+        import model.stylegan1.net as SG1
+        Gs = SG1.Generator(startf=16, maxf=64, layer_count=L, latent_size=512, channels=3)
+        sd = R.fill_encoder(shapes_of(Gs.state_dict()), seed=43)
+        for k in sd:
+            if k.endswith("blur.weight"):
+                sd[k] = Gs.state_dict()[k].clone()
+            if k == "const":
+                sd[k] = R.randn("sg1step.const", tuple(sd[k].shape), 43)
+        Gs.load_state_dict(sd)
+        Gm = SG1.Mapping(num_layers=2 * L, mapping_layers=8, latent_size=512, dlatent_size=512, mapping_fmaps=512)
+        Gm.load_state_dict({k: R.randn("sg1step.m." + k, tuple(v.shape), 44, 0.05 if k.endswith("weight") else 0.01)
+                            for k, v in Gm.state_dict().items()})
+        Gm.buffer1 = cast(R.randn("sg1step.buffer1", (2 * L, 512), 44, 0.5))
+        Gm.eval()
+        Gs.to(dtype); Gm.to(dtype)
+        const1 = Gs.const.repeat(B, 1, 1, 1).detach().clone()
+        layer_idx = torch.arange(2 * L)[np.newaxis, :, np.newaxis]
+        ones = torch.ones(layer_idx.shape, dtype=torch.float32)
+        coefs = cast(torch.where(layer_idx < L, 0.7 * ones, ones))
+        lod = L - 1
+    else:
+        from model.stylegan2_generator import StyleGAN2Generator
+        G = StyleGAN2Generator(64, fmaps_base=2048, fmaps_max=128)
+        G.load_state_dict(R.fill_s2(shapes_of(G.state_dict()), seed=11))
+        G.to(dtype)
+    E = EB.BE(startf=16, maxf=64, layer_count=L)
+    sd = R.fill_encoder(shapes_of(E.state_dict()), seed=31)
+    for k in sd:
+        if k.endswith("blur.weight"):
+            sd[k] = E.state_dict()[k].clone()
+    E.load_state_dict(sd)
+    E.to(dtype)
+    LP = {k: cast(v) for k, v in LR.seeded_params(0).items()}
+    lp = lambda a, b: LR.lpips(LP, a, b)
+    opt = LREQAdam([{"params": E.parameters()}], lr=0.0015, betas=(0.0, 0.99), weight_decay=0)
+    out = {}
+    new_z = cast(R.randn("step.new_z", (B, 512), 1))
+    orig_randn_like = torch.randn_like
+    torch.randn_like = lambda t, **kw: new_z.clone()
+    flat = lambda inf: [inf[0][0], inf[0][1], inf[0][2], inf[1], inf[2], inf[3], inf[4]]
+
+    def snap(it, phase):
+        for k in _CASE2_KEYS:
+            v = E.state_dict()[k]
+            out[f"it{it}_after_phase{phase}:{k}"] = (v.flatten()[:_CASE2_HEAD] if v.numel() > _CASE2_HEAD else v).clone()
+    try:
+        for it in range(2):
+            pfx = "c2sg1" if kind == "sg1" else "c2s2"
+            with _NoiseFeeder(f"{pfx}.it{it}", 1) as nf:
+                if kind == "sg1":
+                    z = cast(R.randn(f"sg1step.z{it}", (B, 512), 1))
+                    with torch.no_grad():
+                        w1 = Gm(z, coefs_m=coefs)
+                        imgs1 = Gs.forward(w1, lod)
+                    n_first = len(nf.log)
+                    const2, w2 = E(imgs1)
+                    n_enc = len(nf.log) - n_first
+                    imgs2 = Gs.forward(w2, lod)
+                else:
+                    np.random.seed(it)
+                    z = cast(R.randn(f"step.z{it}", (B, 512), 1))
+                    with torch.no_grad():
+                        r = G(z, trunc_psi=0.7, trunc_layers=8, randomize_noise=False)
+                    imgs1, w1 = r["image"], r["wp"]
+                    n_first = len(nf.log)
+                    const2, w2 = E(imgs1)
+                    n_enc = len(nf.log) - n_first
+                    imgs2 = G.synthesis(w2)["image"]
+            if it == 0:
+                out["noise_shapes"] = np.array([list(s_) + [0] * (4 - len(s_)) for s_ in nf.log])
+                out["noise_split"] = np.array([n_first, n_enc])
+            phase = 0
+            vals = {}
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                opt.zero_grad()
+                loss_imgs, i_i = TU.space_loss(imgs1, imgs2, lpips_model=lp)
+                vals["imgs"] = float(loss_imgs)
+                if "imgs" in phases:
+                    opt.zero_grad()
+                    loss_imgs.backward(retain_graph=True)
+                    opt.step()
+                    phase += 1; snap(it, phase)
+                m1 = imgs1[:, :, :, imgs1.shape[3] // 8:-imgs1.shape[3] // 8]
+                m2 = imgs2[:, :, :, imgs2.shape[3] // 8:-imgs2.shape[3] // 8]
+                loss_medium, i_m = TU.space_loss(m1, m2, lpips_model=lp)
+                loss_medium = loss_medium * 5
+                vals["AT1"] = float(loss_medium)
+                if "AT1" in phases:
+                    opt.zero_grad()
+                    loss_medium.backward(retain_graph=True)
+                    opt.step()
+                    phase += 1; snap(it, phase)
+                o = imgs1.shape[2] // 8 + imgs1.shape[2] // 32
+                loss_small, i_s = TU.space_loss(imgs1[:, :, o:-o, o:-o], imgs2[:, :, o:-o, o:-o], lpips_model=lp)
+                loss_small = loss_small * 9
+                vals["AT2"] = float(loss_small)
+                if "AT2" in phases:
+                    opt.zero_grad()
+                    loss_small.backward(retain_graph=True)
+                    opt.step()
+                    phase += 1; snap(it, phase)
+                loss_w, i_w = TU.space_loss(w1, w2, image_space=False)
+                total = loss_w
+                i_c = None
+                if "c" in latent:
+                    loss_c, i_c = TU.space_loss(const1, const2, image_space=False)
+                    total = loss_w + loss_c
+                    vals["c"] = float(loss_c)
+                loss_mslv = total * scale if scale != 1.0 else total
+                opt.zero_grad()
+                loss_mslv.backward()
+                opt.step()
+                phase += 1; snap(it, phase)
+            out[f"it{it}_losses"] = np.array([vals["imgs"], vals["AT1"], vals["AT2"], float(loss_w), vals.get("c", 0.0), float(loss_mslv)])
+            out[f"it{it}_param_checksum"] = np.array(R.checksum({k: v.float() for k, v in E.state_dict().items()}))
+            if full:
+                out[f"it{it}_imgs1"], out[f"it{it}_w1"] = imgs1, w1
+                out[f"it{it}_w2"], out[f"it{it}_imgs2"], out[f"it{it}_const2"] = w2.detach(), imgs2.detach(), const2.detach()
+                out[f"it{it}_info"] = np.array([flat(i_i), flat(i_m), flat(i_s), flat(i_w)] + ([flat(i_c)] if i_c is not None else []))
+    finally:
+        torch.randn_like = orig_randn_like
+    return out
+
+
+def _case2_golden(name, kind, phases, latent, scale, full=True):
+    """f32 run = the golden; the same run in float64 gives `<key>_ref_spread` = max |f32 - f64| / max |f64| of every stored float
+    quantity: the reference's own rounding over the chain of optimizer steps (tests allow max(project tolerance, 4 x spread))."""
+    o32 = _case2_run(kind, phases, latent, scale, torch.float32, full)
+    o64 = _case2_run(kind, phases, latent, scale, torch.float64, full)
+    out = {}
+    for k, v in o32.items():
+        out[k] = v.float() if torch.is_tensor(v) else v
+        if k.startswith("noise_"):
+            continue
+        a = torch.as_tensor(np.asarray(v.detach() if torch.is_tensor(v) else v)).double()
+        b = torch.as_tensor(np.asarray(o64[k].detach() if torch.is_tensor(o64[k]) else o64[k])).double()
+        out[k + "_ref_spread"] = np.array(float((a - b).abs().max() / (b.abs().max() + 1e-300)))
+    save_npz(name, **out)
+
+
+SECTIONS["step_case2_sg1"] = lambda: _case2_golden("step_case2_sg1.npz", "sg1", ("imgs", "AT1", "AT2"), ("w", "c"), 0.01)
+SECTIONS["step_case2_s2"] = lambda: _case2_golden("step_case2_s2.npz", "s2", ("imgs", "AT1", "AT2"), ("w",), 1.0)
+SECTIONS["step_case2_sub"] = lambda: _case2_golden("step_case2_sub.npz", "sg1", ("imgs",), ("w", "c"), 0.01, full=False)
+
+
 if __name__ == "__main__":
     todo = sys.argv[1:] or list(SECTIONS)
     for s_ in todo:
