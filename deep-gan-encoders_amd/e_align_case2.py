@@ -22,12 +22,14 @@ PRESETS).  zero_grad() drops the gradients (torch >= 2.0): a parameter without a
 Eager launches only: capture() raises (a replayed graph of the four-phase iteration has not been validated).  Single process,
 --mtype 1 and 2, E_Blur only; everything else raises.
 """
-import math
+import os
 
 import torch
+import torch.distributed as dist
 
-from . import losses
-from .e_align import EAlignStep, _StyleGAN1Adapter, _StyleGAN2Adapter, load_lpips_weights, set_seed
+from . import losses, models, ops
+from .generators import generator_family
+from .train_step import TrainStep
 
 IMAGE_PHASES = ("imgs", "AT1", "AT2")          # the order of the scripts' optimizer steps; also the window order of the loss
 LATENT_TERMS = ("w", "c")
@@ -55,22 +57,20 @@ def _names(what, given, known):
     return tuple(n for n in known if n in given)          # the scripts' order
 
 
-class Case2Step(EAlignStep):
+class Case2Step(TrainStep):
     def __init__(self, generator, E, lpips_model, mapping=None, image_phases=IMAGE_PHASES, latent_terms=LATENT_TERMS,
                  latent_scale=0.01, lr=0.0015, beta_1=0.0, batch_size=2, z_dim=512, reference_noise=False):
         """`generator` + `mapping`: the StyleGAN1 Gs and Gm (mtype 1), or a StyleGAN2Generator alone (mtype 2; latent term `w`
         only).  `E`: encoder_variants.BlurBE.  `image_phases`: which of imgs / AT1 / AT2 get an optimizer step of their own;
         `latent_terms`: the terms of the last step's loss, (sum of terms) * latent_scale."""
-        from .biggan_generator import BigGAN
         from .encoder_variants import BlurBE
-        from .pggan_generator import PGGANGenerator
-        from .stylegan2_generator import StyleGAN2Generator
         self.image_phases = _names("image_phases", image_phases, IMAGE_PHASES)
         self.latent_terms = _names("latent_terms", latent_terms, LATENT_TERMS)
-        if isinstance(generator, (PGGANGenerator, BigGAN)):
+        family = generator_family(generator)
+        if family in ("pggan", "biggan"):
             raise ValueError("Case2Step: --mtype 3 (PGGAN) and 4 (BigGAN) have no case-2 script with E_Blur; supported: StyleGAN1 "
                              "(Gs with mapping=Gm) and StyleGAN2")
-        if mapping is None and not isinstance(generator, StyleGAN2Generator):
+        if mapping is None and family != "stylegan2":
             raise ValueError("Case2Step: pass the StyleGAN1 synthesis network together with mapping=Gm (mtype 1) or a "
                              "StyleGAN2Generator (mtype 2)")
         if not isinstance(E, BlurBE):
@@ -79,10 +79,10 @@ class Case2Step(EAlignStep):
         if mapping is None and "c" in self.latent_terms:
             raise ValueError("Case2Step: latent term 'c' is not offered for StyleGAN2: Cat256/E_align_case_2.py:221-228 logs loss_c "
                              "and trains on loss_w alone; use latent_terms=('w',)")
-        super().__init__(generator, E, lpips_model, lr=lr, beta_1=beta_1, batch_size=batch_size, z_dim=z_dim,
-                         reference_noise=reference_noise, mapping=mapping)
-        if self.world > 1 or self.dist_on:
+        if dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get("DGE_FORCE_DIST") == "1"):
             raise RuntimeError("Case2Step runs in a single process (the case-2 scripts have no data-parallel form)")
+        super().__init__(generator, E, lpips_model, mapping=mapping, lr=lr, beta_1=beta_1, batch_size=batch_size, z_dim=z_dim,
+                         reference_noise=reference_noise)
         self.latent_scale = float(latent_scale)
         # phases 2.. back-propagate after optimizer steps: the strided conv_2 of E_Blur then reads the forward's weights in the
         # reference, every other layer the live ones (autograd_encblur.blur_encoder_forward)
@@ -110,23 +110,7 @@ class Case2Step(EAlignStep):
         mixing) replay captured reference inputs in parity runs.  Returns `self.last` (detached tensors, no host synchronisation)."""
         if prefetch_next:
             raise ValueError("Case2Step.step: prefetch_next is not offered (the generator pass opens its own iteration)")
-        from . import ops
-        E, B = self.E, self.batch_size
-        sg1 = isinstance(self.gen, _StyleGAN1Adapter)
-        if isinstance(self.gen, _StyleGAN2Adapter):
-            self.gen.new_z = new_z
-        ops.zero_arena_begin(self.dev)
-        if z is None or not z.is_cuda:
-            set_seed(iteration % 30000)
-        if z is None:
-            z = torch.randn(B, self.z_dim)
-        z = self._upload(z)
-        with torch.no_grad():
-            imgs1, w1 = self.gen.sample(z, gen_noises[0])
-        if noises is None and self.reference_noise:
-            noises = self._encoder_noises(imgs1.shape[2])
-        const2, w2 = E(imgs1, noises=noises)
-        imgs2 = self.gen.synth(w2, gen_noises[1])
+        z, imgs1, w1, const2, w2, imgs2 = self._head(iteration, z, noises, gen_noises, new_z)
 
         # every window's loss and gradient image from one evaluation, in front of the first optimizer step
         on = tuple(n in self.image_phases for n in IMAGE_PHASES)
@@ -143,8 +127,8 @@ class Case2Step(EAlignStep):
             loss_w, info_w = losses.space_loss(w1, w2, image_space=False)
             total = loss_w
         if "c" in self.latent_terms:
-            if self.const1 is None or self.const1.shape[0] != B:
-                self.const1 = self.G.const.detach().repeat(B, 1, 1, 1).float().clone()         # 8.E_align_x_AT1_AT2.py:30-31
+            if self.const1 is None or self.const1.shape[0] != self.batch_size:
+                self.const1 = self.G.const.detach().repeat(self.batch_size, 1, 1, 1).float().clone()         # 8.E_align_x_AT1_AT2.py:30-31
             loss_c, info_c = losses.space_loss(self.const1, const2, image_space=False)
             total = loss_c if total is None else total + loss_c
         loss_mslv = total * self.latent_scale if self.latent_scale != 1.0 else total
@@ -152,7 +136,7 @@ class Case2Step(EAlignStep):
         loss_mslv.backward()
         self.opt.step()
         ops.zero_arena_end()
-        det = lambda t: t.detach() if torch.is_tensor(t) else t
+        det = self.det
         self.last = dict(imgs1=imgs1, imgs2=det(imgs2), w1=det(w1), w2=det(w2), const2=det(const2), info_img=info_img,
                          phase_losses={n: det(img_losses[k]) for k, n in enumerate(IMAGE_PHASES) if on[k]},
                          loss_imgs=det(img_losses[0]), loss_medium=det(img_losses[1]), loss_small=det(img_losses[2]),
@@ -160,38 +144,26 @@ class Case2Step(EAlignStep):
         return self.last
 
 
-def _blur_encoder(img_size, start_features, compute_dtype, device):
-    from .encoder_variants import BlurBE
-    return BlurBE(startf=start_features, maxf=512, layer_count=int(math.log2(img_size) - 1), latent_size=512,
-                  compute_dtype=compute_dtype).to(device)
-
-
 def build_models(mtype=1, img_size=256, start_features=64, compute_dtype="bf16", device="cuda", lpips=True, seed=0):
     """(G, Gm | None, E_Blur, LPIPS | None) with seeded random-init weights (tests, the timing tool); no checkpoints ship."""
-    from . import e_align
     if mtype == 1:
-        Gs, Gm, _, LP = e_align.build_models_sg1(img_size, start_features, compute_dtype, device=device, lpips=lpips, seed=seed, encoder=False)
+        Gs, Gm, _, LP = models.build_models_sg1(img_size, start_features, compute_dtype, device=device, lpips=lpips, seed=seed, encoder=False)
     elif mtype == 2:
-        Gs, _, LP = e_align.build_models(img_size, start_features, compute_dtype, device=device, lpips=lpips, seed=seed)
+        Gs, _, LP = models.build_models(img_size, start_features, compute_dtype, device=device, lpips=lpips, seed=seed)
         Gm = None
     else:
         raise ValueError("case 2 is offered for --mtype 1 (StyleGAN1) and 2 (StyleGAN2)")
-    return Gs, Gm, _blur_encoder(img_size, start_features, compute_dtype, device), LP
+    return Gs, Gm, models.blur_encoder(img_size, start_features, compute_dtype, device), LP
 
 
 def load_models(args, device="cuda", lpips=True):
-    """Generator checkpoints through e_align.load_models; the encoder is E_Blur with the optional --checkpoint_dir_E state_dict."""
-    from . import e_align
+    """Generator checkpoints through models.load_models; the encoder is E_Blur with the optional --checkpoint_dir_E state_dict."""
     if args.mtype not in (1, 2):
         raise ValueError("case 2 is offered for --mtype 1 (StyleGAN1) and 2 (StyleGAN2); 3 and 4 have no E_Blur case-2 script")
-    ckpt_e, args.checkpoint_dir_E = args.checkpoint_dir_E, None          # (mtype 2 builds an E.BE there: not loaded, not used)
-    try:
-        G, Gm, _, LP = e_align.load_models(args, device=device, lpips=lpips, encoder=False)
-    finally:
-        args.checkpoint_dir_E = ckpt_e
-    E = _blur_encoder(args.img_size, args.start_features, getattr(args, "compute_dtype", "bf16"), device)
-    if ckpt_e is not None:
-        E.load_state_dict(torch.load(ckpt_e, map_location="cpu"))
+    G, Gm, _, LP = models.load_models(args, device=device, lpips=lpips, encoder=False)
+    E = models.blur_encoder(args.img_size, args.start_features, getattr(args, "compute_dtype", "bf16"), device)
+    if args.checkpoint_dir_E is not None:
+        E.load_state_dict(torch.load(args.checkpoint_dir_E, map_location="cpu"))
     return G, Gm, E, LP
 
 
@@ -211,14 +183,9 @@ def resolve_recipe(args):
 def train(tensor_writer=None, args=None):
     """The scripts' train(): info rows printed every iteration there, written to Loss.txt every 100 (here: printed every 100),
     E_model_ep%d_iter%d.pth every 5000 (8.E_align_x_AT1_AT2.py:175-190)."""
-    import os
-    if getattr(args, "deterministic", False):
-        from . import ops
-        ops.set_deterministic(True)
     phases, latent, scale = resolve_recipe(args)
     G, Gm, E, LP = load_models(args)
-    load_lpips_weights(LP, getattr(args, "vgg_weights", None), getattr(args, "lpips_weights", None),
-                       allow_standin=getattr(args, "allow_standin_lpips", False))
+    models.prepare_training(args, LP)
     st = Case2Step(G, E, LP, mapping=Gm, image_phases=phases, latent_terms=latent, latent_scale=scale, lr=args.lr,
                    beta_1=args.beta_1, batch_size=args.batch_size, z_dim=args.z_dim)
     out_dir = args.experiment_dir
@@ -246,29 +213,14 @@ def train(tensor_writer=None, args=None):
 def build_parser():
     import argparse
     parser = argparse.ArgumentParser(description="the training args (case 2: one optimizer step per loss, E_Blur)")
-    parser.add_argument("--iterations", type=int, default=60001)
-    parser.add_argument("--lr", type=float, default=0.0015)
-    parser.add_argument("--beta_1", type=float, default=0.0)
-    parser.add_argument("--batch_size", type=int, default=2)
-    parser.add_argument("--experiment_dir", default=None)
-    parser.add_argument("--checkpoint_dir_GAN", default=None)
-    parser.add_argument("--config_dir", default=None)
-    parser.add_argument("--checkpoint_dir_E", default=None)
-    parser.add_argument("--img_size", type=int, default=1024)
-    parser.add_argument("--img_channels", type=int, default=3)
-    parser.add_argument("--z_dim", type=int, default=512)
-    parser.add_argument("--mtype", type=int, default=1)
-    parser.add_argument("--start_features", type=int, default=16)
+    models.add_train_args(parser, iterations=60001)
+    models.add_model_args(parser)
+    parser.set_defaults(mtype=1)
     # not in the reference
     parser.add_argument("--preset", choices=sorted(PRESETS), default=None, help="the loop body of one script: sets --phases, --latent, --latent_scale")
     parser.add_argument("--phases", default=None, help="image losses with an optimizer step of their own, e.g. imgs,AT1,AT2")
     parser.add_argument("--latent", default=None, help="terms of the latent loss: w or w,c")
     parser.add_argument("--latent_scale", type=float, default=None)
-    parser.add_argument("--compute_dtype", default="bf16")
-    parser.add_argument("--vgg_weights", default=None, help="torchvision vgg16 checkpoint (features.*) or an lpips.LPIPS state_dict")
-    parser.add_argument("--lpips_weights", default=None, help="the lpips package's weights/v0.1/vgg.pth (lin{k}.model.1.weight)")
-    parser.add_argument("--deterministic", action="store_true", help="bit-reproducible reductions: ops.set_deterministic")
-    parser.add_argument("--allow_standin_lpips", action="store_true", help="train on seeded stand-in LPIPS weights (NOT the reference objective)")
     return parser
 
 

@@ -14,34 +14,27 @@ The second backward runs on the weights the first step already updated, as in th
 of Gs or Gm is formed (the reference accumulates them, no optimizer reads them).  StyleGAN1 only (--mtype 1, the
 reference prints `error` for any other type); single process only.
 """
-import math
+import os
 
 import torch
 import torch.distributed as dist
 
-from . import losses
-from .custom_adam import LREQAdam
-from .e_align import _StyleGAN1Adapter, load_lpips_weights, set_seed
+from . import losses, models
+from .train_step import TrainStep
 
 
-class EAlignZStep:
+class EAlignZStep(TrainStep):
     def __init__(self, Gs, Gm, E, lpips_model, lr=0.0015, beta_1=0.0, batch_size=2, z_dim=512):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("EAlignZStep runs in a single process (1.E_align_z.py has no data-parallel form)")
-        self.G, self.Gm, self.E, self.lpips = Gs, Gm, E, lpips_model
-        self.gen = _StyleGAN1Adapter(Gs, Gm)       # coefs: psi 0.7 on the first half of the layers; lod = layer_count - 1
-        self.opt = LREQAdam([{"params": E.parameters()}], lr=lr, betas=(beta_1, 0.99), weight_decay=0)
-        self.batch_size, self.z_dim = batch_size, z_dim
-        self.dev = next(E.parameters()).device
-        self.last = {}
+        super().__init__(Gs, E, lpips_model, mapping=Gm, lr=lr, beta_1=beta_1, batch_size=batch_size, z_dim=z_dim)
+        self.Gm = Gm
 
     def step(self, iteration, z=None, gen_noises=(None, None)):
         """`z`: optional z_c1 [B, 512] (parity runs), else drawn after set_seed(iteration % 30000) on the CPU generator as the
         reference does; `gen_noises`: optional (first, second) lists of StyleGAN1 noise tensors in the reference's draw order."""
-        B = self.batch_size
         if z is None:
-            set_seed(iteration % 30000)
-            z = torch.randn(B, self.z_dim)
+            z = self._draw_z(iteration)
         z_c1 = z.to(self.dev, non_blocking=True).float().contiguous()
         with torch.no_grad():
             imgs1, w1 = self.gen.sample(z_c1, gen_noises[0])
@@ -60,32 +53,25 @@ class EAlignZStep:
         self.opt.zero_grad()
         loss_mslv.backward()
         self.opt.step()
-        det = lambda t: t.detach() if torch.is_tensor(t) else t
+        det = self.det
         self.last = dict(imgs1=imgs1, imgs2=det(imgs2), w1=w1, w2=det(w2), z_c1=z_c1, z_c2=det(z_c2), loss_imgs=loss_imgs.detach(),
                          info_img=info_img, loss_c=loss_c.detach(), info_c=info_c)
         return self.last
 
 
 def build_models_z(img_size=1024, start_features=16, compute_dtype="bf16", device="cuda", lpips=True):
-    """Gs, Gm (seeded random init, e_align.build_models_sg1) and a fresh E_Blur_Z; checkpoints are loaded by `load_models`."""
-    from .e_align import build_models_sg1
-    from .encoder_variants import BlurBEZ
-    Gs, Gm, _, LP = build_models_sg1(img_size, start_features, compute_dtype, device=device, lpips=lpips, encoder=False)
-    E = BlurBEZ(startf=start_features, maxf=512, layer_count=int(math.log2(img_size) - 1), latent_size=512,
-                compute_dtype=compute_dtype).to(device)
-    return Gs, Gm, E, LP
+    """Gs, Gm (seeded random init, models.build_models_sg1) and a fresh E_Blur_Z; checkpoints are loaded by `load_models`."""
+    Gs, Gm, _, LP = models.build_models_sg1(img_size, start_features, compute_dtype, device=device, lpips=lpips, encoder=False)
+    return Gs, Gm, models.blur_encoder(img_size, start_features, compute_dtype, device, z_space=True), LP
 
 
 def load_models(args, device="cuda", lpips=True):
     """--mtype 1 only: Gs_dict.pth, Gm_dict.pth and center_tensor.pt from the --checkpoint_dir_GAN directory (1.E_align_z.py:21-29)
-    through e_align.load_models, then E_Blur_Z with the optional --checkpoint_dir_E state_dict."""
-    from . import e_align
+    through models.load_models, then E_Blur_Z with the optional --checkpoint_dir_E state_dict."""
     if args.mtype != 1:
         raise ValueError("1.E_align_z trains on StyleGAN1 only (--mtype 1); the reference prints 'error' for any other type")
-    Gs, Gm, _, LP = e_align.load_models(args, device=device, lpips=lpips, encoder=False)
-    from .encoder_variants import BlurBEZ
-    E = BlurBEZ(startf=args.start_features, maxf=512, layer_count=int(math.log2(args.img_size) - 1), latent_size=512,
-                compute_dtype=getattr(args, "compute_dtype", "bf16")).to(device)
+    Gs, Gm, _, LP = models.load_models(args, device=device, lpips=lpips, encoder=False)
+    E = models.blur_encoder(args.img_size, args.start_features, getattr(args, "compute_dtype", "bf16"), device, z_space=True)
     if args.checkpoint_dir_E is not None:
         E.load_state_dict(torch.load(args.checkpoint_dir_E, map_location="cpu"))
     return Gs, Gm, E, LP
@@ -93,13 +79,8 @@ def load_models(args, device="cuda", lpips=True):
 
 def train(tensor_writer=None, args=None):
     """Reference 1.E_align_z.train() (flags :137-149): losses printed every 100 iterations, E_model_ep%d_iter%d.pth every 5000."""
-    import os
-    if getattr(args, "deterministic", False):
-        from . import ops
-        ops.set_deterministic(True)
     Gs, Gm, E, LP = load_models(args)
-    load_lpips_weights(LP, getattr(args, "vgg_weights", None), getattr(args, "lpips_weights", None),
-                       allow_standin=getattr(args, "allow_standin_lpips", False))
+    models.prepare_training(args, LP)
     st = EAlignZStep(Gs, Gm, E, LP, lr=args.lr, beta_1=args.beta_1, batch_size=args.batch_size, z_dim=args.z_dim)
     out_dir = args.experiment_dir
     if out_dir:
@@ -117,25 +98,10 @@ def train(tensor_writer=None, args=None):
 def build_parser():
     import argparse
     parser = argparse.ArgumentParser(description="the training args (ablation 1: Z-space encoder)")
-    parser.add_argument("--iterations", type=int, default=60001)
-    parser.add_argument("--lr", type=float, default=0.0015)
-    parser.add_argument("--beta_1", type=float, default=0.0)
-    parser.add_argument("--batch_size", type=int, default=2)
-    parser.add_argument("--experiment_dir", default=None)
-    parser.add_argument("--checkpoint_dir_GAN", default="../checkpoint/stylegan_v1/ffhq1024/")
-    parser.add_argument("--config_dir", default="./checkpoint/biggan/256/biggan-deep-256-config.json")
-    parser.add_argument("--checkpoint_dir_E", default=None)
-    parser.add_argument("--img_size", type=int, default=1024)
-    parser.add_argument("--img_channels", type=int, default=3)
-    parser.add_argument("--z_dim", type=int, default=512)
-    parser.add_argument("--mtype", type=int, default=1)
-    parser.add_argument("--start_features", type=int, default=16)
-    # not in the reference
-    parser.add_argument("--compute_dtype", default="bf16")
-    parser.add_argument("--vgg_weights", default=None, help="torchvision vgg16 checkpoint (features.*) or an lpips.LPIPS state_dict")
-    parser.add_argument("--lpips_weights", default=None, help="the lpips package's weights/v0.1/vgg.pth (lin{k}.model.1.weight)")
-    parser.add_argument("--deterministic", action="store_true", help="bit-reproducible reductions: ops.set_deterministic")
-    parser.add_argument("--allow_standin_lpips", action="store_true", help="train on seeded stand-in LPIPS weights (NOT the reference objective)")
+    models.add_train_args(parser, iterations=60001)
+    models.add_model_args(parser)
+    parser.set_defaults(mtype=1, checkpoint_dir_GAN="../checkpoint/stylegan_v1/ffhq1024/",
+                        config_dir="./checkpoint/biggan/256/biggan-deep-256-config.json")
     return parser
 
 

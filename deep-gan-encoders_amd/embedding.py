@@ -112,8 +112,8 @@ def invert(st, imgs1, iterations=1500, launch="graph"):
 def build_models(img_size=1024, start_features=16, compute_dtype="bf16", device="cuda", seed=0):
     """Models of BASELINE config 5 (StyleGAN1 FFHQ-1024 synthesis + E_Blur) with seeded random-init weights."""
     from .stylegan1 import Generator
-    from .encoder_variants import BlurBE
     from .lpips import LPIPS
+    from .models import blur_encoder
     torch.manual_seed(seed)
     L = int(math.log2(img_size) - 1)
     Gs = Generator(startf=start_features, maxf=512, layer_count=L, latent_size=512, channels=3, compute_dtype=compute_dtype).to(device)
@@ -123,6 +123,6 @@ def build_models(img_size=1024, start_features=16, compute_dtype="bf16", device=
         for name, p in Gs.named_parameters():
             if "noise_weight" in name:
                 p.fill_(0.05)
-    E = BlurBE(startf=start_features, maxf=512, layer_count=L, compute_dtype=compute_dtype).to(device)
+    E = blur_encoder(img_size, start_features, compute_dtype, device)
     LP = LPIPS(compute_dtype=compute_dtype).to(device)
     return Gs, E, LP

@@ -41,6 +41,7 @@ from . import losses, ops, weight_cache
 from .custom_adam import LREQAdam
 from .embedding import select_launch
 from .graph_step import GraphReplay
+from .models import add_model_args, blur_encoder, load_lpips_weights
 
 # per-generator defaults (embedding_v2_styleGAN1.py:195-209 + :118,128-131; embedding_v2_styleGAN2.py:214-232 + :136,153-166)
 DEFAULTS = {
@@ -338,10 +339,8 @@ def build_models_v2(mtype, img_size=1024, start_features=16, compute_dtype="bf16
                     fmaps_base=None, fmaps_max=None, enc_maxf=None):
     """mtype 1: StyleGAN1 Gs + E_Blur (embedding.build_models); mtype 2: StyleGAN2Generator (eval, frozen, fixed noise) +
     BlurBE(layer_count = log2(res) - 1) - 18 W+ rows at 1024^2, 10 at 64^2.  Seeded random-init weights."""
-    from .encoder_variants import BlurBE
     from .lpips import LPIPS
     torch.manual_seed(seed)
-    L = int(math.log2(img_size) - 1)
     if mtype == 1:
         from .embedding import build_models
         G, E, LP = build_models(img_size, start_features, compute_dtype, device=device, seed=seed)
@@ -354,13 +353,13 @@ def build_models_v2(mtype, img_size=1024, start_features=16, compute_dtype="bf16
     G.eval()
     for p in G.parameters():
         p.requires_grad_(False)
-    E = BlurBE(startf=start_features, maxf=enc_maxf or 512, layer_count=L, compute_dtype=compute_dtype).to(device)
+    E = blur_encoder(img_size, start_features, compute_dtype, device, maxf=enc_maxf or 512)
     LP = LPIPS(compute_dtype=compute_dtype).to(device) if lpips else None
     return G, E, LP
 
 
 def load_checkpoints(G, E, mtype, gan=None, enc=None):
-    """The checkpoint containers of e_align.load_models: mtype 2 a dict holding `generator_smooth` (or `generator`), mtype 1 a
+    """The checkpoint containers of models.load_models: mtype 2 a dict holding `generator_smooth` (or `generator`), mtype 1 a
     directory with Gs_dict.pth; the encoder a bare state_dict."""
     if gan:
         if mtype == 2:
@@ -383,7 +382,6 @@ def strict_bool(s):
 
 
 def make_parser():
-    from .e_align import add_model_args
     p = argparse.ArgumentParser(description="real-image inversion (embedding_v2_styleGAN1.py / embedding_v2_styleGAN2.py)")
     p.add_argument("--iterations", type=int, default=None, help="default: 1501 (mtype 1), 2001 (mtype 2)")
     p.add_argument("--lr", type=float, default=None, help="default 0.005")
@@ -430,7 +428,6 @@ def main(argv=None):
     args = parse_args(argv)
     if args.deterministic:
         ops.set_deterministic(True)
-    from .e_align import load_lpips_weights
     from .infer import save_image_grid
     dev = "cuda"
     G, E, LP = build_models_v2(args.mtype, args.img_size, args.start_features, args.compute_dtype, device=dev, seed=args.seed,

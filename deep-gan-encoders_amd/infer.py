@@ -16,22 +16,23 @@ import torch
 
 from . import ops
 from ._lib import lib, check
+from .generators import set_seed
+from .models import add_model_args, load_models
+from .train_step import TrainStep
 from .ops import _f32, _p, _stream
 
 
 @torch.no_grad()
 def reconstruct(step, z=None, iteration=4, noises=None):
-    """One inversion round trip with the models of an `EAlignStep` (any --mtype): returns dict(imgs1, w1, const2, w2, imgs2).
+    """One inversion round trip with the models of a training step (`TrainStep`, any --mtype): returns dict(imgs1, w1, const2, w2, imgs2).
     `noises`: optional encoder noise tensors (the reference draws them on the CPU, model/E/E.py:60,73 - parity runs inject them)."""
-    from .e_align import set_seed, _BigGANAdapter
     gen, E, B = step.gen, step.E, step.batch_size
-    big = isinstance(gen, _BigGANAdapter)
     if z is None:
         set_seed(iteration)                                   # inferE.py:101-103 (seed 4)
-        z = gen.draw(iteration, B, step.dev) if big else torch.randn(B, step.z_dim)
+        z = gen.draw(iteration, B, step.z_dim)
     z = z.to(step.dev)
     imgs1, w1 = gen.sample(z)
-    const2, w2 = E(imgs1, gen.const1, noises=noises) if big else E(imgs1, noises=noises)
+    const2, w2 = gen.encode(E, imgs1, noises)
     return dict(imgs1=imgs1, w1=w1, const2=const2, w2=w2, imgs2=gen.synth(w2))
 
 
@@ -53,9 +54,8 @@ def load_images(paths, size, bicubic=False, device="cuda"):
 def reconstruct_images(step, imgs1):
     """rec_real_img.py:100-112: real images [N,3,S,S] in [-1,1] -> E -> G, one image at a time as the script does (the
     encoder's instance statistics are per sample, so batching changes nothing but the noise draws).  Returns (w2, imgs2)."""
-    from .e_align import _BigGANAdapter
     gen, E = step.gen, step.E
-    if isinstance(gen, _BigGANAdapter):
+    if gen.conditional:
         raise ValueError("BigGAN needs the class-conditional vector of the image (rec_real_img.py:104); use E(img, cond) directly")
     ws, outs = [], []
     for j in imgs1:
@@ -132,16 +132,15 @@ def save_image_grid(imgs, path, nrow=10):
 
 
 def _step_from_args(args, device="cuda"):
-    from .e_align import EAlignStep, load_models
     G, Gm, E, _ = load_models(args, device=device, lpips=False)
     G.eval()
     E.eval()
-    return EAlignStep(G, E, None, batch_size=args.batch_size, z_dim=args.z_dim, mapping=Gm)
+    return TrainStep(G, E, None, mapping=Gm, batch_size=args.batch_size, z_dim=args.z_dim)
 
 
 def main(argv=None):
     """Entry points of the reference's inference scripts on the HIP path (`python -m dge_amd.infer <command> ...`), every
-    --mtype and its checkpoint container (e_align.load_models):
+    --mtype and its checkpoint container (models.load_models):
 
     * `infer` - inferE.py:101-141: seed 4, z -> G -> E -> G, writes <out>/v2ep<seed>.png (originals over reconstructions);
     * `rec`   - rec_real_img.py:84-127: every image of --img_dir -> E -> G, writes <out>/real/%05d_realimg.png and
@@ -150,7 +149,6 @@ def main(argv=None):
                 writes <out>/id<flag>_%05d.png (nrow 10: originals then reconstructions)."""
     import argparse
     import os
-    from .e_align import add_model_args, set_seed, _BigGANAdapter
     parser = argparse.ArgumentParser(prog="dge_amd.infer", description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument("command", choices=("infer", "rec", "synth"))
     add_model_args(parser)
@@ -186,10 +184,9 @@ def main(argv=None):
             save_image_grid(rec[i:i + 1], b, nrow=1)
             written += [a, b]
     else:
-        big = isinstance(step.gen, _BigGANAdapter)
         for iteration in range(30000, 30000 + args.iterations):
-            r = reconstruct(step, iteration=iteration % 30000 if big else iteration)
-            flag = getattr(step.gen, "flag", 0) if big else 0
+            r = reconstruct(step, iteration=iteration % 30000 if step.gen.conditional else iteration)
+            flag = step.gen.flag
             path = os.path.join(args.out, "id%s_%s.png" % (flag, str(iteration - 30000).rjust(5, "0")))
             save_image_grid(torch.cat((r["imgs1"], r["imgs2"])), path, nrow=10)
             written.append(path)

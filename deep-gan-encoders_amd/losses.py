@@ -8,6 +8,7 @@ import torch
 
 from . import ops
 from ._lib import lib, check
+from .collectives import all_reduce
 from .ops import _f32, _p, _stream
 
 
@@ -20,8 +21,7 @@ class GlobalBatch:
         self.world = world
 
     def reduce(self, t):
-        from .e_align import _all_reduce
-        _all_reduce(t)
+        all_reduce(t)
         return t
 
 

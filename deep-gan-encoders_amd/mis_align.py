@@ -9,9 +9,10 @@ without a gradient tape here.  `loss_c` (:197, logged only) is not produced.
 """
 import torch
 
-from . import losses
-from .e_align import EAlignStep, set_seed, _BigGANAdapter
+from . import losses, ops
+from .e_align import EAlignStep
 from .grad_cam import GradCamPlusPlus, GuidedBackPropagation, mask2cam
+from .train_step import TrainStep
 
 
 class MisAlignStep(EAlignStep):
@@ -23,29 +24,11 @@ class MisAlignStep(EAlignStep):
         self.gbp = GuidedBackPropagation(vgg16)
         self.fused_attention = fused_attention
 
+    _first_pass = TrainStep._first_pass          # the plain head: no prefetched pass, no early weight re-pack
+
     def step(self, iteration, z=None, noises=None, gen_noises=(None, None), new_z=None):
-        E = self.E
-        B = self.batch_size
-        from . import ops
-        from .e_align import _StyleGAN2Adapter
-        if isinstance(self.gen, _StyleGAN2Adapter):
-            self.gen.new_z = new_z
-        ops.zero_arena_begin(self.dev)
-        if z is None or not z.is_cuda:
-            set_seed(iteration % 30000)
-        big = isinstance(self.gen, _BigGANAdapter)
-        if z is None:
-            zg = self.gen.draw(iteration, B * self.world, self.dev) if big else torch.randn(B * self.world, self.z_dim)
-            z = zg[self.rank * B:(self.rank + 1) * B]
-        z = self._upload(z)
+        z, imgs1, w1, const2, w2, imgs2 = self._head(iteration, z, noises, gen_noises, new_z, synth_grad=False)
         with torch.no_grad():
-            imgs1, w1 = self.gen.sample(z, gen_noises[0])
-        if noises is None and self.reference_noise:
-            from .autograd_enc import draw_noises
-            noises = [n.to(self.dev) for n in draw_noises(E, B, imgs1.shape[2], "cpu")]
-        const2, w2 = E(imgs1, self.gen.const1, noises=noises) if big else E(imgs1, noises=noises)
-        with torch.no_grad():
-            imgs2 = self.gen.synth(w2.detach(), gen_noises[1])
             # attention maps (:159-170)
             if self.fused_attention:       # one forward + one backward per batch instead of two of each (same results)
                 mask_1, grad_1 = self.grad_cam_plus_plus.with_input_gradient(imgs1)
@@ -65,7 +48,6 @@ class MisAlignStep(EAlignStep):
             l_cam, info_cam = losses.space_loss(cam_1, cam_2, lpips_model=self.lpips, global_batch=gctx)
             loss_tsa = l_imgs + l_mask + l_cam
         # latent phase (:199-205)
-        gctx = losses.GlobalBatch(self.world) if (self.dist_on and self.exact_ddp) else None
         loss_w, info_w = losses.space_loss(w1, w2, image_space=False, global_batch=gctx)
         loss_mtv = loss_w * 0.01
         self.opt.zero_grad()

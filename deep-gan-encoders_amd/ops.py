@@ -86,7 +86,7 @@ def _sum_over_batch(partial, out=None):
 
 # ------------------------------------------------------------------ counter-based noise (dge_randn)
 class _Noise:
-    """State of the step's noise draws: `seed` (set by e_align.set_seed next to torch / numpy), a draw counter that names the
+    """State of the step's noise draws: `seed` (set by generators.set_seed next to torch / numpy), a draw counter that names the
     Philox subsequence of each tensor, and the data-parallel position (rank, world): a draw of per-sample rows [B, ...] is the
     rank's slice of the global-batch tensor [world*B, ...], so N ranks x B reproduce one process at batch N*B exactly."""
 

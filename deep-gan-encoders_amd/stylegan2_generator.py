@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .collectives import all_reduce
 from .weight_cache import lookup, store
 
 __all__ = ["StyleGAN2Generator"]
@@ -329,8 +330,7 @@ class StyleGAN2Generator(nn.Module):
                 import torch.distributed as dist
                 if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
                     # the upstream code all_gather'ed w here (reference :178, commented out): global batch mean
-                    from .e_align import _all_reduce
-                    _all_reduce(batch_w_avg)
+                    all_reduce(batch_w_avg)
                     batch_w_avg = batch_w_avg / dist.get_world_size()
                 self.truncation.w_avg.copy_(self.truncation.w_avg * w_moving_decay + batch_w_avg * (1 - w_moving_decay))
             if self.training and style_mixing_prob > 0:

@@ -1,5 +1,5 @@
 """world_size-2 (gloo, CPU) test of the data-parallel host logic: the globally-reduced loss sums
-(exact cosine / means) and the flat-bucket gradient all-reduce used by EAlignStep."""
+(exact cosine / means) and the flat-bucket gradient all-reduce used by EAlignStep (collectives.GradBucket)."""
 import os
 import socket
 import sys
@@ -22,7 +22,7 @@ def _worker(rank, world, port, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     import dge_amd  # noqa
     from dge_amd.losses import GlobalBatch
-    from dge_amd.e_align import EAlignStep
+    from dge_amd.collectives import GradBucket
     from oracle import ref_torch as O
     torch.manual_seed(0)
     # --- global batch of 4 latents, each rank owns 2 rows: exact cosine needs the global sums
@@ -35,33 +35,31 @@ def _worker(rank, world, port, q):
     ref, _ = O.space_loss(a, b, image_space=False)
     ok1 = abs(float(loss_global) - float(ref)) < 1e-5 * abs(float(ref))
 
-    # --- flat-bucket gradient exchange of EAlignStep (sum over ranks, views installed as .grad)
+    # --- flat-bucket gradient exchange (sum over ranks, views installed as .grad)
     lin = torch.nn.Linear(5, 3)
     with torch.no_grad():
         for p in lin.parameters():
             p.fill_(0.5)
-    st = EAlignStep.__new__(EAlignStep)
-    st.E, st.world, st.rank, st.exact_ddp, st.dev, st._flat, st.dist_on = lin, world, rank, True, torch.device("cpu"), None, True
+    st = GradBucket(lin, torch.device("cpu"), exact=True)
     for p in lin.parameters():
         p.grad = torch.full_like(p, float(rank + 1))
-    gs = st._sync_grads()
+    gs = st.sync()
     ok2 = gs is None and all(torch.allclose(p.grad, torch.full_like(p, 3.0)) for p in lin.parameters())
-    st.exact_ddp = False
+    st.exact = False
     for p in lin.parameters():
         p.grad = torch.full_like(p, float(rank + 1))
-    gs = st._sync_grads()
+    gs = st.sync()
     ok3 = abs(float(gs) - 0.5) < 1e-7
-    # --- early bucket: part of the gradients is reduced asynchronously from inside the backward, the rest in _sync_grads
-    st2 = EAlignStep.__new__(EAlignStep)
+    # --- early bucket: part of the gradients is reduced asynchronously from inside the backward, the rest in sync()
     net = torch.nn.Sequential(torch.nn.Linear(5, 3), torch.nn.Linear(3, 2))
-    st2.E, st2.world, st2.rank, st2.exact_ddp, st2.dev, st2._flat, st2.dist_on = net, world, rank, True, torch.device("cpu"), None, True
+    st2 = GradBucket(net, torch.device("cpu"), exact=True)
     ok5 = True
     for phase in range(2):                                   # two phases per step re-use the layout
         for i_, p in enumerate(net.parameters()):
             p.grad = torch.full_like(p, float((rank + 1) * (i_ + 1) + phase))
         early = {n: p.grad.clone() for n, p in net.named_parameters() if n.startswith("1.")}
         st2.early_reduce(early)
-        st2._sync_grads()
+        st2.sync()
         for i_, p in enumerate(net.parameters()):
             want = float(sum((r + 1) * (i_ + 1) + phase for r in range(world)))
             ok5 = ok5 and torch.allclose(p.grad, torch.full_like(p, want)) and p.grad.data_ptr() >= st2._flat.data_ptr()

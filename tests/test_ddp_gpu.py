@@ -1,7 +1,7 @@
 """Two data-parallel ranks x B images == one process at batch 2B, for the REAL two-phase step (the couplings the
 reference has across a batch: training_utils.py:73-75 batch-flattened cosine, stylegan2_generator.py:177-191 w_avg EMA and
 style mixing, E.py:60,73 per-sample noise).  Two processes share the one GPU of the box, torch.distributed over gloo (device
-tensors staged through the host by e_align._all_reduce; RCCL refuses two ranks on one device), every collective of the step is
+tensors staged through the host by collectives.all_reduce; RCCL refuses two ranks on one device), every collective of the step is
 real: w_avg mean, the packed loss sums, early + remainder gradient buckets in both phases."""
 import os
 import socket

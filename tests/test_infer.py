@@ -172,7 +172,7 @@ def _args(**kw):
 def test_load_models_reads_the_three_checkpoint_containers(tmp_path):
     """E_align_s2.py:30-35 (mtype 1: directory with Gs_dict.pth / Gm_dict.pth / center_tensor.pt), :51-55 (mtype 2 / 3: dict
     with `generator_smooth`, falling back to `generator`), bare encoder state_dict: written, read back through
-    e_align.load_models on the host (map_location='cpu'), parameters identical."""
+    models.load_models on the host (map_location='cpu'), parameters identical."""
     from dge_amd.e_align import load_models, build_models, build_models_sg1, build_models_pg
     # mtype 2
     G, E, _ = build_models(64, 16, "f32", device="cpu", lpips=False, seed=3, fmaps_base=2048, fmaps_max=128, enc_maxf=64)

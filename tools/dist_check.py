@@ -17,7 +17,7 @@ for force in ("1", "0", "0"):
     for it in range(3):
         r = st.step(it)
     if force == "1":
-        assert st._layout["n_early"] > 0.8 * st._flat.numel(), (st._layout["n_early"], st._flat.numel())
+        assert st.bucket._layout["n_early"] > 0.8 * st.bucket._flat.numel(), (st.bucket._layout["n_early"], st.bucket._flat.numel())
     res.append(({k: v.detach().clone() for k, v in E.state_dict().items()}, float(r["loss_tsa"]), float(r["loss_w"])))
 d = max(float((res[0][0][k] - res[1][0][k]).abs().max()) for k in res[0][0])
 d2 = max(float((res[1][0][k] - res[2][0][k]).abs().max()) for k in res[0][0])
