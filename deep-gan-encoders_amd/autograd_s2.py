@@ -2,27 +2,11 @@
 model/stylegan2_generator.py:492-539) and the hand-written data-gradient w.r.t. wp that the
 encoder training needs (E_align_s2.py:160,204).  G's own parameters never receive gradients
 here: the reference computes and discards them, results for E are identical."""
-import math
-
 import torch
 
-from . import ops
+from . import ops, s2_conv
 from .stylegan2_generator import _dt
-from .weight_cache import lookup, store, version
-
-
-def _layer_fwd(L, x, w_row, randomize_noise):
-    dt = ops.dtype_of(x)
-    packed, wsq = L._prepared(dt)
-    s = L.style(w_row)
-    d = ops.linear(s, wsq, None, 1.0, 1.0, L.eps, ops.LIN_RSQRT, 1.0, square_input=True)
-    if randomize_noise:
-        noise = ops.randn((x.shape[0], L.res, L.res), x.device)
-    else:
-        noise = L.noise.reshape(1, L.res, L.res)
-    y = ops.conv2d(x, packed, L.out_c, 3, up=L.up, in_scale=s, out_scale=d, bias=L.bias, bias_scale=L.bscale,
-                   noise=noise, noise_w=L.noise_strength.detach().reshape(1), act=L.act, gain=L.gain)
-    return y, s, d, noise
+from .weight_cache import version
 
 
 def _style_tables(mod, B, dt):
@@ -126,46 +110,6 @@ def synthesis_run(mod, wp, randomize_noise=False, save=False):
     return results, saved
 
 
-def _up_phase_form(L):
-    """Up layers whose data gradient runs in phase form (FIR^T pass + 4-tap conv on the t grid, dge_fir_t2d / in_t2d: 16 tap-units
-    per input pixel instead of the 36 of the folded space-to-depth form): the MFMA-bound ones, 32^2 .. 128^2 input (measured at
-    batch 8, tools/perf_t2d.py, folded -> FIR pass + conv: 512->512 @32^2 221 -> 174 us, 256<-512 @64^2 310 -> 243, 128<-256 @128^2
-    344 -> 313; at 256^2 / 512^2 the launch is bound by its epilogue and the extra pass loses: 430 -> 504, 951 -> 1223).  The small
-    grids stay on the folded form (low-resolution kernel)."""
-    import os
-    return L.up and 32 <= L.res // 2 <= 128 and L.in_c >= 64 and L.in_c % 32 == 0 and L.out_c % 8 == 0 and not os.environ.get("DGE_NO_T2D")
-
-
-def _dgrad_weight(L, dtype):
-    hg = L.res // 2 if L.up else L.res          # grid the data-gradient conv runs on (space-to-depth grid for the up layers)
-    if _up_phase_form(L):
-        mode = ops.PACK_UPT2D_DGRAD
-    else:
-        mode = ops.pack_mode_for(L.weight, ops.PACK_UPFOLD_DGRAD if L.up else ops.PACK_DGRAD, hg, hg, dtype)
-    c = lookup(L._cache, ("dg", dtype, mode), L.weight)
-    return c if c is not None else store(L._cache, ("dg", dtype, mode), L.weight, ops.pack_conv_weight(L.weight, mode, dtype, L.wscale))
-
-
-def _pp_dgrad(L, B, hg, dtype):
-    """the data gradient of this layer runs on conv_pp (GEMM K = out channels, x 4 phases for the folded up layer; N = in channels)"""
-    import os
-    K = 4 * L.out_c if L.up else L.out_c
-    return (not L.up or L.out_c % 32 == 0) and ops.conv_pp_supported(B, hg, hg, K, L.in_c, dtype) and not os.environ.get("DGE_NO_PP_DG")
-
-
-def _dgrad_weight_pp(L, d, t2d=False):
-    """data-gradient weight image of conv_pp.  Stride 1 / folded up layer: per sample, W'[b] = bf16(w * wscale * d[b, o]) (the up layer
-    through its folded f32 rows, packed once per weight version); phase form: one shared 4-tap image, cached per weight version"""
-    if not L.up:
-        return ops.pack_conv_pp(L.weight, L.wscale, in_scale=d, dgrad=True)
-    name = "dgpp_t2d" if t2d else "dgpp"
-    c = lookup(L._cache, name, L.weight)
-    if c is None:
-        rows = ops.pack_conv_weight(L.weight, ops.PACK_UPT2D_DGRAD if t2d else ops.PACK_UPFOLD_DGRAD, ops.F32, L.wscale)
-        c = store(L._cache, name, L.weight, ops.pack_conv_pp_rows(rows, L.in_c, t2d=True) if t2d else rows)
-    return c if t2d else ops.pack_conv_pp_rows(c, L.in_c, in_scale=d, in_period=L.out_c)
-
-
 def synthesis_backward(mod, wp, saved, g_image):
     """d(image)/d(wp) contracted with g_image [B,3,R,R] -> g_wp [B,num_layers,512].
 
@@ -224,29 +168,11 @@ def synthesis_backward(mod, wp, saved, g_image):
                 g_img = ops.up2_bwd(g_img)
         st = ops.SlotStats(B, L.in_c, dev) if fused else ops.zeros((B, L.in_c, 2), dev)
         prep, P_next = None, None
-        # (the space-to-depth data gradient of a narrow up layer - layer 15: 64 -> 32 channels - loses more in its 64-wide tile
-        #  than the separate pass costs: measured 890 vs 747 us; tools/perf_prep.py)
-        t2d = _up_phase_form(L)
-        if fused and i >= 1 and (t2d or not (L.up and L.in_c < 128)):
+        if fused and i >= 1 and s2_conv.dgrad_takes_prep(L):
             Lp = getattr(mod, f"layer{i - 1}")
             P_next = ops.SlotStats(B, L.in_c, dev)
             prep = dict(gain=Lp.gain, noise=layers[i - 1]["noise"], ns=Lp.noise_strength.detach().reshape(1), stats=P_next)
-        hg = L.res // 2 if L.up else L.res
-        if fused and d_in is not None and not t2d and _pp_dgrad(L, B, hg, dt):
-            # MFMA-bound launches on the ping-pong kernel (csrc/conv_pp.hip): the demodulation factor is folded into a per-sample
-            # weight image instead of scaling g_z in a prologue
-            g_xprev = ops.conv_pp(g_y, _dgrad_weight_pp(L, d_in), L.in_c, dgrad=True, in_s2d=L.up, out_scale=rec["s"], addend=addend,
-                                  add_scale=1.0, stats=st, dot_src=x_in, prep=prep)
-        elif t2d and fused and prep is not None and _pp_dgrad(L, B, hg, dt):
-            # phase form on the ping-pong kernel: the same FIR^T pass, then the 4-tap conv with ONE shared weight image
-            g_xprev = ops.conv_pp(ops.fir_t2d(g_y, d_in), _dgrad_weight_pp(L, None, t2d=True), L.in_c, dgrad=True, in_t2d=True, out_scale=rec["s"],
-                                  addend=addend, add_scale=1.0, stats=st, dot_src=x_in, prep=prep)
-        elif t2d:      # phase form: FIR^T (times the demodulation factor) to the t grid, then the 4-tap conv
-            g_xprev = ops.conv2d(ops.fir_t2d(g_y, d_in), _dgrad_weight(L, dt), L.in_c, 3, in_t2d=True, out_scale=rec["s"], addend=addend,
-                                 add_scale=1.0, stats=st, dot_src=x_in, prep=prep)
-        else:
-            g_xprev = ops.conv2d(g_y, _dgrad_weight(L, dt), L.in_c, 3, in_s2d=L.up, in_scale=d_in, out_scale=rec["s"], addend=addend,
-                                 add_scale=1.0, stats=st, dot_src=x_in, prep=prep)
+        g_xprev = s2_conv.dgrad(L, g_y, d_in, dt, fused, prep=prep, out_scale=rec["s"], addend=addend, stats=st, dot_src=x_in)
         # ---- style / demodulation gradients -> g_wp[:, i]
         _, wsq = L._prepared(dt)
         if fused and P is not None:

@@ -232,9 +232,7 @@ def _bwd_split(a, b, wins, sums, gps, ks, ns, wts, outs):
     wflat = (C.c_int * (4 * nw))(*[int(v) for win in wins for v in win])
     check(lib().dge_space_loss_bwd_split(_f32(a), _f32(b), ptrs(sums), ptrs(gps), ptrs(outs), B * Cc, H, W, wflat, (C.c_int * nw)(*ks),
                                          (C.c_float * nw)(*ns), (C.c_float * nw)(*wts), nw, _stream()), "dge_space_loss_bwd_split")
-    if ops.KERNEL_LOG is not None:
-        from ._lib import last_kernel
-        ops.KERNEL_LOG.append((last_kernel(), _stream()))
+    ops.log_kernel()
 
 
 def _space_loss_windows_split(a, b, wins, lpips_model, weights, g_split, gb=None):

@@ -13,7 +13,6 @@ PACK_FWD, PACK_UPFOLD, PACK_DGRAD, PACK_UPFOLD_DGRAD, PACK_SG1_UP, PACK_SG1_UP_D
 PACK_FRAG = 0x100     # OR-ed into a pack mode: MFMA-fragment order for the low-resolution kernel (csrc/conv_small.hip)
 import os as _os
 import weakref as _weakref
-_PF = {"on": not _os.environ.get("DGE_NO_PREFETCH"), "prev": {}, "next": {}}     # low-resolution weight prefetch chain (conv2d)
 KERNEL_LOG = None   # tests set this to a list: (kernel instantiation name, stream handle) per conv_pp / up_pp launch (which streams ran them)
 PROFILE = None      # bench.py sets this to a list: (start_event, stop_event, algorithmic_flops, tag, algorithmic_bytes) per conv launch
 
@@ -362,6 +361,90 @@ def truncation(w, w_avg, num_layers, psi, layers):
     return wp
 
 
+def log_kernel():
+    """KERNEL_LOG hook: records (name of the kernel the library launched last, current stream handle)"""
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append((last_kernel(), _stream()))
+
+
+def _launch(fn, args, name, macs, tag, tensors, wbytes=0, log=False):
+    """The one launch path of the conv family (dge_conv2d, dge_conv_pp, dge_up_pp, dge_upconv_fir): check(fn(*args)), timed by an
+    event pair when PROFILE is a list - the entry is (start, stop, algorithmic flops = 2 * macs, tag, algorithmic bytes = every tensor
+    of `tensors` crossing HBM once, + wbytes for weights counted by formula) - and named in KERNEL_LOG when `log`."""
+    if PROFILE is None:
+        check(fn(*args), name)
+    else:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        check(fn(*args), name)
+        e1.record()
+        PROFILE.append((e0, e1, 2.0 * macs, tag, sum(t.numel() * t.element_size() for t in tensors if t is not None) + wbytes))
+    if log and KERNEL_LOG is not None:
+        log_kernel()
+
+
+def _stats_slots(B, H, W, tile_w):
+    """Copies that the statistics atomics of a launch on an H x W grid are spread over (same-address contention): one per 16 tiles
+    of 16 x tile_w pixels - the kernel's tile: 16 wide for dge_conv2d, 32 for dge_conv_pp - and 64 at the most."""
+    return max(1, min(64, ((H + 15) // 16) * ((W + tile_w - 1) // tile_w) * B // 16))
+
+
+def _mask_as_dot_src(name, relu_mask, dot_src, prep):
+    """the stored activation of `relu_mask` reaches the kernel in the dot_src operand, so it excludes dot_src and prep"""
+    if relu_mask is not None and (dot_src is not None or prep is not None):
+        raise DgeError(f"{name}: relu_mask excludes dot_src / prep")
+    return dot_src if relu_mask is None else relu_mask
+
+
+def _set_prep(d, prep, nslot):
+    """the `prep` dict of conv2d / conv_pp -> the prep_* fields that dge_conv_desc and dge_conv_pp_desc share"""
+    pn = prep.get("noise")
+    d.prep, d.prep_gain = 1, float(prep["gain"])
+    d.prep_noise, d.prep_ns = _f32(pn), _f32(prep.get("ns") if pn is not None else None)
+    d.prep_noise_batch = 1 if pn is None else pn.shape[0]
+    d.prep_stats = _f32(prep["stats"].alloc(nslot))
+
+
+def _weight_images(in_scale, out_scale):
+    """number of weight images a pack_* call writes: one shared copy, or the batch of the per-sample scales (the last one given)"""
+    t = in_scale if out_scale is None else out_scale
+    return 1 if t is None else t.shape[0]
+
+
+class _PrefetchChain:
+    """L2 warm-up hint for the low-resolution kernel: the launch warms the weights of the low-resolution launch that followed it
+    the LAST time it ran (a step repeats its launch sequence; packed copies keep their addresses) - dge_conv_desc.prefetch_w
+    The chain is keyed by (stream, address): launches of different streams (the three loss windows) do not follow each other.
+    An entry holds a WEAK reference to the packed tensor it points at: a re-allocated copy (load_state_dict, a new model) makes
+    the entry stale and it is dropped instead of warming freed memory; the table is bounded."""
+
+    def __init__(self, on=True):
+        self.on, self.prev, self.next = on, {}, {}       # prev: stream -> address; next: (stream, address) -> (next address, ntot, cin, weakref)
+
+    def link(self, stream, w_packed):
+        """Records that `w_packed` follows the stream's previous launch; returns (ptr, ntot, cin) of what followed it last time, or None."""
+        if not self.on:
+            return None
+        key = w_packed.data_ptr()
+        prev = self.prev.get(stream)
+        if prev is not None and prev != key:
+            if len(self.next) > 512:
+                self.next.clear()
+            self.next[(stream, prev)] = (key, w_packed.shape[1], w_packed.shape[2], _weakref.ref(w_packed))
+        self.prev[stream] = key
+        nxt = self.next.get((stream, key))
+        if nxt is None:
+            return None
+        t = nxt[3]()
+        if t is None or t.data_ptr() != nxt[0]:
+            del self.next[(stream, key)]
+            return None
+        return nxt[:3]
+
+
+_PREFETCH = _PrefetchChain(on=not _os.environ.get("DGE_NO_PREFETCH"))
+
+
 def conv2d(x, w_packed, cout, ksize=3, up=False, in_scale=None, in_shift=None, out_scale=None, bias=None,
            bias_scale=1.0, noise=None, noise_w=None, act=ACT_NONE, gain=1.0, addend=None, add_scale=1.0, stats=None,
            out=None, in_s2d=False, dot_src=None, in_up2=False, in_relu=False, prep=None, relu_mask=None, in_t2d=False, rgb=None, pool_out=False, pool_mask=False,
@@ -398,10 +481,7 @@ def conv2d(x, w_packed, cout, ksize=3, up=False, in_scale=None, in_shift=None, o
         out = torch.empty((B, OH, OW, cout), dtype=x.dtype, device=x.device)
     d = ConvDesc()
     d.pool_out, d.pool_mask = 1 if pool_out else 0, _p(mask)
-    if relu_mask is not None:
-        if dot_src is not None or prep is not None:
-            raise DgeError("conv2d: relu_mask excludes dot_src / prep")
-        dot_src = relu_mask
+    dot_src = _mask_as_dot_src("conv2d", relu_mask, dot_src, prep)
     d.mask_relu = 0 if relu_mask is None else 1
     d.in_t2d = 1 if in_t2d else 0
     d.x, d.w_packed, d.y, d.addend, d.dot_src = _p(x), _p(w_packed), _p(out), _p(addend), _p(dot_src)
@@ -410,8 +490,7 @@ def conv2d(x, w_packed, cout, ksize=3, up=False, in_scale=None, in_shift=None, o
     partial, nslot = None, 1
     lazy = isinstance(stats, SlotStats)
     if stats is not None:
-        nblk = ((H + 15) // 16) * ((W + 15) // 16) * B
-        nslot = max(1, min(64, nblk // 16))
+        nslot = _stats_slots(B, H, W, 16)
         if lazy:
             partial = stats.alloc(nslot)
         elif nslot > 1:
@@ -422,42 +501,18 @@ def conv2d(x, w_packed, cout, ksize=3, up=False, in_scale=None, in_shift=None, o
     d.ksize, d.up, d.in_s2d, d.in_up2 = ksize, 1 if up else 0, 1 if in_s2d else 0, 1 if in_up2 else 0
     d.in_relu = 1 if in_relu else 0
     d.w_layout = 1 if getattr(w_packed, "_dge_frag", False) else 0
-    if d.w_layout and _PF["on"]:
-        # L2 warm-up hint for the low-resolution kernel: the launch warms the weights of the low-resolution launch that followed it
-        # the LAST time it ran (a step repeats its launch sequence; packed copies keep their addresses) - dge_conv_desc.prefetch_w
-        # The chain is keyed by (stream, address): launches of different streams (the three loss windows) do not follow each other.
-        # An entry holds a WEAK reference to the packed tensor it points at: a re-allocated copy (load_state_dict, a new model) makes
-        # the entry stale and it is dropped instead of warming freed memory; the table is bounded.
-        sk = (_stream().value or 0)
-        key = w_packed.data_ptr()
-        prev = _PF["prev"].get(sk) if isinstance(_PF["prev"], dict) else None
-        if not isinstance(_PF["prev"], dict):
-            _PF["prev"] = {}
-        if prev is not None and prev != key:
-            if len(_PF["next"]) > 512:
-                _PF["next"].clear()
-            _PF["next"][(sk, prev)] = (key, w_packed.shape[1], w_packed.shape[2], _weakref.ref(w_packed))
-        _PF["prev"][sk] = key
-        nxt = _PF["next"].get((sk, key))
+    if d.w_layout:
+        nxt = _PREFETCH.link(_stream().value or 0, w_packed)
         if nxt is not None:
-            t = nxt[3]()
-            if t is None or t.data_ptr() != nxt[0]:
-                del _PF["next"][(sk, key)]
-            else:
-                d.prefetch_w, d.prefetch_ntot, d.prefetch_cin = C.c_void_p(nxt[0]), int(nxt[1]), int(nxt[2])
+            d.prefetch_w, d.prefetch_ntot, d.prefetch_cin = C.c_void_p(nxt[0]), int(nxt[1]), int(nxt[2])
     if prep is not None:
         if stats is None or dot_src is None:
             raise DgeError("conv2d: prep needs stats and dot_src")
-        pn = prep.get("noise")
-        d.prep, d.prep_gain = 1, float(prep["gain"])
-        d.prep_noise, d.prep_ns = _f32(pn), _f32(prep.get("ns") if pn is not None else None)
-        d.prep_noise_batch = 1 if pn is None else pn.shape[0]
-        d.prep_stats = _f32(prep["stats"].alloc(nslot))
+        _set_prep(d, prep, nslot)
     if in_bwd is not None:
         if dot_src is None or stats is not None or prep is not None:
             raise DgeError("conv2d: in_bwd needs dot_src and excludes stats / prep")
-        nblk = ((H + 15) // 16) * ((W + 15) // 16) * B
-        d.stats_slots = max(1, min(64, nblk // 16))
+        d.stats_slots = _stats_slots(B, H, W, 16)
         pn = in_bwd.get("noise")
         d.in_bwd_coef = _f32(in_bwd["coef"])
         d.prep_noise, d.prep_noise_batch = _f32(pn), 1 if pn is None else pn.shape[0]
@@ -478,29 +533,16 @@ def conv2d(x, w_packed, cout, ksize=3, up=False, in_scale=None, in_shift=None, o
     d.act, d.bias_scale, d.gain, d.add_scale, d.dtype = act, bias_scale, gain, add_scale, dt
     if w_packed.dtype != x.dtype:
         raise DgeError("conv2d: packed weight dtype differs from activation dtype")
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib().dge_conv2d(C.byref(d), _stream()), "dge_conv2d")
-        e1.record()
-        # algorithmic work: a folded up layer / its adjoint count as the 3x3 transposed conv they replace
-        # (9*Cin*Cout MACs per INPUT pixel), everything else k*k*Cin*Cout per output pixel
-        if up:
-            macs = 9.0 * Cin * cout * H * W
-        elif in_s2d or in_t2d:
-            macs = 9.0 * (Cin // 4) * cout * H * W
-        else:
-            macs = float(ksize * ksize) * Cin * cout * H * W
-        # algorithmic bytes: every operand tensor crosses HBM once (input, output, optional addend / dot_src, packed weights)
-        skip_y = rgb is not None and rgb.get("skip_y")
-        abytes = sum(t.numel() * t.element_size() for t in (x, None if skip_y else out, addend, dot_src, w_packed,
-                                                            rgb["out"] if rgb is not None else None) if t is not None)
-        PROFILE.append((e0, e1, 2.0 * macs * B, (B, H, W, Cin, cout, ksize, up, in_s2d), abytes))
-    else:
-        check(lib().dge_conv2d(C.byref(d), _stream()), "dge_conv2d")
+    # algorithmic work: a folded up layer / its adjoint count as the 3x3 transposed conv they replace
+    # (9*Cin*Cout MACs per INPUT pixel), everything else k*k*Cin*Cout per output pixel
+    taps_cin = 9.0 * Cin if up else 9.0 * (Cin // 4) if (in_s2d or in_t2d) else float(ksize * ksize) * Cin
+    # algorithmic bytes: every operand tensor crosses HBM once (input, output, optional addend / dot_src, packed weights)
+    skip_y = rgb is not None and rgb.get("skip_y")
+    _launch(lib().dge_conv2d, (C.byref(d), _stream()), "dge_conv2d", taps_cin * cout * H * W * B, (B, H, W, Cin, cout, ksize, up, in_s2d),
+            (x, None if skip_y else out, addend, dot_src, w_packed, rgb["out"] if rgb is not None else None))
     if partial is not None and not lazy:
         check(lib().dge_sum_slots(_p(partial), _p(stats), nslot, stats.numel(), 1, _stream()), "dge_sum_slots")
-    if rgb is not None and rgb.get("skip_y"):
+    if skip_y:
         return None
     if pool_out and pool_mask:
         return out, mask
@@ -530,10 +572,7 @@ def pack_up_pp(w_units, cout, cin, in_scale=None, out_scale=None, gain=1.0, out=
     out_scale [B, Cout] - B copies with style, demodulation and gain folded in (stylegan2_generator.py:858-875).  [nb, 9*Cin*Cout] bf16."""
     if w_units.dtype != torch.bfloat16:
         raise DgeError("pack_up_pp: expects the bf16 units of pack_upconv_weight")
-    nb = 1
-    for t in (in_scale, out_scale):
-        if t is not None:
-            nb = t.shape[0]
+    nb = _weight_images(in_scale, out_scale)
     if out is None:
         out = torch.empty((nb, 9 * cin * cout), dtype=torch.bfloat16, device=w_units.device)
     check(lib().dge_pack_up_pp(_p(w_units), _p(out), int(cout), int(cin), _f32(in_scale), _f32(out_scale), float(gain), nb, _stream()),
@@ -553,18 +592,9 @@ def up_pp(x, w_img, cout, bias=None, bias_scale=1.0, noise=None, noise_w=None, a
         raise DgeError("up_pp: one noise strength per layer (stylegan2_generator.py:911-916)")
     wbs = 0 if w_img.shape[0] == 1 else w_img.stride(0)
 
-    def launch():
-        check(lib().dge_up_pp(_p(x), _p(w_img), int(wbs), _p(y), _f32(noise), nbs, _f32(noise_w), _f32(bias), float(bias_scale),
-                              float(gain), int(act), B, H, W, Cin, int(cout), _stream()), "dge_up_pp")
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); launch(); e1.record()
-        abytes = sum(t.numel() * t.element_size() for t in (x, y)) + 18 * Cin * cout * B
-        PROFILE.append((e0, e1, 2.0 * 9.0 * Cin * cout * H * W * B, (B, H, W, Cin, cout, 3, "upfir", False), abytes))
-    else:
-        launch()
-    if KERNEL_LOG is not None:
-        KERNEL_LOG.append((last_kernel(), _stream()))
+    _launch(lib().dge_up_pp, (_p(x), _p(w_img), int(wbs), _p(y), _f32(noise), nbs, _f32(noise_w), _f32(bias), float(bias_scale),
+                              float(gain), int(act), B, H, W, Cin, int(cout), _stream()), "dge_up_pp",
+            9.0 * Cin * cout * H * W * B, (B, H, W, Cin, cout, 3, "upfir", False), (x, y), wbytes=18 * Cin * cout * B, log=True)
     return y
 
 
@@ -579,10 +609,7 @@ def pack_conv_pp(w, wscale=1.0, in_scale=None, out_scale=None, gain=1.0, dgrad=F
     data gradient reads ((n, k) = (in, out) channel, taps flipped).  Returns a [nb, 9*N*K] bf16 tensor."""
     cout, cin = w.shape[0], w.shape[1]
     N, K = (cin, cout) if dgrad else (cout, cin)
-    nb = 1
-    for t in (in_scale, out_scale):
-        if t is not None:
-            nb = t.shape[0]
+    nb = _weight_images(in_scale, out_scale)
     if out is None:
         out = torch.empty((nb, 9 * N * K), dtype=torch.bfloat16, device=w.device)
     check(lib().dge_pack_conv_pp(_f32(w.detach().contiguous()), _p(out), N, K, float(wscale), _f32(in_scale), _f32(out_scale), float(gain),
@@ -596,10 +623,7 @@ def pack_conv_pp_rows(w_rows, N, in_scale=None, in_period=None, out_scale=None, 
     if w_rows.dtype != torch.float32 or w_rows.ndim != 3 or w_rows.shape[0] != 9:
         raise DgeError("pack_conv_pp_rows: expects an f32 [9, Npad, K] packed weight")
     K = w_rows.shape[2]
-    nb = 1
-    for t in (in_scale, out_scale):
-        if t is not None:
-            nb = t.shape[0]
+    nb = _weight_images(in_scale, out_scale)
     if out is None:
         out = torch.empty((nb, (4 if t2d else 9) * N * K), dtype=torch.bfloat16, device=w_rows.device)
     per = K if in_period is None else int(in_period)
@@ -632,13 +656,10 @@ def conv_pp(x, w_pp, cout, out_scale=None, bias=None, bias_scale=1.0, noise=None
     d.noise_w_per_channel = 0 if (noise_w is None or noise_w.numel() == 1) else 1
     d.act, d.bias_scale, d.gain = act, bias_scale, gain
     if dgrad:
-        if relu_mask is not None:
-            if dot_src is not None or prep is not None:
-                raise DgeError("conv_pp: relu_mask excludes dot_src / prep")
-            dot_src = relu_mask
+        dot_src = _mask_as_dot_src("conv_pp", relu_mask, dot_src, prep)
         d.dgrad, d.in_s2d, d.in_t2d, d.mask_relu = 1, 1 if in_s2d else 0, 1 if in_t2d else 0, 0 if relu_mask is None else 1
         d.dot_src, d.addend, d.add_scale = _p(dot_src), _p(addend), float(add_scale)
-        nslot = max(1, min(64, (((H + 15) // 16) * ((W + 31) // 32) * B) // 16))
+        nslot = _stats_slots(B, H, W, 32)
         if stats is not None:
             d.stats = _f32(stats.alloc(nslot) if isinstance(stats, SlotStats) else stats)
             if not isinstance(stats, SlotStats):
@@ -647,25 +668,12 @@ def conv_pp(x, w_pp, cout, out_scale=None, bias=None, bias_scale=1.0, noise=None
         if prep is not None:
             if dot_src is None:
                 raise DgeError("conv_pp: prep needs dot_src")
-            pn = prep.get("noise")
-            d.prep, d.prep_gain = 1, float(prep["gain"])
-            d.prep_noise, d.prep_ns = _f32(pn), _f32(prep.get("ns") if pn is not None else None)
-            d.prep_noise_batch = 1 if pn is None else pn.shape[0]
-            d.prep_stats = _f32(prep["stats"].alloc(nslot))
+            _set_prep(d, prep, nslot)
     elif in_s2d or in_t2d or dot_src is not None or addend is not None or stats is not None or prep is not None or relu_mask is not None:
         raise DgeError("conv_pp: in_s2d / dot_src / addend / stats / prep / relu_mask need dgrad=True")
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(lib().dge_conv_pp(C.byref(d), _stream()), "dge_conv_pp")
-        e1.record()
-        abytes = sum(t.numel() * t.element_size() for t in (x, out, w_pp, dot_src, addend) if t is not None)
-        macs = 9.0 * (Cin // 4 if (in_s2d or in_t2d) else Cin) * cout * H * W         # (an up layer's adjoint counts as the 3x3 transposed conv it replaces)
-        PROFILE.append((e0, e1, 2.0 * macs * B, (B, H, W, Cin, cout, 3, False, bool(in_s2d or in_t2d)), abytes))
-    else:
-        check(lib().dge_conv_pp(C.byref(d), _stream()), "dge_conv_pp")
-    if KERNEL_LOG is not None:
-        KERNEL_LOG.append((last_kernel(), _stream()))
+    macs = 9.0 * (Cin // 4 if (in_s2d or in_t2d) else Cin) * cout * H * W         # (an up layer's adjoint counts as the 3x3 transposed conv it replaces)
+    _launch(lib().dge_conv_pp, (C.byref(d), _stream()), "dge_conv_pp", macs * B, (B, H, W, Cin, cout, 3, False, bool(in_s2d or in_t2d)),
+            (x, out, w_pp, dot_src, addend), log=True)
     return out
 
 
@@ -1246,17 +1254,9 @@ def upconv_fir(x, w_packed, cout, in_scale=None, out_scale=None, bias=None, bias
     y = torch.empty((B, 2 * H, 2 * W, cout), dtype=x.dtype, device=x.device)
     nbs = 0 if (noise is None or noise.shape[0] == 1) else 4 * H * W
     nws = 0 if (noise_w is None or noise_w.numel() == 1) else 1
-    def launch():
-        check(lib().dge_upconv_fir(_p(x), _p(w_packed), _p(y), _f32(in_scale), _f32(out_scale), _f32(noise), nbs, _f32(noise_w), nws,
+    _launch(lib().dge_upconv_fir, (_p(x), _p(w_packed), _p(y), _f32(in_scale), _f32(out_scale), _f32(noise), nbs, _f32(noise_w), nws,
                                    _f32(bias), float(bias_scale), float(gain), int(act), B, H, W, Cin, cout, dtype_of(x), _stream()),
-              "dge_upconv_fir")
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); launch(); e1.record()
-        abytes = sum(t.numel() * t.element_size() for t in (x, y, w_packed))
-        PROFILE.append((e0, e1, 2.0 * 9.0 * Cin * cout * H * W * B, (B, H, W, Cin, cout, 3, "upfir", False), abytes))
-    else:
-        launch()
+            "dge_upconv_fir", 9.0 * Cin * cout * H * W * B, (B, H, W, Cin, cout, 3, "upfir", False), (x, y, w_packed))
     return y
 
 

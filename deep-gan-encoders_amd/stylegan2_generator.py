@@ -20,9 +20,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import ops, s2_conv
 from .collectives import all_reduce
-from .weight_cache import lookup, store
 
 __all__ = ["StyleGAN2Generator"]
 
@@ -39,9 +38,7 @@ def _dt(compute_dtype):
 
 
 import os as _os
-_PP_GEN = not _os.environ.get("DGE_NO_PP_GEN")
 _DENSE_CHAIN = _os.environ.get("DGE_DENSE_CHAIN") == "1"
-_UP_PP = _os.environ.get("DGE_UP_PP", "1") != "0"      # round 6: the default for the Cin >= 128 up layers (dge_up_pp: up_s4 / up_pp kernels; DGE_UP_PP=0: upconv_fir)
 
 
 class DenseBlock(nn.Module):
@@ -161,57 +158,11 @@ class ModulateConvBlock(nn.Module):
             self.noise_strength = nn.Parameter(torch.zeros(()))
         self._cache = {}
 
-    # -- derived weights, rebuilt only when the parameter changes ---------------------------
     def _prepared(self, dtype):
-        c = lookup(self._cache, ("w", dtype), self.weight)
-        if c is None:
-            mode = ops.PACK_UPFOLD if self.up else ops.PACK_FWD
-            hin = self.res // 2 if self.up else self.res         # the low-resolution layers get fragment-ordered weights (conv_small)
-            packed = ops.pack_conv_weight(self.weight, ops.pack_mode_for(self.weight, mode, hin, hin, dtype), dtype, self.wscale) \
-                if self.ksize == 3 else None
-            wsq = ops.weight_sumsq(self.weight, self.wscale) if self.demodulate else None
-            c = store(self._cache, ("w", dtype), self.weight, (packed, wsq))
-        return c
-
-    def _prepared_up(self, dtype):
-        """[9 units][Cout][Cin] weights of the phase-form up kernel (ops.upconv_fir), or None when the layer shape is not
-        covered by it (then the folded 3x3-per-phase form of conv2d(up=True) runs)."""
-        import os
-        # (input resolutions below 16: a single 16x16 t-pixel tile per sample would be mostly padding -- the folded form is faster)
-        if (not self.up or self.res < 32 or os.environ.get("DGE_UP_FOLDED") == "1"
-                or not ops.upconv_supported(self.in_c, self.out_c, dtype)):
-            return None
-        c = lookup(self._cache, ("wu", dtype), self.weight)
-        return c if c is not None else store(self._cache, ("wu", dtype), self.weight, ops.pack_upconv_weight(self.weight, dtype, self.wscale))
+        return s2_conv.prepared(self, dtype)
 
     def conv(self, x, s, d, noise, dt, rgb=None):
-        """The modulated conv proper (:898-921) on NHWC activations: shared-weight form with s / d as prologue / epilogue scales.
-        `rgb`: fused toRGB of the result (ops.conv2d), stride-1 layers only."""
-        nw = self.noise_strength.detach().reshape(1) if noise is not None else None
-        wu = self._prepared_up(dt)
-        if wu is not None:
-            assert rgb is None
-            B, H, W, _ = x.shape
-            if (_UP_PP and s is not None and d is not None and (noise is None or nw.numel() == 1)
-                    and ops.up_pp_supported(B, H, W, self.in_c, self.out_c, dt)):
-                # MFMA-bound up layers (Cin >= 128): fused modulation (:858-875) folded into one weight image per sample, ping-pong
-                # implicit GEMM with the FIR in registers (csrc/up_pp.hip)
-                wimg = ops.pack_up_pp(wu, self.out_c, self.in_c, in_scale=s, out_scale=d, gain=self.gain)
-                return ops.up_pp(x, wimg, self.out_c, bias=self.bias, bias_scale=self.bscale, noise=noise, noise_w=nw, act=self.act,
-                                 gain=self.gain)
-            return ops.upconv_fir(x, wu, self.out_c, in_scale=s, out_scale=d, bias=self.bias, bias_scale=self.bscale,
-                                  noise=noise, noise_w=nw, act=self.act, gain=self.gain)
-        B, H, W, _ = x.shape
-        if (rgb is None and not self.up and d is not None and s is not None and self.ksize == 3 and _PP_GEN
-                and ops.conv_pp_supported(B, H, W, self.in_c, self.out_c, dt)):
-            # MFMA-bound layers (>= 128 channels at 64^2 .. 256^2): the reference's fused modulation (:858-875) - style, demodulation
-            # and gain folded into one weight image per sample - feeding the ping-pong implicit GEMM (csrc/conv_pp.hip)
-            wpp = ops.pack_conv_pp(self.weight, self.wscale, in_scale=s, out_scale=d, gain=self.gain)
-            return ops.conv_pp(x, wpp, self.out_c, bias=self.bias, bias_scale=self.bscale, noise=noise, noise_w=nw, act=self.act,
-                               gain=self.gain)
-        packed, _ = self._prepared(dt)
-        return ops.conv2d(x, packed, self.out_c, 3, up=self.up, in_scale=s, out_scale=d, bias=self.bias,
-                          bias_scale=self.bscale, noise=noise, noise_w=nw, act=self.act, gain=self.gain, rgb=rgb)
+        return s2_conv.forward(self, x, s, d, noise, dt, rgb=rgb)
 
     def styles(self, w):
         """style s[b,i] and demodulation d[b,o] for latent rows w [B, 512] (any row stride)."""
