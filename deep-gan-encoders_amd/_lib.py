@@ -113,6 +113,9 @@ SIGNATURES = {
     "dge_fromrgb_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "dge_head_entry_size": [],
     "dge_heads_bwd": [_P, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P],
+    "dge_head_rows_entry_size": [],
+    "dge_heads_rows_fwd": [_P, _I, _P, _P, C.c_long, C.c_long, _I, _I, _I, _P],
+    "dge_heads_rows_bwd": [_P, _I, _I, _P, C.c_long, C.c_long, _I, _P, _P, _P, _P, _I, _I, _P],
     "dge_dense_wgrad": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _P],
     "dge_lpips_prep": [_P, _P, _I, _I, _I, _P, _P, _I, _P],
     "dge_lpips_prep_bwd": [_P, _P, _I, _I, _I, _P, _F, _I, _I, _P],

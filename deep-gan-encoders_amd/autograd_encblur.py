@@ -32,11 +32,64 @@ def blur_noises(E, B, R, dev):
     return noises
 
 
+def heads_rows_layout(E, B, dev):
+    """Static layout of the heads of an encoder that declares `w_rows` (E_Blur_W, E_Blur_W_2) for the grouped launches
+    dge_heads_rows_fwd / dge_heads_rows_bwd, built once per encoder and cached like autograd_enc.heads_layout.  The (mean, std)
+    vectors of all blocks live in one flat buffer, slot 2j = block j's musig1, slot 2j + 1 = musig2; the statistics gradients use
+    the same offsets.  One table entry per head that feeds W+: weight / bias pointers (parameter storage does not move), I, its
+    slot offset, the offset of its weight / bias gradient in flat buffers, and its one or two rows of w [B, 2L, O]: block j owns
+    rows 2(L-1-j) and 2(L-1-j)+1 (later blocks first, E_Blur_W.py:130-134), `w_rows` gives the row(s) inside that pair."""
+    import numpy as np
+    L = E.layer_count
+    heads = []                 # (state_dict prefix, module, slot, rows)
+    for j, blk in enumerate(E.decode_block):
+        for name, slot in (("inver_mod1", 2 * j), ("inver_mod2", 2 * j + 1)):
+            rows = E.w_rows.get(name)
+            if rows:
+                heads.append((f"decode_block.{j}.{name}", getattr(blk, name), slot, [2 * (L - 1 - j) + r for r in rows]))
+    key = (B, str(dev), tuple((h[1].weight.data_ptr(), h[1].bias.data_ptr()) for h in heads))
+    lay = E.__dict__.get("_heads_rows_layout")
+    if lay is not None and lay["key"] == key:
+        return lay
+    slots, moff = [], 0
+    for blk in E.decode_block:
+        for _ in range(2):
+            slots.append((moff, 2 * blk.inputs)); moff += B * 2 * blk.inputs
+    O = heads[0][1].weight.shape[0]
+    rec = np.dtype([("W", "u8"), ("bias", "u8"), ("moff", "i8"), ("woff", "i8"), ("I", "i4"), ("row_a", "i4"), ("row_b", "i4"), ("boff", "i4")])
+    assert rec.itemsize == ops.lib().dge_head_rows_entry_size()
+    tab = np.zeros(len(heads), dtype=rec)
+    woff, items = 0, []
+    for i, (name, lin, slot, rows) in enumerate(heads):
+        so, I = slots[slot]
+        if tuple(lin.weight.shape) != (O, I) or not lin.weight.is_contiguous() or not 1 <= len(rows) <= 2 or max(rows) >= 2 * L:
+            raise ops.DgeError(f"heads_rows_layout: head {name} does not fit the table (weight {tuple(lin.weight.shape)}, rows {rows})")
+        tab[i] = (lin.weight.data_ptr(), lin.bias.data_ptr(), so, woff, I, rows[0], rows[1] if len(rows) == 2 else -1, i * O)
+        items.append((name, slot, woff, i * O, I))
+        woff += O * I
+    lay = dict(key=key, tab=torch.from_numpy(tab.view(np.uint8).copy()).to(dev), items=items, slots=slots, n=len(heads), O=O, total_m=moff,
+               total_w=woff, max_I=max(it[4] for it in items), by_slot={it[1] for it in items})
+    E.__dict__["_heads_rows_layout"] = lay
+    return lay
+
+
 def blur_encoder_forward(E, img, noises=None, save=False):
     dt = _dt(E.compute_dtype)
     dev = img.device
     B, _, R, _ = img.shape
     noise, heads = getattr(E, "noise", True), getattr(E, "heads", True)       # E_Blur_Z (BlurBEZ): neither
+    # E_Blur_W / E_Blur_W_2 (`w_rows`): no head feeds the trunk, so all of them run as ONE launch after the last block, from a flat
+    # buffer of the blocks' (mean, std) vectors, and write their rows of w directly
+    lay = heads_rows_layout(E, B, dev) if getattr(E, "w_rows", None) else None
+    musig_all = torch.empty(lay["total_m"], dtype=torch.float32, device=dev) if lay else None
+
+    def ms_slot(i):
+        if lay is None:
+            return None
+        so, I = lay["slots"][i]
+        return musig_all[so:so + B * I].view(B, I)
+    if lay:
+        heads = False          # (the per-head launches below are BlurBE's)
     if noises is None and noise:
         noises = blur_noises(E, B, R, dev)
     cache = pack_cache(E)
@@ -44,13 +97,13 @@ def blur_encoder_forward(E, img, noises=None, save=False):
     fr = E.FromRGB.from_rgb
     stats = zeros(E.startf)
     x = ops.fromrgb(img.float(), fr.weight.detach(), fr.bias.detach(), dt, stats)
-    saved = {"img": img, "x0": x, "blocks": []} if save else None
+    saved = {"img": img, "x0": x, "blocks": [], "musig_all": musig_all} if save else None
     ws, ni = [], 0
     for j, blk in enumerate(E.decode_block):
         Cc, C2, H = blk.inputs, blk.outputs, R >> j
         last = not blk.has_last_conv
         has3 = Cc != C2
-        musig1, sc1, sh1 = ops.stats_finalize(stats, H * H)
+        musig1, sc1, sh1 = ops.stats_finalize(stats, H * H, musig_out=ms_slot(2 * j))
         w1 = ops.linear(musig1, blk.inver_mod1.weight.detach(), blk.inver_mod1.bias.detach()) if heads else None
         n1 = nw1 = None
         if noise:
@@ -59,7 +112,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
         st1 = zeros(Cc)
         x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
                         noise_w=nw1, bias=blk.bias_1.detach().reshape(-1), act=ops.ACT_LRELU, stats=st1)
-        musig2, sc2, sh2 = ops.stats_finalize(st1, H * H)
+        musig2, sc2, sh2 = ops.stats_finalize(st1, H * H, musig_out=ms_slot(2 * j + 1))
         w2 = ops.linear(musig2, blk.inver_mod2.weight.detach(), blk.inver_mod2.bias.detach()) if heads else None
         rec = dict(x=x, musig1=musig1, sc1=sc1, sh1=sh1, n1=n1, x1=x1, musig2=musig2, sc2=sc2, sh2=sh2) if save else None
         nstats = zeros(C2) if not last else None
@@ -102,6 +155,10 @@ def blur_encoder_forward(E, img, noises=None, save=False):
             saved["blocks"].append(rec)
         ws = [w2, w1] + ws
         x, stats = out, nstats
+    if lay:
+        w = torch.empty((B, 2 * E.layer_count, lay["O"]), dtype=torch.float32, device=dev)
+        ops.heads_rows_fwd(lay["tab"], lay["n"], musig_all, w)
+        return ops.nhwc_to_nchw(x), w, saved
     return ops.nhwc_to_nchw(x), (torch.stack(ws, dim=1) if heads else None), saved
 
 
@@ -112,9 +169,13 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
     gradients are dropped; the data path is the same launches in the same order, so the image gradient is the same bits.
     Every parameter gradient is None.
     An encoder without heads (E.heads False, E_Blur_Z) takes g_w=None: the statistics gradient fed to in_bwd_coef is then zero.
-    Without noise (E.noise False) no noise-weight gradient is formed."""
+    Without noise (E.noise False) no noise-weight gradient is formed.
+    An encoder with `w_rows` (E_Blur_W, E_Blur_W_2): g_w [B, 2L, O] with unit inner stride (row strides free); the backward of every
+    head runs once, in front of the block loop (ops.heads_rows_bwd).  A head that feeds no row of w (inver_mod1 of E_Blur_W_2) gets
+    no statistics gradient and None - not zeros - for its weight and bias."""
     cache = pack_cache(E)
     noise, heads = getattr(E, "noise", True), getattr(E, "heads", True)
+    lay = heads_rows_layout(E, saved["img"].shape[0], saved["img"].device) if getattr(E, "w_rows", None) else None
     dev = saved["img"].device
     L = E.layer_count
     B = saved["img"].shape[0]
@@ -124,6 +185,22 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
     g_out = None
     if g_const is not None:
         g_out = ops.nchw_to_nhwc(g_const.float().contiguous(), B, dt) if g_const.shape[0] == B else None
+    gms_all = None
+    if lay:
+        gms_all = torch.empty(lay["total_m"], dtype=torch.float32, device=dev)
+        gw_all = torch.empty(lay["total_w"], dtype=torch.float32, device=dev) if params else None
+        gb_all = torch.empty(lay["n"] * lay["O"], dtype=torch.float32, device=dev) if params else None
+        ops.heads_rows_bwd(lay["tab"], lay["n"], lay["max_I"], g_w, saved["musig_all"], gms_all, gw_all, gb_all)
+        if params:
+            for name, _, woff, boff, I in lay["items"]:
+                grads[name + ".weight"] = gw_all[woff:woff + lay["O"] * I].view(lay["O"], I)
+                grads[name + ".bias"] = gb_all[boff:boff + lay["O"]]
+
+    def gms_slot(i):
+        if i not in lay["by_slot"]:
+            return None
+        so, I = lay["slots"][i]
+        return gms_all[so:so + B * I].view(B, I)
     for j in range(L - 1, -1, -1):
         blk = E.decode_block[j]
         rec = saved["blocks"][j]
@@ -133,7 +210,9 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
         N = H * H
         last = not blk.has_last_conv
         has3 = Cc != C2
-        if not heads:
+        if lay:
+            gms2, gms1 = gms_slot(2 * j + 1), gms_slot(2 * j)
+        elif not heads:
             gms2 = gms1 = None
         else:
             g_w2, g_w1 = g_w[:, 2 * (L - 1 - j)], g_w[:, 2 * (L - 1 - j) + 1]
@@ -219,8 +298,10 @@ class BlurEncoderFunction(torch.autograd.Function):
         if g_w is None:
             g_w = torch.zeros((B, 2 * ctx.E.layer_count, ctx.E.latent_size), dtype=torch.float32, device=ctx.saved_acts["img"].device)
         frozen = not any(ctx.needs_input_grad[3:])      # no encoder parameter requires a gradient: data gradient only
-        grads, g_img = blur_encoder_backward(ctx.E, ctx.saved_acts, g_w.float().contiguous(), g_x, need_img=ctx.need_img,
-                                             params=not frozen)
+        g_w = g_w.float()
+        if not (getattr(ctx.E, "w_rows", None) and g_w.stride(2) == 1):      # (the grouped head backward reads strided rows)
+            g_w = g_w.contiguous()
+        grads, g_img = blur_encoder_backward(ctx.E, ctx.saved_acts, g_w, g_x, need_img=ctx.need_img, params=not frozen)
         if frozen:
             return (None, g_img, None) + (None,) * len(grads)
         if _DIRECT_ACCUMULATE:

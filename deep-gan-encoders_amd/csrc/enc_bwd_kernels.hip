@@ -841,6 +841,117 @@ extern "C" int dge_heads_bwd(const void* dev_entries, int n, int max_I, const fl
     return 0;
 }
 
+// ------------------------------------------------------------------ grouped heads with a row list (E_Blur_W / E_Blur_W_2)
+// A head owns one or two rows of the W+ tensor w [B][nrows][O] (E_Blur_W_2.py:128-130 writes w2 into both rows of its block): the
+// forward stores its result to each row, the backward reads g = g_w[:, row_a] (+ g_w[:, row_b]).  w / g_w are addressed by a
+// batch stride and a row stride (unit inner stride), so views work.  Rows outside [0, nrows) are skipped (row_b = -1: none).
+struct HeadRowsEntry { const float* W; const float* bias; long moff, woff; int I, row_a, row_b, boff; };
+constexpr int HEAD_ROWS_MAX_O = 1024;
+
+// one wave per (head, sample, output) with linear_kernel's arithmetic (lane-strided partial sum, wave_sum, + bias): the same bits
+__global__ __launch_bounds__(256) void head_rows_fwd_kernel(const HeadRowsEntry* __restrict__ tab, const float* __restrict__ musig_all,
+                                                            float* __restrict__ w, long ldb, long ldr, int nrows, int B, int O) {
+    const HeadRowsEntry e = tab[blockIdx.y];
+    const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (wave >= B * O) return;
+    const int b = wave / O, o = wave % O;
+    const float* xr = musig_all + e.moff + (size_t)b * e.I;
+    const float* wr = e.W + (size_t)o * e.I;
+    float s = 0.f;
+    for (int i = lane; i < e.I; i += 64) { const float xv = xr[i]; s += xv * wr[i]; }
+    s = wave_sum(s);
+    if (lane == 0) {
+        const float v = s + (e.bias ? e.bias[o] : 0.f);
+        if ((unsigned)e.row_a < (unsigned)nrows) w[(size_t)b * ldb + (size_t)e.row_a * ldr + o] = v;
+        if ((unsigned)e.row_b < (unsigned)nrows) w[(size_t)b * ldb + (size_t)e.row_b * ldr + o] = v;
+    }
+}
+
+// gms_l[b,k] = sum_o g[b,o] * W_l[o,k]: head_bwd_data_kernel's split (lanes own 64 consecutive k, 16 waves split O, LDS combine in a
+// fixed order) after the block has formed g = row_a (+ row_b) once in LDS
+__global__ __launch_bounds__(1024) void head_rows_bwd_data_kernel(const HeadRowsEntry* __restrict__ tab, const float* __restrict__ g,
+                                                                  long ldb, long ldr, int nrows, float* __restrict__ gms_all, int O) {
+    __shared__ float gs[HEAD_ROWS_MAX_O];
+    __shared__ float part[16][64];
+    const HeadRowsEntry e = tab[blockIdx.z];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = blockIdx.x * 64 + lane, b = blockIdx.y;
+    if (blockIdx.x * 64 >= e.I) return;                    // block-uniform
+    const bool ha = (unsigned)e.row_a < (unsigned)nrows, hb = (unsigned)e.row_b < (unsigned)nrows;
+    for (int o = threadIdx.x; o < O; o += 1024) {
+        float v = ha ? g[(size_t)b * ldb + (size_t)e.row_a * ldr + o] : 0.f;
+        if (hb) v += g[(size_t)b * ldb + (size_t)e.row_b * ldr + o];
+        gs[o] = v;
+    }
+    __syncthreads();
+    const int per = (O + 15) / 16, o0 = min(O, wave * per), o1 = min(O, o0 + per);
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) acc[j] = 0.f;
+    if (k < e.I) {
+        int o = o0;
+        for (; o + 7 < o1; o += 8) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc[j] += gs[o + j] * e.W[(size_t)(o + j) * e.I + k];
+        }
+        for (; o < o1; o++) acc[0] += gs[o] * e.W[(size_t)o * e.I + k];
+    }
+    part[wave][lane] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+    __syncthreads();
+    if (wave == 0 && k < e.I) {
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; j++) s += part[j][lane];
+        gms_all[e.moff + (size_t)b * e.I + k] = s;
+    }
+}
+// gW_l[o,i] = sum_b g[b,o] * musig_l[b,i], gb_l[o] = sum_b g[b,o]: one thread per element, samples in order
+__global__ __launch_bounds__(256) void head_rows_bwd_param_kernel(const HeadRowsEntry* __restrict__ tab, const float* __restrict__ g,
+                                                                  long ldb, long ldr, int nrows, const float* __restrict__ musig_all,
+                                                                  float* __restrict__ gw_all, float* __restrict__ gb_all, int B, int O) {
+    const HeadRowsEntry e = tab[blockIdx.y];
+    const bool ha = (unsigned)e.row_a < (unsigned)nrows, hb = (unsigned)e.row_b < (unsigned)nrows;
+    const int total = O * e.I;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int o = idx / e.I, i = idx - o * e.I;
+        float s = 0.f, sb = 0.f;
+        for (int b = 0; b < B; b++) {
+            float gv = ha ? g[(size_t)b * ldb + (size_t)e.row_a * ldr + o] : 0.f;
+            if (hb) gv += g[(size_t)b * ldb + (size_t)e.row_b * ldr + o];
+            s += gv * musig_all[e.moff + (size_t)b * e.I + i]; sb += gv;
+        }
+        gw_all[e.woff + idx] = s;
+        if (i == 0) gb_all[e.boff + o] = sb;
+    }
+}
+
+extern "C" int dge_head_rows_entry_size(void) { return (int)sizeof(HeadRowsEntry); }
+extern "C" int dge_heads_rows_fwd(const void* dev_entries, int n, const float* musig_all, float* w, long ldb, long ldr, int nrows,
+                                  int B, int O, hipStream_t s) {
+    DGE_CHECK(dev_entries && musig_all && w, "heads_rows_fwd: null tensor");
+    DGE_CHECK(n >= 1 && n <= 65535 && B >= 1 && O >= 1 && nrows >= 1 && (long)B * O <= (1L << 24), "heads_rows_fwd: bad sizes");
+    DGE_CHECK(ldr >= O && ldb >= O, "heads_rows_fwd: w strides (%ld, %ld) are below the row length %d", ldb, ldr, O);
+    hipLaunchKernelGGL(head_rows_fwd_kernel, dim3((unsigned)(((long)B * O * 64 + 255) / 256), n), dim3(256), 0, s,
+                       (const HeadRowsEntry*)dev_entries, musig_all, w, ldb, ldr, nrows, B, O);
+    DGE_LAUNCH_CHECK("heads_rows_fwd");
+    return 0;
+}
+extern "C" int dge_heads_rows_bwd(const void* dev_entries, int n, int max_I, const float* g, long ldb, long ldr, int nrows,
+                                  const float* musig_all, float* gms_all, float* gw_all, float* gb_all, int B, int O, hipStream_t s) {
+    DGE_CHECK(dev_entries && g && gms_all, "heads_rows_bwd: null tensor");
+    DGE_CHECK(n >= 1 && n <= 65535 && B >= 1 && B <= 65535 && O >= 1 && O <= HEAD_ROWS_MAX_O && max_I >= 1 && nrows >= 1,
+              "heads_rows_bwd: bad sizes (O <= %d)", HEAD_ROWS_MAX_O);
+    DGE_CHECK((gw_all == nullptr) == (gb_all == nullptr) && (gw_all == nullptr || musig_all != nullptr),
+              "heads_rows_bwd: gw_all, gb_all and musig_all go together (all null: the data gradient alone)");
+    hipLaunchKernelGGL(head_rows_bwd_data_kernel, dim3((max_I + 63) / 64, B, n), dim3(1024), 0, s, (const HeadRowsEntry*)dev_entries, g,
+                       ldb, ldr, nrows, gms_all, O);
+    if (gw_all)
+        hipLaunchKernelGGL(head_rows_bwd_param_kernel, dim3(64, n), dim3(256), 0, s, (const HeadRowsEntry*)dev_entries, g, ldb, ldr, nrows,
+                           musig_all, gw_all, gb_all, B, O);
+    DGE_LAUNCH_CHECK("heads_rows_bwd");
+    return 0;
+}
+
 extern "C" int dge_act_bwd(const void* gup, const void* a, const float* noise, void* gpre, float* red, int red_cols, int B, int H,
                            int W, int C, int pool, float scale, float slope, int dtype, hipStream_t s) {
     const int ep = dtype == DGE_BF16 ? 8 : 4;

@@ -61,9 +61,9 @@ class Case2Step(TrainStep):
     def __init__(self, generator, E, lpips_model, mapping=None, image_phases=IMAGE_PHASES, latent_terms=LATENT_TERMS,
                  latent_scale=0.01, lr=0.0015, beta_1=0.0, batch_size=2, z_dim=512, reference_noise=False):
         """`generator` + `mapping`: the StyleGAN1 Gs and Gm (mtype 1), or a StyleGAN2Generator alone (mtype 2; latent term `w`
-        only).  `E`: encoder_variants.BlurBE.  `image_phases`: which of imgs / AT1 / AT2 get an optimizer step of their own;
+        only).  `E`: encoder_variants.BlurBE, or its noise-free forms BlurBEW / BlurBEW2 (dge_amd.e_align_w).  `image_phases`: which of imgs / AT1 / AT2 get an optimizer step of their own;
         `latent_terms`: the terms of the last step's loss, (sum of terms) * latent_scale."""
-        from .encoder_variants import BlurBE
+        from .encoder_variants import BlurBE, BlurBEW
         self.image_phases = _names("image_phases", image_phases, IMAGE_PHASES)
         self.latent_terms = _names("latent_terms", latent_terms, LATENT_TERMS)
         family = generator_family(generator)
@@ -73,9 +73,9 @@ class Case2Step(TrainStep):
         if mapping is None and family != "stylegan2":
             raise ValueError("Case2Step: pass the StyleGAN1 synthesis network together with mapping=Gm (mtype 1) or a "
                              "StyleGAN2Generator (mtype 2)")
-        if not isinstance(E, BlurBE):
-            raise ValueError(f"Case2Step: case 2 trains the E_Blur encoder (encoder_variants.BlurBE), got {type(E).__name__}; "
-                             "E.BE belongs to case 1 (e_align.EAlignStep)")
+        if not isinstance(E, (BlurBE, BlurBEW)):            # (BlurBEW2 is a BlurBEW)
+            raise ValueError(f"Case2Step: case 2 trains the E_Blur encoder (encoder_variants.BlurBE, BlurBEW, BlurBEW2), got "
+                             f"{type(E).__name__}; E.BE belongs to case 1 (e_align.EAlignStep)")
         if mapping is None and "c" in self.latent_terms:
             raise ValueError("Case2Step: latent term 'c' is not offered for StyleGAN2: Cat256/E_align_case_2.py:221-228 logs loss_c "
                              "and trains on loss_w alone; use latent_terms=('w',)")
@@ -95,6 +95,8 @@ class Case2Step(TrainStep):
     def _encoder_noises(self, R):
         """reference_noise: the reference's own sequence of CPU draws (model/E/E_Blur.py: two per block, the second at half
         resolution where conv_2 is strided; one for the last block)."""
+        if not getattr(self.E, "noise", True):         # E_Blur_W / E_Blur_W_2 draw none: nothing to replay
+            return None
         out = []
         B = self.batch_size
         for j, blk in enumerate(self.E.decode_block):

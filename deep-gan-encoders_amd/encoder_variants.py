@@ -10,6 +10,9 @@
   The reference returns (tensor(0), tensor(0)); the evident intent is implemented:
   `(tensor(0), new_final(x.view(B, -1)))`, and `trunk()` exposes the activation before the head.
 
+* `E_Blur_W.BE` / `E_Blur_W_2.BE` (model/E/Ablation_Study, ablations 3 and 2): E_Blur without noise; the second writes one head
+  into both W+ rows of a block.  Their heads run as one grouped launch per direction (`w_rows`).
+
 State_dict keys match the reference (110 keys for E_Blur 1024/16/9, 57 for E_PG 256/64/7).
 """
 import numpy as np
@@ -128,6 +131,64 @@ class BlurBEZ(nn.Module):
             raise ValueError("progressive block_num != 9 is not used by the reference's scripts")
         from .autograd_encblur import BlurZEncoderFunction
         return BlurZEncoderFunction.apply(self, img, *list(self.parameters())), torch.tensor(0)
+
+
+# ----------------------------------------------------------------------------------- E_Blur_W / E_Blur_W_2
+class BlurBEWBlock(nn.Module):
+    """E_Blur_W.BEBlock (model/E/Ablation_Study/E_Blur_W.py:17-86; E_Blur_W_2.py has the same block): BlurBEBlock without the noise
+    weights and their two addcmul draws; both inver_mod heads stay."""
+
+    def __init__(self, inputs, outputs, latent_size, has_last_conv=True, fused_scale=True):
+        super().__init__()
+        self.has_last_conv, self.fused_scale, self.inputs, self.outputs = has_last_conv, fused_scale, inputs, outputs
+        self.bias_1 = nn.Parameter(torch.zeros(1, inputs, 1, 1))
+        self.inver_mod1 = ln.Linear(2 * inputs, latent_size, gain=1)
+        self.conv_1 = ln.Conv2d(inputs, inputs, 3, 1, 1, bias=False)
+        self.bias_2 = nn.Parameter(torch.zeros(1, outputs, 1, 1))
+        self.inver_mod2 = ln.Linear(2 * inputs, latent_size, gain=1)
+        self.blur = Blur(inputs)
+        if has_last_conv:
+            self.conv_2 = ln.Conv2d(inputs, outputs, 3, 1, 1, bias=False)     # stride 2 is realised as conv + pool (see module doc)
+        if inputs != outputs:
+            self.conv_3 = ln.Conv2d(inputs, outputs, 1, 1, 0)
+
+
+class BlurBEW(nn.Module):
+    """E_Blur_W.BE (model/E/Ablation_Study/E_Blur_W.py:89-136, the encoder of ablation_utils/3.E_align_w.py): E_Blur without noise.
+    forward -> (x [B,C,4,4], w [B,2*layer_count,512]), differentiable w.r.t. the parameters and the image (autograd_encblur).
+    `w_rows`: which rows of its block's pair of W+ rows each head writes; the heads of all blocks run as one grouped launch
+    (ops.heads_rows_fwd / heads_rows_bwd)."""
+
+    noise = False
+    w_rows = {"inver_mod1": (1,), "inver_mod2": (0,)}          # w_ = cat(w2, w1), E_Blur_W.py:130
+
+    def __init__(self, startf=16, maxf=512, layer_count=9, latent_size=512, channels=3, compute_dtype="bf16"):
+        super().__init__()
+        _dt(compute_dtype)
+        self.maxf, self.startf, self.latent_size, self.layer_count, self.compute_dtype = maxf, startf, latent_size, layer_count, compute_dtype
+        self.decode_block = nn.ModuleList()
+        self.FromRGB = FromRGB(channels, startf)
+        inputs, outputs, resolution = startf, startf * 2, 1024
+        for i in range(layer_count):
+            self.decode_block.append(BlurBEWBlock(inputs, outputs, latent_size, i + 1 != layer_count, fused_scale=resolution >= 128))
+            inputs, outputs = min(maxf, inputs * 2), min(maxf, outputs * 2)
+            resolution /= 2
+
+    def forward(self, img, block_num=9, noises=None):
+        if block_num != 9:
+            raise ValueError("progressive block_num != 9 is not used by the reference's scripts")
+        if noises is not None:
+            raise ValueError(f"{type(self).__name__} draws no noise (the reference's addcmul draws are commented out): noises must be None")
+        from .autograd_encblur import BlurEncoderFunction
+        return BlurEncoderFunction.apply(self, img, None, *list(self.parameters()))
+
+
+class BlurBEW2(BlurBEW):
+    """E_Blur_W_2.BE (the encoder of ablation_utils/2.E_align_w_2.py): BE.forward drops w1 and writes w2 into both W+ rows of its
+    block (w_ = cat(w2, w2), E_Blur_W_2.py:128-130).  inver_mod1 stays in the state_dict but never receives a gradient (its .grad
+    stays None, LREQAdam skips it); inver_mod2 receives the sum of the two row gradients."""
+
+    w_rows = {"inver_mod2": (0, 1)}
 
 
 # ----------------------------------------------------------------------------------- E_PG

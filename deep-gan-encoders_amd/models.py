@@ -5,7 +5,7 @@ import torch
 
 from .biggan_generator import BigGAN, BigGANConfig
 from .encoder import BE
-from .encoder_variants import BigBE, BlurBE, BlurBEZ, PGBE
+from .encoder_variants import BigBE, BlurBE, BlurBEW, BlurBEW2, BlurBEZ, PGBE
 from .lpips import LPIPS
 from .pggan_generator import PGGANGenerator
 from .stylegan1 import Generator, Mapping
@@ -68,10 +68,19 @@ def build_models_big(config, img_size=256, start_features=64, compute_dtype="bf1
     return G, E, (LPIPS(compute_dtype=compute_dtype).to(device) if lpips else None)
 
 
-def blur_encoder(img_size, start_features, compute_dtype, device, z_space=False, maxf=512):
-    """E_Blur (encoder_variants.BlurBE), or with z_space its Z-code form E_Blur_Z (BlurBEZ), sized for `img_size`."""
-    return (BlurBEZ if z_space else BlurBE)(startf=start_features, maxf=maxf, layer_count=int(math.log2(img_size) - 1), latent_size=512,
-                                            compute_dtype=compute_dtype).to(device)
+BLUR_VARIANTS = {None: BlurBE, "z": BlurBEZ, "w": BlurBEW, "w_2": BlurBEW2}
+
+
+def blur_encoder(img_size, start_features, compute_dtype, device, z_space=False, maxf=512, variant=None):
+    """E_Blur (encoder_variants.BlurBE), or with z_space its Z-code form E_Blur_Z (BlurBEZ), sized for `img_size`.
+    `variant`: "w" / "w_2" for the noise-free W-space forms E_Blur_W / E_Blur_W_2 (BlurBEW, BlurBEW2), "z" = z_space."""
+    if variant not in BLUR_VARIANTS:
+        raise ValueError(f"blur_encoder: unknown variant {variant!r}; supported: {sorted(k for k in BLUR_VARIANTS if k)}")
+    if z_space and variant not in (None, "z"):
+        raise ValueError("blur_encoder: z_space goes with variant 'z' only")
+    cls = BlurBEZ if z_space else BLUR_VARIANTS[variant]
+    return cls(startf=start_features, maxf=maxf, layer_count=int(math.log2(img_size) - 1), latent_size=512,
+               compute_dtype=compute_dtype).to(device)
 
 
 def load_lpips_weights(LP, vgg_weights=None, lin_weights=None, allow_standin=False):

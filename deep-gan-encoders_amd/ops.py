@@ -293,6 +293,7 @@ def linear(x, w, bias=None, wscale=1.0, bscale=1.0, add=0.0, act=ACT_NONE, gain=
     check(lib().dge_linear(C.c_void_p(x.data_ptr()), x.stride(0), _f32(w), _f32(bias), C.c_void_p(out.data_ptr()),
                            out.stride(0), B, I, O, float(wscale), float(bscale), float(add), act, float(gain),
                            1 if square_input else 0, _stream()), "dge_linear")
+    _log_dense("dge_linear")
     return out
 
 
@@ -365,6 +366,12 @@ def log_kernel():
     """KERNEL_LOG hook: records (name of the kernel the library launched last, current stream handle)"""
     if KERNEL_LOG is not None:
         KERNEL_LOG.append((last_kernel(), _stream()))
+
+
+def _log_dense(name):
+    """KERNEL_LOG entry of a dense-layer entry point (they select no kernel instantiation: the entry point's name)"""
+    if KERNEL_LOG is not None:
+        KERNEL_LOG.append((name, _stream()))
 
 
 def _launch(fn, args, name, macs, tag, tensors, wbytes=0, log=False):
@@ -796,6 +803,7 @@ def linear_t(x, w, y, mul=None, scale=1.0, accumulate=False, incx=1, incy=1, ldx
     ldy = y.stride(0) if ldy is None else ldy
     check(lib().dge_linear_t(C.c_void_p(x.data_ptr()), ldx, incx, _f32(w), _f32(mul), C.c_void_p(y.data_ptr()), ldy, incy,
                              B, O, K, float(scale), 1 if accumulate else 0, _stream()), "dge_linear_t")
+    _log_dense("dge_linear_t")
     return y
 
 
@@ -1028,7 +1036,34 @@ def dense_wgrad(gy, x, gw, gb=None, accumulate=False):
     I = x.shape[1]
     check(lib().dge_dense_wgrad(C.c_void_p(gy.data_ptr()), gy.stride(0), C.c_void_p(x.data_ptr()), x.stride(0), _f32(gw),
                                 _f32(gb), B, O, I, 1 if accumulate else 0, _stream()), "dge_dense_wgrad")
+    _log_dense("dge_dense_wgrad")
     return gw, gb
+
+
+def _rows_view(t, what):
+    """(pointer, batch stride, row stride, rows) of a W+ tensor [B, rows, O] f32 with unit inner stride (views allowed)"""
+    if not t.is_cuda or t.dtype != torch.float32 or t.ndim != 3 or t.stride(2) != 1:
+        raise DgeError(f"{what}: expected a float32 GPU tensor [B, rows, O] with unit inner stride")
+    return C.c_void_p(t.data_ptr()), t.stride(0), t.stride(1), t.shape[1]
+
+
+def heads_rows_fwd(tab, n, musig_all, w):
+    """Every head of a row-list table (autograd_encblur.heads_rows_layout) in one launch: w[b, row_a | row_b] = musig_l @ W_l^T + b_l,
+    written in place into w [B, rows, O] (a view with unit inner stride works); the bits of linear() per head."""
+    wp, ldb, ldr, rows = _rows_view(w, "heads_rows_fwd")
+    check(lib().dge_heads_rows_fwd(_p(tab), n, _f32(musig_all), wp, ldb, ldr, rows, w.shape[0], w.shape[2], _stream()), "dge_heads_rows_fwd")
+    _log_dense("dge_heads_rows_fwd")
+    return w
+
+
+def heads_rows_bwd(tab, n, max_I, g, musig_all, gms_all, gw_all=None, gb_all=None):
+    """Backward of heads_rows_fwd from g = dL/dw [B, rows, O] (row strides free): gms_all (flat, by the table's moff) always; gw_all /
+    gb_all (flat, by woff / boff) when given - without them the data gradient alone, one launch.  No atomics."""
+    gp, ldb, ldr, rows = _rows_view(g, "heads_rows_bwd")
+    check(lib().dge_heads_rows_bwd(_p(tab), n, int(max_I), gp, ldb, ldr, rows, _f32(musig_all), _f32(gms_all), _f32(gw_all), _f32(gb_all),
+                                   g.shape[0], g.shape[2], _stream()), "dge_heads_rows_bwd")
+    _log_dense("dge_heads_rows_bwd")
+    return gms_all
 
 
 def scale_(t, factor):

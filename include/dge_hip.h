@@ -405,6 +405,19 @@ int dge_heads_fwd(const void* dev_entries, int n, const float* musig_all, float*
 int dge_head_entry_size(void);
 int dge_heads_bwd(const void* dev_entries, int n, int max_I, const float* g, int ldg, const float* musig_all, float* gms_all,
                   float* gw_all, float* gb_all, int B, int O, dge_stream_t stream);
+/* Grouped heads with a row list (E_Blur_W.py:128-134, E_Blur_W_2.py:128-130: a head may own two rows of W+).
+ * dev_entries: n records {const float* W [O][I]; const float* bias; long moff, woff; int I, row_a, row_b, boff} in DEVICE memory
+ * (dge_head_rows_entry_size() bytes).  w / g [B][nrows][O] are addressed as b*ldb + row*ldr + o (elements, unit inner stride);
+ * a row outside [0, nrows) is skipped, row_b = -1 means none.
+ * fwd: w[b, row_a | row_b, o] = musig_all[moff + b*I ..] . W[o,:] + bias[o] in one launch, dge_linear's arithmetic bit for bit.
+ * bwd: with g_l = g[:, row_a] (+ g[:, row_b]):  gms_all[moff + b*I + k] = sum_o g_l*W,  gw_all[woff + o*I + i] = sum_b g_l*musig,
+ * gb_all[boff + o] = sum_b g_l; two launches, no atomics (the same bits every run).  gw_all = gb_all = NULL: the data gradient
+ * alone, one launch.  O <= 1024. */
+int dge_head_rows_entry_size(void);
+int dge_heads_rows_fwd(const void* dev_entries, int n, const float* musig_all, float* w, long ldb, long ldr, int nrows, int B, int O,
+                       dge_stream_t stream);
+int dge_heads_rows_bwd(const void* dev_entries, int n, int max_I, const float* g, long ldb, long ldr, int nrows,
+                       const float* musig_all, float* gms_all, float* gw_all, float* gb_all, int B, int O, dge_stream_t stream);
 /* gw[o][i] (+)= sum_b gy[b][o]*x[b][i]; gb[o] (+)= sum_b gy[b][o]   (ln.Linear parameter gradients) */
 int dge_dense_wgrad(const float* gy, int ldgy, const float* x, int ldx, float* gw, float* gb, int B, int O, int I,
                     int accumulate, dge_stream_t stream);

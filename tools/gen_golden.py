@@ -1516,6 +1516,147 @@ def gen_step_z():
 
 SECTIONS["step_z"] = gen_step_z
 
+# --------------------------------------------------------------------------- ablations 3 / 2: E_Blur_W, E_Blur_W_2
+_ENCW = {"w": "E_Blur_W", "w_2": "E_Blur_W_2"}
+
+
+def _encw_model(variant):
+    """E_Blur_W.BE / E_Blur_W_2.BE (model/E/Ablation_Study) at startf 32 / maxf 512 / 5 blocks, seeded parameters with the leaky-relu
+    kinks cleared for a 64^2 input.  The two variants share the trunk, so they get the same parameters and the same nudges."""
+    import importlib
+    M = importlib.import_module("model.E.Ablation_Study." + _ENCW[variant])
+    E = M.BE(startf=32, maxf=512, layer_count=5)
+    sd = R.fill_encoder(shapes_of(E.state_dict()), seed=81)
+    for k in sd:
+        if k.endswith("blur.weight"):
+            sd[k] = E.state_dict()[k].clone()
+    E.load_state_dict(sd)
+    img = R.randn("ew.img", (2, 3, 64, 64), 81, 0.5)
+    nudged, margin = clear_kinks([lambda: E(img)], *enc_kink_owners(E, "has_last_conv"))
+    return E, img, nudged, margin
+
+
+def gen_encw_grad():
+    """encw_keys.json: state_dict keys / shapes of both encoders at 1024/16/9 and 256/64/7.  encw_grad.npz: per variant (`<variant>:`
+    prefix) w, the gradients w.r.t. every parameter and the input image of (x*gx).sum() + (w*gw).sum(); the nudged biases
+    (`param:`) and x are common to both."""
+    import importlib
+    keys = {}
+    for variant, mod in _ENCW.items():
+        M = importlib.import_module("model.E.Ablation_Study." + mod)
+        for size, startf, L in ((1024, 16, 9), (256, 64, 7)):
+            keys[f"{variant}:{size}/{startf}/{L}"] = shapes_of(M.BE(startf=startf, maxf=512, layer_count=L).state_dict())
+    with open(os.path.join(OUT, "encw_keys.json"), "w") as f:
+        json.dump(keys, f)
+    out, common = {}, None
+    for variant in _ENCW:
+        E, img, nudged, margin = _encw_model(variant)
+        if common is None:
+            common = nudged
+            out.update({"param:" + k: v for k, v in nudged.items()})
+            out["kink_margin"] = np.array(margin)
+        else:
+            assert nudged.keys() == common.keys() and all(torch.equal(nudged[k], common[k]) for k in nudged)
+        img = img.clone().requires_grad_(True)
+        x, w = E(img)
+        gx, gw = R.randn("ew.gx", tuple(x.shape), 83), R.randn("ew.gw", tuple(w.shape), 84)
+        loss = (x * gx).sum() + (w * gw).sum()
+        loss.backward()
+        if "x" not in out:
+            out["x"] = x.detach()                  # the trunk output does not depend on the heads: stored once
+        assert torch.equal(out["x"], x.detach())
+        o = {"loss": loss.detach(), "g_img": img.grad, "w": w.detach()}
+        _grad_entries(E, o, full_max=4096)         # (two variants in one file: tensors above 4096 elements as their first 4096)
+        if variant == "w_2":
+            assert not any("inver_mod1" in k for k in o)
+        out.update({f"{variant}:{k}": v for k, v in o.items()})
+    save_npz("encw_grad.npz", **out)
+
+
+SECTIONS["encw_grad"] = gen_encw_grad
+
+
+def gen_step_w(variant):
+    """Two iterations of ablation_utils/3.E_align_w.py (:56-90; 2.E_align_w_2.py is the same loop) at reduced size: Gs / Gm / LPIPS
+    as gen_step_z (res 64, 5 blocks), E = the encw_grad encoder of the variant.  Every generator noise tensor is captured; the
+    encoders draw none."""
+    import warnings
+    import model.stylegan1.net as SG1
+    import training_utils as TU
+    from model.utils.custom_adam import LREQAdam
+    from oracle import lpips_ref as LR
+
+    L = 5
+    Gs = SG1.Generator(startf=16, maxf=64, layer_count=L, latent_size=512, channels=3)
+    sd = R.fill_encoder(shapes_of(Gs.state_dict()), seed=43)
+    for k in sd:
+        if k.endswith("blur.weight"):
+            sd[k] = Gs.state_dict()[k].clone()
+        if k == "const":
+            sd[k] = R.randn("sg1step.const", tuple(sd[k].shape), 43)
+    Gs.load_state_dict(sd)
+    Gm = SG1.Mapping(num_layers=2 * L, mapping_layers=8, latent_size=512, dlatent_size=512, mapping_fmaps=512)
+    Gm.load_state_dict({k: R.randn("sg1step.m." + k, tuple(v.shape), 44, 0.05 if k.endswith("weight") else 0.01)
+                        for k, v in Gm.state_dict().items()})
+    Gm.buffer1 = R.randn("sg1step.buffer1", (2 * L, 512), 44, 0.5)
+    Gm.eval()
+    layer_idx = torch.arange(2 * L)[np.newaxis, :, np.newaxis]
+    ones = torch.ones(layer_idx.shape, dtype=torch.float32)
+    coefs = torch.where(layer_idx < L, 0.7 * ones, ones)
+    E, _, _, _ = _encw_model(variant)
+    init = {k: v.clone() for k, v in E.state_dict().items()}
+    LP = LR.seeded_params(0)
+    lp = lambda a, b: LR.lpips(LP, a, b)
+    opt = LREQAdam([{"params": E.parameters()}], lr=0.0015, betas=(0.0, 0.99), weight_decay=0)
+    out = {}
+    B, lod = 2, L - 1
+    flat = lambda inf: [inf[0][0], inf[0][1], inf[0][2], inf[1], inf[2], inf[3], inf[4]]
+    for it in range(2):
+        z = R.randn(f"wstep.z{it}", (B, 512), 1)
+        with _NoiseFeeder(f"wstep.it{it}", 1) as nf:
+            with torch.no_grad():
+                w1 = Gm(z, coefs_m=coefs)
+                imgs1 = Gs.forward(w1, lod)
+            n_first = len(nf.log)
+            const2, w2 = E(imgs1)
+            assert len(nf.log) == n_first              # no encoder noise
+            imgs2 = Gs.forward(w2, lod)
+        if it == 0:
+            out["noise_shapes"] = np.array([list(s_) + [0] * (4 - len(s_)) for s_ in nf.log])
+            out["noise_split"] = np.array([n_first, 0])
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            l_i, i_i = TU.space_loss(imgs1, imgs2, lpips_model=lp)
+            opt.zero_grad()
+            l_i.backward(retain_graph=True)
+            opt.step()
+            l_w, i_w = TU.space_loss(w1, w2, image_space=False)
+            l_m = l_w * 0.01
+            opt.zero_grad()
+            l_m.backward()
+            opt.step()
+        out[f"it{it}_w1"] = w1.detach()
+        out[f"it{it}_w2"] = w2.detach()
+        out[f"it{it}_imgs2"] = imgs2.detach()
+        out[f"it{it}_losses"] = np.array([float(l_i.detach()), float(l_w.detach()), float(l_m.detach())])
+        out[f"it{it}_info"] = np.array([flat(i_i), flat(i_w)])
+        out[f"it{it}_param_checksum"] = np.array(R.checksum(E.state_dict()))
+        for k in ("decode_block.0.conv_1.weight", "decode_block.0.conv_2.weight", "decode_block.0.conv_3.weight", "decode_block.2.bias_1",
+                  "FromRGB.from_rgb.weight", "decode_block.4.inver_mod2.bias", "decode_block.1.inver_mod1.bias"):
+            out[f"it{it}_after_phase2:{k}"] = E.state_dict()[k].clone()
+        for k in ("decode_block.4.inver_mod2.weight", "decode_block.0.inver_mod2.weight", "decode_block.3.inver_mod1.weight"):
+            v = E.state_dict()[k]
+            out[f"it{it}_after_phase2_head:{k}"] = v.flatten()[:4096].clone()
+            out[f"it{it}_after_phase2_norm:{k}"] = v.norm()
+    if variant == "w_2":
+        assert all(torch.equal(init[k], v) for k, v in E.state_dict().items() if "inver_mod1" in k)
+    save_npz("step_w.npz" if variant == "w" else "step_w2.npz", **out)
+
+
+SECTIONS["step_w"] = lambda: gen_step_w("w")
+SECTIONS["step_w2"] = lambda: gen_step_w("w_2")
+
+
 # --------------------------------------------------------------------------- case 2: one optimizer step per loss, E_Blur
 _CASE2_KEYS = ("decode_block.0.conv_1.weight", "decode_block.3.conv_2.weight", "decode_block.4.inver_mod2.weight",
                "decode_block.1.bias_1", "FromRGB.from_rgb.weight")
