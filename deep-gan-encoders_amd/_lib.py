@@ -189,6 +189,13 @@ SIGNATURES = {
     "dge_wplus_lerp": [_P, _P, _I, _F, _P, _I, _I, _I, _P],
     "dge_wplus_lerp_bwd": [_P, _F, _P, C.c_long, _I, _P],
     "dge_embed_track": [_P, _P, _P, C.c_long, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
+    "dge_loss_reduce_rows": [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P],
+    "dge_ssim_fwd_rows": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "dge_space_loss_finalize_rows": [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _P],
+    "dge_space_loss_bwd_rows": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P],
+    "dge_latent_pnorm_rows_fwd": [_P, _P, _P, _I, C.c_long, _I, _P],
+    "dge_latent_pnorm_rows_bwd": [_P, _P, _P, _P, _I, C.c_long, _I, _F, _P],
+    "dge_embed_track_rows": [_P, _P, _P, _I, C.c_long, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
     "dge_mapping_bwd": [_P, _I, C.POINTER(DenseLayer), _I, _P, _P, _I, _P, _P, _I, _I, _I, _F, _P],
 }
 

@@ -25,7 +25,9 @@ def draw_noises(E, B, R, device):
 def heads_layout(E, B, dev):
     """Static layout of the encoder's `inver_mod` heads for the grouped backward (dge_heads_bwd): entry order = (inver_mod1,
     inver_mod2) per block; statistics / their gradients in one flat buffer, parameter gradients in another; the device-side
-    table holds the weight pointers (parameter storage does not move) and the column of each head in w (E.py:130-134)."""
+    table holds the weight pointers (parameter storage does not move) and the column of each head in w (E.py:130-134).
+    One layout per (batch size, device), kept while the parameters stay where they are: a captured graph holds the address of its
+    table, and a call at another batch size on the same encoder must not free it under that graph."""
     import numpy as np
     lins = []
     L = E.layer_count
@@ -33,7 +35,8 @@ def heads_layout(E, B, dev):
         lins.append((blk.inver_mod1, 2 * (L - 1 - j) + 1))
         lins.append((blk.inver_mod2, 2 * (L - 1 - j)))
     key = (B, str(dev), tuple((l.weight.data_ptr(), l.bias.data_ptr()) for l, _ in lins))
-    lay = E.__dict__.get("_heads_layout")
+    cache = E.__dict__.setdefault("_heads_layout", {})
+    lay = cache.get(key[:2])
     if lay is not None and lay["key"] == key:
         return lay
     O = lins[0][0].weight.shape[0]
@@ -51,7 +54,7 @@ def heads_layout(E, B, dev):
         woff += O * I
     lay = dict(key=key, tab=torch.from_numpy(tab.view(np.uint8).copy()).to(dev), items=items, n=len(lins), O=O, total_m=moff,
                total_w=woff, max_I=max(it[3] for it in items))
-    E.__dict__["_heads_layout"] = lay
+    cache[key[:2]] = lay
     return lay
 
 

@@ -38,7 +38,8 @@ def heads_rows_layout(E, B, dev):
     vectors of all blocks live in one flat buffer, slot 2j = block j's musig1, slot 2j + 1 = musig2; the statistics gradients use
     the same offsets.  One table entry per head that feeds W+: weight / bias pointers (parameter storage does not move), I, its
     slot offset, the offset of its weight / bias gradient in flat buffers, and its one or two rows of w [B, 2L, O]: block j owns
-    rows 2(L-1-j) and 2(L-1-j)+1 (later blocks first, E_Blur_W.py:130-134), `w_rows` gives the row(s) inside that pair."""
+    rows 2(L-1-j) and 2(L-1-j)+1 (later blocks first, E_Blur_W.py:130-134), `w_rows` gives the row(s) inside that pair.
+    One layout per (batch size, device), as autograd_enc.heads_layout keeps them (captured graphs hold the table's address)."""
     import numpy as np
     L = E.layer_count
     heads = []                 # (state_dict prefix, module, slot, rows)
@@ -48,7 +49,8 @@ def heads_rows_layout(E, B, dev):
             if rows:
                 heads.append((f"decode_block.{j}.{name}", getattr(blk, name), slot, [2 * (L - 1 - j) + r for r in rows]))
     key = (B, str(dev), tuple((h[1].weight.data_ptr(), h[1].bias.data_ptr()) for h in heads))
-    lay = E.__dict__.get("_heads_rows_layout")
+    cache = E.__dict__.setdefault("_heads_rows_layout", {})
+    lay = cache.get(key[:2])
     if lay is not None and lay["key"] == key:
         return lay
     slots, moff = [], 0
@@ -69,7 +71,7 @@ def heads_rows_layout(E, B, dev):
         woff += O * I
     lay = dict(key=key, tab=torch.from_numpy(tab.view(np.uint8).copy()).to(dev), items=items, slots=slots, n=len(heads), O=O, total_m=moff,
                total_w=woff, max_I=max(it[4] for it in items), by_slot={it[1] for it in items})
-    E.__dict__["_heads_rows_layout"] = lay
+    cache[key[:2]] = lay
     return lay
 
 

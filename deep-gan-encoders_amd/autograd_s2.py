@@ -11,11 +11,15 @@ from .weight_cache import version
 
 def _style_tables(mod, B, dt):
     """Row-concatenated style weights / demodulation tables of all 17 + 9 modulated blocks (cached; G is frozen in E_align)
-    so that every style vector and demodulation factor of a pass comes from two launches (dge_linear_rows, dge_demod_rows)."""
+    so that every style vector and demodulation factor of a pass comes from two launches (dge_linear_rows, dge_demod_rows).
+    One entry per (batch size, dtype), kept while the weights stay as they are: a captured graph holds the addresses of the index
+    tables of its batch size, and a step at another batch size on the same generator must not free them under it (the next
+    replay of the first graph would index through freed memory)."""
     nl = mod.num_layers
     groups = [(getattr(mod, f"layer{i}"), i) for i in range(nl - 1)] + [(getattr(mod, f"output{k}"), 2 * k + 1) for k in range(nl // 2)]
     key = (B, str(dt)) + tuple(version(p) for L, _ in groups for p in (L.style.weight, L.style.bias, L.weight))
-    hit = mod.__dict__.get("_style_tab")
+    cache = mod.__dict__.setdefault("_style_tab", {})
+    hit = cache.get(key[:2])
     if hit is not None and hit[0] == key:
         return hit[1]
     dev = groups[0][0].weight.device
@@ -49,7 +53,7 @@ def _style_tables(mod, B, dt):
     tab = dict(groups=groups, Wc=Wc, bc=bc, xoff=i32(xoff), ybase=i32(ybase), ybs=i32(ybs), s_off=s_off, s_total=B * off,
                wsq=torch.cat(wsq).contiguous(), woff=i32(woff), sbase=i32(sbase), cin=i32(cin), dbase=i32(dbase), dbs=i32(dbs),
                d_off=d_off, d_total=B * doff, wscale=st0.wscale, bscale=st0.bscale, add=st0.additional_bias, eps=groups[0][0].eps)
-    mod.__dict__["_style_tab"] = (key, tab)
+    cache[key[:2]] = (key, tab)
     return tab
 
 

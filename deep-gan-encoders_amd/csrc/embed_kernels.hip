@@ -5,6 +5,8 @@
 //   - the best-loss / best-norm trackers of the reference's `if` chains, kept on the device.
 // All small: one workgroup for the reductions (a fixed-order LDS tree, so the same bits every run), a flat grid for the
 // element-wise passes.  No atomics.
+// The norm and tracker kernels take the row of a batch from the grid (row r works on w + r*n and on element / block r of every
+// output and state array): the whole-tensor entry points launch one row, the *_rows ones a row per sample (independent inversions).
 #include "common.h"
 #include "../../include/dge_hip.h"
 
@@ -19,12 +21,14 @@ __device__ __forceinline__ float ipow_abs(float x, int p) {      // |x|^p for an
     return r;
 }
 
-// out[0] = (sum |w|^p)^(1/p); out_l2[0] = sqrt(sum w^2) when out_l2 != nullptr (either output may be null)
+// row r = blockIdx.x: out[r] = (sum |w[r]|^p)^(1/p); out_l2[r] = sqrt(sum w[r]^2) when out_l2 != nullptr (either output may be null)
 __global__ void __launch_bounds__(kRedThreads) pnorm_fwd_kernel(const float* __restrict__ w, float* __restrict__ out,
                                                                 float* __restrict__ out_l2, long n, int p) {
     __shared__ float sp[kRedThreads];
     __shared__ float s2[kRedThreads];
     const int t = threadIdx.x;
+    const size_t row = blockIdx.x;
+    w += row * n;
     float ap = 0.f, a2 = 0.f;
     for (long i = t; i < n; i += kRedThreads) {
         const float v = w[i];
@@ -43,18 +47,21 @@ __global__ void __launch_bounds__(kRedThreads) pnorm_fwd_kernel(const float* __r
     }
     if (t == 0) {
         const float s = sp[0];
-        if (out) out[0] = p == 1 ? s : (p == 2 ? sqrtf(s) : powf(s, 1.f / (float)p));
-        if (out_l2) out_l2[0] = sqrtf(s2[0]);
+        if (out) out[row] = p == 1 ? s : (p == 2 ? sqrtf(s) : powf(s, 1.f / (float)p));
+        if (out_l2) out_l2[row] = sqrtf(s2[0]);
     }
 }
 
-// g[i] += beta * gout * sign(w)|w|^(p-1) / ||w||_p^(p-1); 0 where ||w||_p == 0
+// row r = blockIdx.y: g[r][i] += beta * gout[r] * sign(w)|w|^(p-1) / ||w[r]||_p^(p-1); 0 where ||w[r]||_p == 0
 __global__ void pnorm_bwd_kernel(const float* __restrict__ w, const float* __restrict__ norm, const float* __restrict__ gout,
                                  float* __restrict__ g, long n, int p, float beta) {
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float nrm = norm[0];
-    const float scale = beta * (gout ? gout[0] : 1.f);
+    const size_t row = blockIdx.y;
+    w += row * n;
+    g += row * n;
+    const float nrm = norm[row];
+    const float scale = beta * (gout ? gout[row] : 1.f);
     const float v = w[i];
     float d = 0.f;
     if (nrm > 0.f) {
@@ -91,12 +98,17 @@ __global__ void wplus_lerp_bwd_kernel(const float* __restrict__ g, float psi, fl
 // check: min_loss > loss*loss_hyst -> min_loss := loss, event kind 0, best_loss_w := w;
 //        (norm_hyst > 0) min_norm > norm*norm_hyst -> min_norm := norm, event kind 1, best_norm_w := w.
 // Event e goes to ring slot e % cap as (iteration, kind, loss, norm); slots of dropped events are overwritten by later ones.
+// Row r = blockIdx.x has a tracker of its own: loss[r], norm[r], w[r][n], istate[r][4], fstate[r][2], events[r][cap][4], best_*[r][n].
 __global__ void __launch_bounds__(kRedThreads) embed_track_kernel(const float* __restrict__ loss, const float* __restrict__ norm,
                                                                   const float* __restrict__ w, long n, int* istate, float* fstate,
                                                                   float* best_loss_w, float* best_norm_w, float* events, int cap,
                                                                   int arm_rule, int arm_iter, float loss_hyst, float norm_hyst) {
     __shared__ int take[2];
     const int t = threadIdx.x;
+    const size_t row = blockIdx.x;
+    loss += row; norm += row; w += row * n;
+    istate += row * 4; fstate += row * 2; events += row * (size_t)cap * 4;
+    best_loss_w += row * n; best_norm_w += row * n;
     if (t == 0) {
         const int it = istate[0];
         const float l = loss[0], nr = norm[0];
@@ -193,5 +205,40 @@ extern "C" int dge_embed_track(const float* loss, const float* norm, const float
     hipLaunchKernelGGL(embed_track_kernel, dim3(1), dim3(kRedThreads), 0, s, loss, norm, w, n, istate, fstate, best_loss_w,
                        best_norm_w, events, cap, arm_rule, arm_iter, loss_hyst, norm_hyst);
     DGE_LAUNCH_CHECK("embed_track");
+    return 0;
+}
+
+// ---- a row per sample: B independent inversions in one batch
+extern "C" int dge_latent_pnorm_rows_fwd(const float* w, float* out, float* out_l2, int B, long n, int p, hipStream_t s) {
+    DGE_CHECK(B >= 1 && n > 0, "latent_pnorm_rows_fwd: B = %d, n = %ld", B, n);
+    DGE_CHECK(p >= 1 && p <= 16, "latent_pnorm_rows_fwd: p = %d (integer 1..16)", p);
+    DGE_CHECK(w && (out || out_l2), "latent_pnorm_rows_fwd: no input or no output");
+    hipLaunchKernelGGL(pnorm_fwd_kernel, dim3(B), dim3(kRedThreads), 0, s, w, out, out_l2, n, p);
+    dge_note_kernel("latent_pnorm_rows_fwd");
+    DGE_LAUNCH_CHECK("latent_pnorm_rows_fwd");
+    return 0;
+}
+
+extern "C" int dge_latent_pnorm_rows_bwd(const float* w, const float* norm, const float* gout, float* g, int B, long n, int p,
+                                         float beta, hipStream_t s) {
+    DGE_CHECK(B >= 1 && B <= 65535 && n > 0, "latent_pnorm_rows_bwd: B = %d, n = %ld", B, n);
+    DGE_CHECK(p >= 1 && p <= 16, "latent_pnorm_rows_bwd: p = %d (integer 1..16)", p);
+    DGE_CHECK(w && norm && g, "latent_pnorm_rows_bwd: null argument");
+    hipLaunchKernelGGL(pnorm_bwd_kernel, dim3(grid_of(n), B), dim3(256), 0, s, w, norm, gout, g, n, p, beta);
+    dge_note_kernel("latent_pnorm_rows_bwd");
+    DGE_LAUNCH_CHECK("latent_pnorm_rows_bwd");
+    return 0;
+}
+
+extern "C" int dge_embed_track_rows(const float* loss, const float* norm, const float* w, int B, long n, int* istate, float* fstate,
+                                    float* best_loss_w, float* best_norm_w, float* events, int cap, int arm_rule, int arm_iter,
+                                    float loss_hyst, float norm_hyst, hipStream_t s) {
+    DGE_CHECK(B >= 1 && n > 0 && cap > 0, "embed_track_rows: B = %d, n = %ld, cap = %d", B, n, cap);
+    DGE_CHECK(arm_rule == DGE_TRACK_ARM_AT || arm_rule == DGE_TRACK_ARM_AFTER, "embed_track_rows: arm_rule %d", arm_rule);
+    DGE_CHECK(loss && norm && w && istate && fstate && best_loss_w && best_norm_w && events, "embed_track_rows: null argument");
+    hipLaunchKernelGGL(embed_track_kernel, dim3(B), dim3(kRedThreads), 0, s, loss, norm, w, n, istate, fstate, best_loss_w,
+                       best_norm_w, events, cap, arm_rule, arm_iter, loss_hyst, norm_hyst);
+    dge_note_kernel("embed_track_rows");
+    DGE_LAUNCH_CHECK("embed_track_rows");
     return 0;
 }

@@ -80,6 +80,9 @@ struct Gauss11 { float g[11]; };
 
 // SSIM forward on [BC, h, w] planes: ssim_sum += sum of the SSIM map; optional derivative maps
 // dmap[0] = dS/dmu2, dmap[1] = dS/dE[b^2], dmap[2] = dS/dE[ab]  (each [BC,h,w]) for the backward.
+// ROWS: ssim_sum is [BC][tiles] and every workgroup STORES its tile's sum there (no atomics, nothing pre-zeroed): a sample's sums
+// stay apart and space_loss_finalize_rows_kernel adds them in a fixed order.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                         float* __restrict__ ssim_sum, float* __restrict__ dmap,
                                                         int BC, int h, int w, Gauss11 G) {
@@ -119,6 +122,10 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const float* __restrict__
     S = wave_sum(S);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = S;
     __syncthreads();
+    if (ROWS) {
+        if (threadIdx.x == 0) ssim_sum[((size_t)bc * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        return;
+    }
     if (det_on()) {            // deterministic mode: one slot per workgroup, ordered total into copy 0
         const int nslots = gridDim.x * gridDim.y * gridDim.z;
         const int sl = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -164,10 +171,8 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
 
 // loss/info on device.  sums (loss_reduce), ssim_sum, lpips (mean over batch, may be null).
 // out[0] = 5*mse + 3*cos + ssim_l + 2*lpips (:97); out[1..7] = mse, mse_mean, mse_std, kl, cos, ssim_l, lpips
-__global__ void space_loss_finalize_kernel(const float* __restrict__ sums, const float* __restrict__ ssim_sum,
-                                           const float* __restrict__ lpips, float* __restrict__ out, float n, float n_pooled,
-                                           int image_space) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ __forceinline__ void space_loss_terms(const float* sums, float ssim_tot, const float* lpips, float* out, float n,
+                                                 float n_pooled, int image_space) {
     const float mse = sums[0] / n;
     const float cosv = 1.f - sums[1] / (sqrtf(sums[2]) * sqrtf(sums[3]));
     const float ma = sums[4] / n, mb = sums[5] / n;
@@ -176,12 +181,60 @@ __global__ void space_loss_finalize_kernel(const float* __restrict__ sums, const
     float kl = sums[6] / n;
     if (isnan(kl)) kl = 0.f;
     if (isinf(kl)) kl = 1.f;
-    float ssim_tot = 0.f;
-    if (image_space) for (int k = 0; k < 32; k++) ssim_tot += ssim_sum[k];
     const float ssim_l = image_space ? 1.f - ssim_tot / n_pooled : 0.f;
     const float lp = (image_space && lpips) ? lpips[0] : 0.f;
     out[0] = 5.f * mse + 3.f * cosv + ssim_l + 2.f * lp;
     out[1] = mse; out[2] = dm * dm; out[3] = ds * ds; out[4] = kl; out[5] = cosv; out[6] = ssim_l; out[7] = lp;
+}
+__global__ void space_loss_finalize_kernel(const float* __restrict__ sums, const float* __restrict__ ssim_sum,
+                                           const float* __restrict__ lpips, float* __restrict__ out, float n, float n_pooled,
+                                           int image_space) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float ssim_tot = 0.f;
+    if (image_space) for (int k = 0; k < 32; k++) ssim_tot += ssim_sum[k];
+    space_loss_terms(sums, ssim_tot, lpips, out, n, n_pooled, image_space);
+}
+
+// The finaliser of the per-sample forms (loss_reduce3 / ssim_fwd with ROWS): one workgroup per (window k, sample b) adds the sample's
+// nblk partial sums and its SSIM tile sums (f.ssim[k] [B][f.ssim_cnt[k]]) in a fixed order - thread t takes entries t, t + 256, ...,
+// then an LDS tree - and writes sums7[b][k][8] (read by the gradient) and out8[b][k][8] (space_loss_terms with n, n_pooled of ONE
+// sample and the sample's own LPIPS value f.lpips[k][b]).
+struct RowsFin { const float* ssim[3]; const float* lpips[3]; int ssim_cnt[3]; float n[3], npool[3]; };
+__global__ __launch_bounds__(256) void space_loss_finalize_rows_kernel(const float* __restrict__ part, int nblk, RowsFin f,
+                                                                        float* __restrict__ sums7, float* __restrict__ out8,
+                                                                        int nwin, int image_space) {
+    __shared__ float red[8][256];
+    const int k = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const float* p = part + ((size_t)b * nwin + k) * nblk * 8;
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int i = t; i < nblk; i += 256) {
+        const float4 lo = *(const float4*)(p + (size_t)i * 8), hi = *(const float4*)(p + (size_t)i * 8 + 4);
+        v[0] += lo.x; v[1] += lo.y; v[2] += lo.z; v[3] += lo.w; v[4] += hi.x; v[5] += hi.y; v[6] += hi.z;
+    }
+    if (image_space) {
+        const float* sp = f.ssim[k] + (size_t)b * f.ssim_cnt[k];
+        for (int i = t; i < f.ssim_cnt[k]; i += 256) v[7] += sp[i];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) red[j][t] = v[j];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (t < h) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) red[j][t] += red[j][t + h];
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    float* sm = sums7 + ((size_t)b * nwin + k) * 8;
+    float tot[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) tot[j] = red[j][0];
+#pragma unroll
+    for (int j = 0; j < 7; j++) sm[j] = tot[j];
+    sm[7] = 0.f;
+    space_loss_terms(tot, tot[7], f.lpips[k] ? f.lpips[k] + b : nullptr, out8 + ((size_t)b * nwin + k) * 8, f.n[k], f.npool[k],
+                     image_space);
 }
 
 // d(5*mse + 3*cos)/db at full resolution + un-pooled gradient of the pooled terms:
@@ -220,6 +273,20 @@ __global__ void axpy_scalar_kernel(const float* __restrict__ x, const float* __r
 // gradient (which also re-read and re-wrote the 100 MB gradient as an accumulator).  These forms take up to 3 windows, all inside
 // window 0, and touch every pixel once.
 struct Win3 { int n; int y0[3], x0[3], h[3], w[3]; };
+// ROWS (both forms below): workgroup grid (block, sample); a workgroup walks the pixels of its own sample and STORES its seven sums
+// per window to sums[sample][window][block][8] (block_store_sums): no atomics, nothing pre-zeroed, the same bits in both reduction
+// modes.  space_loss_finalize_rows_kernel adds a sample's blocks in a fixed order.
+__device__ __forceinline__ void block_store_sums(const float* vals, float* dst, float* red) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = 0; i < 7; i++) {
+        const float s = wave_sum(vals[i]);
+        if (lane == 0) red[i * 4 + wave] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8)
+        dst[threadIdx.x] = threadIdx.x < 7 ? red[threadIdx.x * 4] + red[threadIdx.x * 4 + 1] + red[threadIdx.x * 4 + 2] + red[threadIdx.x * 4 + 3] : 0.f;
+}
+template <bool ROWS>
 __global__ __launch_bounds__(256) void loss_reduce3_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                             float* __restrict__ sums, int B, int C, int H, int W, Win3 wn) {
     __shared__ float red[7 * 4];
@@ -229,10 +296,11 @@ __global__ __launch_bounds__(256) void loss_reduce3_kernel(const float* __restri
 #pragma unroll
         for (int i = 0; i < 7; i++) v[k][i] = 0.f;
     const int h0 = wn.h[0], w0 = wn.w[0];
-    const long npix = (long)B * h0 * w0;
+    const int b0 = ROWS ? blockIdx.y : 0;
+    const long npix = (long)(ROWS ? 1 : B) * h0 * w0;
     const size_t plane = (size_t)H * W;
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < npix; idx += gridDim.x * 256L) {
-        const int x = idx % w0; const long r = idx / w0; const int y = r % h0; const int bb = r / h0;
+        const int x = idx % w0; const long r = idx / w0; const int y = r % h0; const int bb = b0 + r / h0;
         const int gy = wn.y0[0] + y, gx = wn.x0[0] + x;
         const size_t off = (size_t)bb * C * plane + (size_t)gy * W + gx;
         float t[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -258,13 +326,15 @@ __global__ __launch_bounds__(256) void loss_reduce3_kernel(const float* __restri
         }
     }
     for (int k = 0; k < wn.n; k++) {                      // (not offered in deterministic mode: one slot domain per launch)
-        block_atomic_sums(v[k], 7, sums + (size_t)k * 16 * 8, red);
+        if (ROWS) block_store_sums(v[k], sums + (((size_t)blockIdx.y * wn.n + k) * gridDim.x + blockIdx.x) * 8, red);
+        else block_atomic_sums(v[k], 7, sums + (size_t)k * 16 * 8, red);
         __syncthreads();
     }
 }
 
 // loss_reduce3 for RGB images, four consecutive pixels of a row per thread: every plane is read once with 16-byte loads (the general
 // form walks the channels three times with scalar loads and decodes the pixel index with 64-bit divisions)
+template <bool ROWS>
 __global__ __launch_bounds__(256) void loss_reduce3_c3v4_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                  float* __restrict__ sums, int B, int H, int W, Win3 wn) {
     __shared__ float red[7 * 4];
@@ -274,10 +344,11 @@ __global__ __launch_bounds__(256) void loss_reduce3_c3v4_kernel(const float* __r
 #pragma unroll
         for (int i = 0; i < 7; i++) v[k][i] = 0.f;
     const unsigned h0 = wn.h[0], w4 = wn.w[0] / 4;
-    const unsigned n4 = (unsigned)B * h0 * w4;
+    const unsigned b0 = ROWS ? blockIdx.y : 0u;
+    const unsigned n4 = (ROWS ? 1u : (unsigned)B) * h0 * w4;
     const size_t plane = (size_t)H * W;
     for (unsigned idx = blockIdx.x * 256u + threadIdx.x; idx < n4; idx += gridDim.x * 256u) {
-        const unsigned x4 = idx % w4, r = idx / w4, y = r % h0, bb = r / h0;
+        const unsigned x4 = idx % w4, r = idx / w4, y = r % h0, bb = b0 + r / h0;
         const int gy = wn.y0[0] + (int)y, gx = wn.x0[0] + 4 * (int)x4;
         const size_t off = (size_t)bb * 3 * plane + (size_t)gy * W + gx;
         float4 A[3], Bq[3];
@@ -317,7 +388,8 @@ __global__ __launch_bounds__(256) void loss_reduce3_c3v4_kernel(const float* __r
         }
     }
     for (int k = 0; k < wn.n; k++) {
-        block_atomic_sums(v[k], 7, sums + (size_t)k * 16 * 8, red);
+        if (ROWS) block_store_sums(v[k], sums + (((size_t)blockIdx.y * wn.n + k) * gridDim.x + blockIdx.x) * 8, red);
+        else block_atomic_sums(v[k], 7, sums + (size_t)k * 16 * 8, red);
         __syncthreads();
     }
 }
@@ -351,8 +423,16 @@ __global__ void crop_pool6_kernel(Pool6 t, int BC, int H, int W) {
 }
 
 struct Bwd3 { const float* sums[3]; const float* gp[3]; int k[3]; float n[3], wgt[3]; };
+// ROWS (both forms below): q.sums[k] is window k's column of sums7 [B][nwin][8]; plane bc reads the sums of its own sample
+// (bc / rows.C).  rows.swap: the planes are passed as (b, a) and g receives d/da (5*mse + 3*cos is symmetric: |a| and |b| change places).
+struct RowSums { int C, stride, swap; };
+template <bool ROWS>
+__device__ __forceinline__ const float* sums_of(const Bwd3& q, int k, int bc, RowSums rows) {
+    return ROWS ? q.sums[k] + (size_t)(bc / rows.C) * rows.stride : q.sums[k];
+}
+template <bool ROWS>
 __global__ void space_loss_bwd3_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ g,
-                                       int BC, int H, int W, Win3 wn, Bwd3 q) {
+                                       int BC, int H, int W, Win3 wn, Bwd3 q, RowSums rows) {
     const long tot = (long)BC * wn.h[0] * wn.w[0];
     const long idx = blockIdx.x * 256L + threadIdx.x;
     if (idx >= tot) return;
@@ -366,8 +446,8 @@ __global__ void space_loss_bwd3_kernel(const float* __restrict__ a, const float*
         if (k >= wn.n || q.wgt[k] == 0.f) continue;
         const int ly = gy - wn.y0[k], lx = gx - wn.x0[k];
         if ((unsigned)ly >= (unsigned)wn.h[k] || (unsigned)lx >= (unsigned)wn.w[k]) continue;
-        const float* sm = q.sums[k];
-        const float na = sqrtf(sm[2]), nb = sqrtf(sm[3]);
+        const float* sm = sums_of<ROWS>(q, k, bc, rows);
+        const float na = sqrtf(sm[ROWS && rows.swap ? 3 : 2]), nb = sqrtf(sm[ROWS && rows.swap ? 2 : 3]);
         float v = 10.f * (bv - av) / q.n[k] + 3.f * (-av / (na * nb) + sm[1] * bv / (na * nb * nb * nb));
         if (q.gp[k]) {
             const int kk = q.k[k], oh = wn.h[k] / kk, ow = wn.w[k] / kk;
@@ -388,8 +468,9 @@ __device__ __forceinline__ int div_small(int a, int d, float rd) {
 // The same with four consecutive pixels of a row per thread (16-byte accesses; W, window 0's x0 and width multiples of 4) and
 // (row, plane) from the grid: the scalar form spends ~10 integer divisions per pixel (400 instructions for 12 bytes of traffic:
 // 243 us on the three windows of a batch of eight 1024^2 images, 4x its byte floor).
+template <bool ROWS>
 __global__ __launch_bounds__(256) void space_loss_bwd3_v4_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ g,
-                                                                  int H, int W, Win3 wn, Bwd3 q) {
+                                                                  int H, int W, Win3 wn, Bwd3 q, RowSums rows) {
     const int x = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (x >= wn.w[0]) return;
     const int bc = blockIdx.z;
@@ -403,8 +484,8 @@ __global__ __launch_bounds__(256) void space_loss_bwd3_v4_kernel(const float* __
         if (k >= wn.n || q.wgt[k] == 0.f) continue;
         const int ly = gy - wn.y0[k];
         if ((unsigned)ly >= (unsigned)wn.h[k]) continue;
-        const float* sm = q.sums[k];
-        const float na = sqrtf(sm[2]), nb = sqrtf(sm[3]);
+        const float* sm = sums_of<ROWS>(q, k, bc, rows);
+        const float na = sqrtf(sm[ROWS && rows.swap ? 3 : 2]), nb = sqrtf(sm[ROWS && rows.swap ? 2 : 3]);
         const float c0 = 10.f / q.n[k], inv = 1.f / (na * nb), c2 = sm[1] * inv / (nb * nb);
         const int kk = q.k[k];
         const float rk = 1.f / (float)kk, rkk = 1.f / (float)(kk * kk);
@@ -525,9 +606,9 @@ extern "C" int dge_loss_reduce3(const float* a, const float* b, float* sums, int
     int grid = (int)((npix + 255) / 256); if (grid > 2048) grid = 2048;
     if (C == 3 && W % 4 == 0 && wn.x0[0] % 4 == 0 && wn.w[0] % 4 == 0 && npix / 4 < (1L << 31)) {
         int g4 = (int)((npix / 4 + 255) / 256); if (g4 > 2048) g4 = 2048;
-        hipLaunchKernelGGL(loss_reduce3_c3v4_kernel, dim3(g4), dim3(256), 0, s, a, b, sums, B, H, W, wn);
+        hipLaunchKernelGGL(loss_reduce3_c3v4_kernel<false>, dim3(g4), dim3(256), 0, s, a, b, sums, B, H, W, wn);
     } else
-    hipLaunchKernelGGL(loss_reduce3_kernel, dim3(grid), dim3(256), 0, s, a, b, sums, B, C, H, W, wn);
+    hipLaunchKernelGGL(loss_reduce3_kernel<false>, dim3(grid), dim3(256), 0, s, a, b, sums, B, C, H, W, wn);
     DGE_LAUNCH_CHECK("loss_reduce3");
     return 0;
 }
@@ -565,9 +646,9 @@ extern "C" int dge_space_loss_bwd3(const float* a, const float* b, const float* 
     }
     const long tot = (long)BC * wn.h[0] * wn.w[0];
     if (W % 4 == 0 && wn.x0[0] % 4 == 0 && wn.w[0] % 4 == 0 && wn.h[0] <= 65535 && BC <= 65535 && wn.h[0] < (1 << 22) && wn.w[0] < (1 << 22))
-        hipLaunchKernelGGL(space_loss_bwd3_v4_kernel, dim3((unsigned)((wn.w[0] / 4 + 255) / 256), wn.h[0], BC), dim3(256), 0, s, a, b, g, H, W, wn, q);
+        hipLaunchKernelGGL(space_loss_bwd3_v4_kernel<false>, dim3((unsigned)((wn.w[0] / 4 + 255) / 256), wn.h[0], BC), dim3(256), 0, s, a, b, g, H, W, wn, q, RowSums{1, 0, 0});
     else
-        hipLaunchKernelGGL(space_loss_bwd3_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a, b, g, BC, H, W, wn, q);
+        hipLaunchKernelGGL(space_loss_bwd3_kernel<false>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a, b, g, BC, H, W, wn, q, RowSums{1, 0, 0});
     DGE_LAUNCH_CHECK("space_loss_bwd3");
     return 0;
 }
@@ -598,6 +679,85 @@ extern "C" int dge_space_loss_bwd_split(const float* a, const float* b, const fl
         dge_note_kernel("space_loss_bwd_split");
     }
     DGE_LAUNCH_CHECK("space_loss_bwd_split");
+    return 0;
+}
+
+// ------------------------------------------------------------------ per-sample forms (every sample of the batch a loss of its own)
+// dge_loss_reduce3 with the samples kept apart: partials [B][nwin][nblk][8], every entry WRITTEN by workgroup (block, sample).
+extern "C" int dge_loss_reduce_rows(const float* a, const float* b, float* partials, int B, int C, int H, int W, const int* wins,
+                                    int nwin, int nblk, hipStream_t s) {
+    Win3 wn;
+    if (win3_from(wins, nwin, H, W, wn)) return -1;
+    DGE_CHECK(a && b && partials && B >= 1 && B <= 65535 && C >= 1 && nblk >= 1 && nblk <= 65535, "loss_reduce_rows: bad arguments (B %d, C %d, nblk %d)", B, C, nblk);
+    DGE_CHECK((long)wn.h[0] * wn.w[0] < (1L << 31), "loss_reduce_rows: window 0 too large");
+    if (C == 3 && W % 4 == 0 && wn.x0[0] % 4 == 0 && wn.w[0] % 4 == 0) {
+        hipLaunchKernelGGL(loss_reduce3_c3v4_kernel<true>, dim3(nblk, B), dim3(256), 0, s, a, b, partials, B, H, W, wn);
+        dge_note_kernel("loss_reduce_rows_c3v4");
+    } else {
+        hipLaunchKernelGGL(loss_reduce3_kernel<true>, dim3(nblk, B), dim3(256), 0, s, a, b, partials, B, C, H, W, wn);
+        dge_note_kernel("loss_reduce_rows");
+    }
+    DGE_LAUNCH_CHECK("loss_reduce_rows");
+    return 0;
+}
+
+// dge_ssim_fwd with the tile sums kept apart: tile_sums [BC][ceil(h/16) * ceil(w/16)], every entry WRITTEN.
+extern "C" int dge_ssim_fwd_rows(const float* a, const float* b, float* tile_sums, float* dmap, int BC, int h, int w, hipStream_t s) {
+    DGE_CHECK(a && b && tile_sums && BC >= 1 && BC <= 65535 && h >= 1 && w >= 1 && (h + 15) / 16 <= 65535, "ssim_fwd_rows: bad arguments");
+    hipLaunchKernelGGL(ssim_fwd_kernel<true>, dim3((w + 15) / 16, (h + 15) / 16, BC), dim3(256), 0, s, a, b, tile_sums, dmap, BC, h, w, gauss11());
+    dge_note_kernel("ssim_fwd_rows");
+    DGE_LAUNCH_CHECK("ssim_fwd_rows");
+    return 0;
+}
+
+// sums7 [B][nwin][8] and out8 [B][nwin][8] from the partials of dge_loss_reduce_rows, the tile sums of dge_ssim_fwd_rows
+// (ssim_tiles[k] [B][ssim_cnt[k]], image_space only) and the per-sample LPIPS values lpips_val[k] [B] (array or entries may be NULL).
+extern "C" int dge_space_loss_finalize_rows(const float* partials, int nblk, const float* const* ssim_tiles, const int* ssim_cnt,
+                                            const float* const* lpips_val, float* sums7, float* out8, int B, int nwin, const float* n,
+                                            const float* n_pooled, int image_space, hipStream_t s) {
+    DGE_CHECK(partials && sums7 && out8 && n && n_pooled && B >= 1 && B <= 65535 && nwin >= 1 && nwin <= 3 && nblk >= 1,
+              "space_loss_finalize_rows: bad arguments");
+    DGE_CHECK(!image_space || (ssim_tiles && ssim_cnt), "space_loss_finalize_rows: image space needs the SSIM tile sums");
+    RowsFin f;
+    for (int k = 0; k < 3; k++) {
+        const int j = k < nwin ? k : 0;
+        f.ssim[k] = image_space ? ssim_tiles[j] : nullptr; f.ssim_cnt[k] = image_space ? ssim_cnt[j] : 0;
+        f.lpips[k] = (image_space && lpips_val) ? lpips_val[j] : nullptr; f.n[k] = n[j]; f.npool[k] = n_pooled[j];
+        DGE_CHECK(f.n[k] > 0.f && (!image_space || (f.ssim[k] && f.ssim_cnt[k] >= 1 && f.npool[k] > 0.f)), "space_loss_finalize_rows: bad window %d", k);
+    }
+    hipLaunchKernelGGL(space_loss_finalize_rows_kernel, dim3(nwin, B), dim3(256), 0, s, partials, nblk, f, sums7, out8, nwin, image_space);
+    dge_note_kernel("space_loss_finalize_rows");
+    DGE_LAUNCH_CHECK("space_loss_finalize_rows");
+    return 0;
+}
+
+// dge_space_loss_bwd3 with per-sample sums: sums7 [B][nwin][8] (dge_space_loss_finalize_rows), n[k] counted for one sample; g over
+// window 0 is WRITTEN.  swap_ab != 0: the planes are passed as (b, a) and g receives the gradient w.r.t. the first argument.
+extern "C" int dge_space_loss_bwd_rows(const float* a, const float* b, const float* sums7, const float* const* g_pooled, float* g, int B,
+                                       int C, int H, int W, const int* wins, const int* ks, const float* n, const float* weight, int nwin,
+                                       int swap_ab, hipStream_t s) {
+    Win3 wn;
+    if (win3_from(wins, nwin, H, W, wn)) return -1;
+    DGE_CHECK(a && b && sums7 && g && ks && n && weight && B >= 1 && C >= 1, "space_loss_bwd_rows: bad arguments");
+    Bwd3 q;
+    for (int k = 0; k < 3; k++) {
+        const int j = k < nwin ? k : 0;
+        q.sums[k] = sums7 + (size_t)j * 8; q.gp[k] = g_pooled ? g_pooled[j] : nullptr; q.k[k] = ks[j]; q.n[k] = n[j]; q.wgt[k] = k < nwin ? weight[j] : 0.f;
+        DGE_CHECK(q.k[k] >= 1 && q.n[k] > 0.f, "space_loss_bwd_rows: bad window %d", k);
+        DGE_CHECK(!q.gp[k] || (wn.h[k] / q.k[k] >= 1 && wn.w[k] / q.k[k] >= 1), "space_loss_bwd_rows: window %d smaller than its pooling factor", k);
+    }
+    const RowSums rows = {C, nwin * 8, swap_ab ? 1 : 0};
+    const long BC = (long)B * C;
+    const long tot = BC * wn.h[0] * wn.w[0];
+    if (W % 4 == 0 && wn.x0[0] % 4 == 0 && wn.w[0] % 4 == 0 && wn.h[0] <= 65535 && BC <= 65535 && wn.w[0] < (1 << 22)) {
+        hipLaunchKernelGGL(space_loss_bwd3_v4_kernel<true>, dim3((unsigned)((wn.w[0] / 4 + 255) / 256), wn.h[0], (unsigned)BC), dim3(256), 0, s, a, b, g, H, W, wn, q, rows);
+        dge_note_kernel("space_loss_bwd_rows_v4");
+    } else {
+        DGE_CHECK((tot + 255) / 256 < (1L << 31), "space_loss_bwd_rows: too many elements");
+        hipLaunchKernelGGL(space_loss_bwd3_kernel<true>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a, b, g, (int)BC, H, W, wn, q, rows);
+        dge_note_kernel("space_loss_bwd_rows");
+    }
+    DGE_LAUNCH_CHECK("space_loss_bwd_rows");
     return 0;
 }
 
@@ -670,7 +830,7 @@ extern "C" int dge_ssim_box7(const float* a, const float* b, float* sums, int BC
 }
 
 extern "C" int dge_ssim_fwd(const float* a, const float* b, float* ssim_sum, float* dmap, int BC, int h, int w, hipStream_t s) {
-    hipLaunchKernelGGL(ssim_fwd_kernel, dim3((w + 15) / 16, (h + 15) / 16, BC), dim3(256), 0, s, a, b, ssim_sum, dmap, BC, h, w, gauss11());
+    hipLaunchKernelGGL(ssim_fwd_kernel<false>, dim3((w + 15) / 16, (h + 15) / 16, BC), dim3(256), 0, s, a, b, ssim_sum, dmap, BC, h, w, gauss11());
     DGE_LAUNCH_CHECK("ssim_fwd");
     return 0;
 }

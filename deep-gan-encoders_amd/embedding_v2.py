@@ -30,6 +30,19 @@ Decisions where the reference cannot run as written:
   * W mode takes a batch B >= 1 (the reference hard-codes 1); the norm and space_loss terms couple the rows as in the reference.
     StyleGAN2's W-mode start is randn(B, L, 512) from a seeded generator (unseeded in the reference).
   * --optimizeE parses true / false strictly (the reference's `type=bool` cannot be switched off).
+  * `independent` (--independent true; W mode only): the B rows of a group are B inversions of their own, each equal to the
+    batch-1 run of its image.  Every loss and logged value of row b is what the coupled code returns on the one-row slices
+    (losses.image_loss_tsa_rows / space_loss_rows, ||w1[b]||_p); phase 1 back-propagates sum_b loss_msiv_b, phase 2
+    sum_b (0.01*lat_b + beta*||w1[b]||_p), so row b of w1.grad is the gradient of row b's own loss and Adam (element-wise) gives
+    the row the steps it would take alone.  Decisions of this mode:
+      - one tracker per row (iteration counter, minima, event ring, best latents); the minima of EVERY row restart at
+        begin_image for both generators: the StyleGAN2 carry-over between groups is a property of the sequential batch-1 loop
+        (image k inherits image k-1's minima) and has no counterpart among rows that run side by side - it stays there;
+      - StyleGAN2 start code: row b of group g draws randn(1, L, 512) from manual_seed(seed + g*B + b), the draw a batch-1 run
+        makes for image number g*B + b;
+      - files are numbered by image (g*B + b), not by group; main() pads a short last group by repeating its last image (the
+        captured iteration keeps its shape) and discards the padded rows' outputs;
+      - the encoder is shared by a group, so mode "E" has no independent form (ValueError).
 """
 import argparse
 import math
@@ -78,6 +91,22 @@ class _PNorm(torch.autograd.Function):
         return g, None
 
 
+class _PNormRows(torch.autograd.Function):
+    """||w[b]||_p for every row b -> [B] (dge_latent_pnorm_rows_fwd) with its gradient (dge_latent_pnorm_rows_bwd)."""
+
+    @staticmethod
+    def forward(ctx, w, p):
+        ctx.w, ctx.p = w.detach(), p
+        ctx.n = ops.latent_pnorm_rows(ctx.w, p)
+        return ctx.n.clone()
+
+    @staticmethod
+    def backward(ctx, go):
+        g = torch.zeros_like(ctx.w)
+        ops.latent_pnorm_rows_bwd(ctx.w, ctx.n, g, ctx.p, 1.0, gout=go.contiguous().float())
+        return g, None
+
+
 class _WplusLerp(torch.autograd.Function):
     """avg + psi*(w - avg) on every row of a W+ code (dge_wplus_lerp / dge_wplus_lerp_bwd)."""
 
@@ -93,9 +122,12 @@ class _WplusLerp(torch.autograd.Function):
 
 class LatentEmbedStep(GraphReplay):
     def __init__(self, G, E, lpips_model, mode="E", generator="sg2", lr=0.005, beta_1=0.0, beta=None, norm_p=2, truncation=None,
-                 iterations=None, arm_iter=None, events_cap=256, seed=0):
+                 iterations=None, arm_iter=None, events_cap=256, seed=0, independent=False):
         if mode not in ("E", "W"):
             raise ValueError(f"mode must be 'E' or 'W', got {mode!r}")
+        if independent and mode != "W":
+            raise ValueError("independent=True needs mode 'W': in mode 'E' one encoder is shared by the rows of a group")
+        self.independent = bool(independent)
         if generator not in ("sg1", "sg2"):
             raise ValueError(f"generator must be 'sg1' or 'sg2', got {generator!r}")
         mt = 1 if generator == "sg1" else 2
@@ -132,6 +164,16 @@ class LatentEmbedStep(GraphReplay):
     def _track_alloc(self, shape, dev):
         n = int(math.prod(shape))
         t = self._track
+        if self.independent:      # a tracker per row: every state array gets a leading batch dimension
+            B = shape[0]
+            if t is None or t["n"] != n or t["fstate"].device != torch.device(dev):
+                self._track = t = dict(n=n, istate=torch.zeros((B, 4), dtype=torch.int32, device=dev),
+                                       fstate=torch.tensor([self.rules["init"]] * B, dtype=torch.float32, device=dev),
+                                       best_loss=torch.zeros(shape, dtype=torch.float32, device=dev),
+                                       best_norm=torch.zeros(shape, dtype=torch.float32, device=dev),
+                                       events=torch.zeros((B, self.events_cap, 4), dtype=torch.float32, device=dev),
+                                       l2=torch.zeros(B, dtype=torch.float32, device=dev))
+            return t
         if t is None or t["n"] != n or t["fstate"].device != torch.device(dev):
             self._track = t = dict(n=n, istate=torch.zeros(4, dtype=torch.int32, device=dev),
                                    fstate=torch.tensor(self.rules["init"], dtype=torch.float32, device=dev),
@@ -145,8 +187,9 @@ class LatentEmbedStep(GraphReplay):
         """Start an image group: E mode re-loads the encoder checkpoint and clears the Adam state (embedding_v2_*.py: the
         per-group `E.load_state_dict`); W mode starts a fresh w1 (StyleGAN1: E(imgs1) detached, StyleGAN2: seeded randn or
         `w_init`) with a fresh Adam state.  The tracker's iteration counter and event log restart (in place: a captured
-        iteration stays valid); the StyleGAN1 minima restart too, the StyleGAN2 ones carry over.  `noises`: optional noise list of
-        the StyleGAN1 W-mode E(imgs1) (parity runs)."""
+        iteration stays valid); the StyleGAN1 minima restart too, the StyleGAN2 ones carry over (independent mode: the minima of
+        every row restart, and a StyleGAN2 row draws its start code from the seed of its image number).  `noises`: optional noise
+        list of the StyleGAN1 W-mode E(imgs1) (parity runs)."""
         dev = imgs1.device
         B = imgs1.shape[0]
         self.group += 1
@@ -164,6 +207,9 @@ class LatentEmbedStep(GraphReplay):
                     if self._const2 is None or self._const2.shape != c0.shape:
                         self._const2 = torch.empty_like(c0)
                     self._const2.copy_(c0)
+                elif self.independent:
+                    w0 = torch.cat([torch.randn((1,) + shape[1:], generator=torch.Generator().manual_seed(int(self.seed) + self.group * B + r))
+                                    for r in range(B)])
                 else:
                     gen = torch.Generator().manual_seed(int(self.seed) + self.group)
                     w0 = torch.randn(shape, generator=gen)
@@ -178,8 +224,8 @@ class LatentEmbedStep(GraphReplay):
         first = getattr(self, "_track_started", False) is False
         t["istate"].zero_()
         t["events"].zero_()
-        if first or self.rules["reset_per_group"]:
-            t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32))
+        if first or self.rules["reset_per_group"] or self.independent:
+            t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32).expand_as(t["fstate"]))
         self._track_started = True
 
     # ------------------------------------------------------------------ one iteration
@@ -193,8 +239,10 @@ class LatentEmbedStep(GraphReplay):
 
     def step(self, imgs1, noises=(None, None, None)):
         """One iteration; `noises` = optional (E(imgs1), G, E(imgs2)) noise lists for parity runs (StyleGAN2: G's is unused, the
-        synthesis noise is its fixed buffers; W mode: E(imgs1)'s is unused)."""
+        synthesis noise is its fixed buffers; W mode: E(imgs1)'s is unused).  Independent mode: the loss entries of the result
+        (`loss_msiv`, `loss_w`, `loss_c1`, `norm`, `loss_mslv`, `w_norm`) are [B], `info_img` is [B,3,8]."""
         E = self.E
+        rows = self.independent
         t = self._track
         if t is None:
             raise RuntimeError("LatentEmbedStep.step: call begin_image() first")
@@ -206,28 +254,40 @@ class LatentEmbedStep(GraphReplay):
         imgs2 = self._generate(w1, noises[1])
         if self.generator == "sg1":
             const3, w2 = E(imgs2, noises=noises[2])
-        loss_msiv, info_img = losses.image_loss_tsa(imgs1, imgs2, self.lpips, weights=IMG_WEIGHTS, grad_windows=(True, True, True))
+        image_loss, latent_loss = (losses.image_loss_tsa_rows, losses.space_loss_rows) if rows else (losses.image_loss_tsa, losses.space_loss)
+        loss_msiv, info_img = image_loss(imgs1, imgs2, self.lpips, weights=IMG_WEIGHTS, grad_windows=(True, True, True))
         self.opt.zero_grad()
         loss_msiv.backward(retain_graph=True)
         self.opt.step()
         if self.generator == "sg2":
             const3, w2 = E(imgs2, noises=noises[2])
-        loss_w, _ = losses.space_loss(w1, w2, image_space=False)
+        loss_w, info_w = latent_loss(w1, w2, image_space=False)
         lat = loss_w
         loss_c1 = None
         if const2 is not None:
-            loss_c1, _ = losses.space_loss(const2, const3, image_space=False)
+            loss_c1, info_c = latent_loss(const2, const3, image_space=False)
             lat = lat + loss_c1
-        nrm = _PNorm.apply(w1, self.norm_p)
-        loss_mslv = lat * 0.01 + nrm * self.beta
+        nrm = (_PNormRows if rows else _PNorm).apply(w1, self.norm_p)
+        loss_mslv = lat * 0.01 + (nrm.sum() if rows else nrm) * self.beta
         self.opt.zero_grad()
         loss_mslv.backward()
         self.opt.step()
         w1d = w1.detach()
-        ops.latent_l2(w1d, out=t["l2"])
         r = self.rules
-        ops.embed_track(loss_msiv.detach(), t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
-                        r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
+        if rows:      # the values of every row: the [B] columns of the info tensors (the scalars above are their sums over the rows)
+            loss_msiv = info_img[:, 0, 0] * IMG_WEIGHTS[0] + info_img[:, 1, 0] * IMG_WEIGHTS[1] + info_img[:, 2, 0] * IMG_WEIGHTS[2]
+            loss_w = info_w[:, 0].contiguous()
+            loss_mslv = loss_w * 0.01 + nrm.detach() * self.beta
+            if loss_c1 is not None:
+                loss_c1 = info_c[:, 0].contiguous()
+                loss_mslv = loss_mslv + loss_c1 * 0.01
+            ops.latent_l2_rows(w1d, out=t["l2"])
+            ops.embed_track_rows(loss_msiv, t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
+                                 r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
+        else:
+            ops.latent_l2(w1d, out=t["l2"])
+            ops.embed_track(loss_msiv.detach(), t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
+                            r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
         ops.zero_arena_end()
         self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const2=const2.detach() if const2 is not None else None,
                          const3=const3.detach(), loss_msiv=loss_msiv.detach(), info_img=info_img, loss_w=loss_w.detach(),
@@ -267,7 +327,21 @@ class LatentEmbedStep(GraphReplay):
 
     # ------------------------------------------------------------------ tracker read-out (one host read)
     def tracker(self):
+        """The tracker's state on the host; independent mode: a list with one such read-out per row."""
         t = self._track
+        if self.independent:
+            B, cap = t["istate"].shape[0], self.events_cap
+            # one host read: the three small state arrays travel as one float tensor (counters < 2^24 are exact in f32)
+            host = torch.cat((t["istate"].float(), t["fstate"], t["events"].reshape(B, -1)), dim=1).cpu()
+            bl, bn = t["best_loss"], t["best_norm"]
+            out = []
+            for b in range(B):
+                ist = [int(v) for v in host[b, :4]]
+                ev = host[b, 6:].view(cap, 4)
+                idx = [k % cap for k in range(max(0, ist[1] - cap), ist[1])]
+                out.append(dict(iteration=ist[0], events=[(int(ev[i, 0]), int(ev[i, 1]), float(ev[i, 2]), float(ev[i, 3])) for i in idx],
+                                dropped=ist[2], min_loss=float(host[b, 4]), min_norm=float(host[b, 5]), best_loss=bl[b:b + 1].clone(), best_norm=bn[b:b + 1].clone()))
+            return out
         ist = t["istate"].cpu().tolist()
         cnt, cap = ist[1], self.events_cap
         ev = t["events"].cpu()
@@ -298,11 +372,24 @@ def write_tracker_files(tr, g, models_dir, result_dir):
         torch.save(tr["best_norm"], os.path.join(models_dir, "id%d-iter%d-norm-min%f-imgLoss%f.pt" % (g, it, norm, lm if lm is not None else 0.0)))
 
 
-def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=None, group=0, w_init=None):
+def group_plan(n_images, batch_size):
+    """Independent mode: the groups of a folder of n_images as (first image number, rows kept) - every image is inverted, the last
+    group may keep fewer rows than the batch holds."""
+    return [(i, min(batch_size, n_images - i)) for i in range(0, n_images, batch_size)]
+
+
+def padded_rows(first, batch_size, n_images):
+    """Image numbers of the batch_size rows of the group that starts at image `first`: a short last group repeats its last image
+    (the captured iteration keeps its shape); the caller discards those rows' outputs."""
+    return [min(first + r, n_images - 1) for r in range(batch_size)]
+
+
+def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=None, group=0, w_init=None, keep=None):
     """`iterations` iterations on one image group.  launch="graph" captures the iteration once (its warm-up iteration is a real one)
     and replays it; later groups go through set_image.  With `out_dir` the reference's every-`save_every` dumps (image pair,
     per-row w1) are written - one host read per chunk - and, at the end, the trackers' files.  Returns the last result dict with
-    the tracker read-out under "tracker"."""
+    the tracker read-out under "tracker".  Independent mode: files carry the image number group*B + b and that row's norm and loss;
+    only the first `keep` rows (default: all) are written, and "tracker" is the list of per-row read-outs."""
     st.begin_image(imgs1, w_init=w_init)
     if launch not in ("graph", "eager"):
         raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
@@ -313,8 +400,17 @@ def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=Non
         if out_dir is None:
             return
         from .infer import save_image_grid
-        norm, loss = float(r["w_norm"]), float(r["loss_msiv"])
         B = imgs1.shape[0]
+        if st.independent:
+            vals = torch.stack((r["w_norm"], r["loss_msiv"])).cpu()
+            for b in range(B if keep is None else keep):
+                num, norm, loss = group * B + b, float(vals[0, b]), float(vals[1, b])
+                save_image_grid(torch.cat((imgs1[b:b + 1], r["imgs2"][b:b + 1])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f-imgLoss%f.jpg"
+                                                                                              % (num, i, norm, loss)), nrow=2)
+                torch.save(r["w1"][b:b + 1].clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f-imgLoss%f.pt"
+                                                                        % (num, 0, i, norm, loss)))
+            return
+        norm, loss = float(r["w_norm"]), float(r["loss_msiv"])
         save_image_grid(torch.cat((imgs1[:B], r["imgs2"][:B])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f-imgLoss%f.jpg"
                                                                             % (group, i, norm, loss)), nrow=2)
         for k, row in enumerate(r["w1"]):
@@ -328,7 +424,10 @@ def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=Non
         if save_every and i % save_every == 0:
             dump(i, r)
     tr = st.tracker()
-    if out_dir is not None:
+    if out_dir is not None and st.independent:
+        for b in range(imgs1.shape[0] if keep is None else keep):
+            write_tracker_files(tr[b], group * imgs1.shape[0] + b, os.path.join(out_dir, "models"), out_dir)
+    elif out_dir is not None:
         write_tracker_files(tr, group, os.path.join(out_dir, "models"), out_dir)
     r = dict(r)
     r["tracker"] = tr
@@ -392,6 +491,8 @@ def make_parser():
     p.set_defaults(mtype=1)
     p.add_argument("--img_dir", default="./real_imgs/", help="a directory of images or a .pt tensor in [0,1]")
     p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise W+ directly")
+    p.add_argument("--independent", type=strict_bool, default=False,
+                   help="true (with --optimizeE false): every image of a batch is an inversion of its own, equal to its batch-1 run")
     p.add_argument("--beta", type=float, default=None, help="weight of ||w1||_p: default 1e-3 (mtype 1), 3e-4 (mtype 2)")
     p.add_argument("--norm_p", type=int, default=None, help="p of ||w1||_p (default 2)")
     p.add_argument("--truncation", type=float, default=None, help="StyleGAN2: psi of avg + psi*(w1 - avg) (default 0.7; 1: none)")
@@ -410,6 +511,8 @@ def parse_args(argv=None):
     args = make_parser().parse_args(argv)
     if args.mtype not in DEFAULTS:
         raise SystemExit("embedding_v2: --mtype must be 1 (StyleGAN1) or 2 (StyleGAN2)")
+    if args.independent and args.optimizeE:
+        raise SystemExit("embedding_v2: --independent true needs --optimizeE false (the fine-tuned encoder is shared by a group)")
     for k, v in DEFAULTS[args.mtype].items():
         if getattr(args, k, None) is None:
             setattr(args, k, v)
@@ -440,9 +543,23 @@ def main(argv=None):
     imgs = _load_imgs(args.img_dir, args.img_size, dev)
     st = LatentEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", generator="sg1" if args.mtype == 1 else "sg2", lr=args.lr,
                          beta_1=args.beta_1, beta=args.beta, norm_p=args.norm_p, truncation=args.truncation,
-                         iterations=args.iterations, seed=args.seed)
+                         iterations=args.iterations, seed=args.seed, independent=args.independent)
     bs = args.batch_size
     w_all = []
+    if args.independent:
+        n = imgs.shape[0]
+        for g, (first, keep) in enumerate(group_plan(n, bs)):
+            imgs1 = imgs[padded_rows(first, bs, n)].contiguous()
+            r = invert_v2(st, imgs1, args.iterations, launch=args.launch, save_every=args.save_every, out_dir=out, group=g, keep=keep)
+            vals = torch.stack((r["loss_msiv"], r["w_norm"])).cpu()
+            for b in range(keep):
+                print("image %d: loss_msiv %.5f  w_norm %.4f  events %d" % (first + b, float(vals[0, b]), float(vals[1, b]),
+                                                                          len(r["tracker"][b]["events"])))
+                w_all.append(r["w1"][b].clone().cpu())
+            save_image_grid(r["imgs2"][:keep], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
+        if w_all:
+            torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (n - 1)))
+        return st
     ngroups = imgs.shape[0] // bs
     for g in range(ngroups):
         imgs1 = imgs[g * bs:(g + 1) * bs].contiguous()

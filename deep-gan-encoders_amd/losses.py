@@ -1,6 +1,10 @@
 """space_loss (reference training_utils.py:54-99) and the three-scale image loss of
 E_align_s2.py:185-203 on the HIP kernels, as autograd Functions whose forward also produces the
-analytic gradient w.r.t. the second argument (the only one that carries grad in E_align)."""
+analytic gradient w.r.t. the second argument (the only one that carries grad in E_align).
+
+image_loss_tsa_rows / space_loss_rows are the per-sample forms (embedding_v2 `independent`): sample b's loss is what image_loss_tsa
+/ space_loss return on the one-row slices, the result is their sum over b (so the gradient of row b is the gradient of its own
+loss) and the info tensors keep a row per sample."""
 import contextlib
 import os
 
@@ -122,6 +126,17 @@ def _side_streams(dev, n):
     return have[:n]
 
 
+def _window_streams(dev, lpips_model, nw, npix):
+    """(caller's stream, the side streams the windows 1.. of a merged-window loss fork to - none when they stay on one stream)"""
+    main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+    # (the stream switches cost ~1 ms of host time per step: taken where the GPU work hides them - >= 4 Mpixel per call - or
+    #  where the host is out of the picture, i.e. while a hipGraph is being captured)
+    fork = (main is not None and lpips_model is not None and nw > 1 and _WINDOW_STREAMS and not ops.is_deterministic()
+            and getattr(lpips_model, "_streams_warm", False)
+            and (npix >= (4 << 20) or torch.cuda.is_current_stream_capturing()))
+    return main, (_side_streams(dev, nw - 1) if fork else [])
+
+
 def _space_loss_windows3(a, b, wins, lpips_model, weights, g, need, gb=None, g_split=None):
     """The three nested attention windows of image_loss_tsa with every image pass merged (dge_loss_reduce3, dge_crop_pool_multi,
     dge_space_loss_bwd3): `g` (or None) is WRITTEN with the weighted sum of the windows' gradients; need[i] False leaves window i
@@ -156,13 +171,8 @@ def _space_loss_windows3(a, b, wins, lpips_model, weights, g, need, gb=None, g_s
     # other on a half-empty chip.  Each window gets its own stream (forked off the caller's, joined before the results are
     # read); the first call stays on one stream (it fills the LPIPS weight-pack cache), so does the deterministic mode (its
     # slot workspace belongs to one stream at a time).
-    main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-    # (the stream switches cost ~1 ms of host time per step: taken where the GPU work hides them - >= 4 Mpixel per call - or
-    #  where the host is out of the picture, i.e. while a hipGraph is being captured)
-    fork = (main is not None and lpips_model is not None and nw > 1 and _WINDOW_STREAMS and not ops.is_deterministic()
-            and getattr(lpips_model, "_streams_warm", False)
-            and (B * H * W >= (4 << 20) or torch.cuda.is_current_stream_capturing()))
-    side = _side_streams(dev, nw - 1) if fork else []
+    main, side = _window_streams(dev, lpips_model, nw, B * H * W)
+    fork = bool(side)
     for i, win in enumerate(wins):
         y0, x0, h, w = win
         ap, bp, k = aps[i], bps[i], ks[i]
@@ -382,3 +392,133 @@ def space_loss(imgs1, imgs2, image_space=True, lpips_model=None, global_batch=No
     if need:
         loss = _ScaledGrad.apply(imgs2, loss, g)
     return loss, out8
+
+
+# ------------------------------------------------------------------ per-sample forms
+def _space_loss_rows(a, b, wins, image_space, lpips_model, weights, need, ga=None, gb=None):
+    """space_loss of every sample of a, b [B,C,H,W] on up to 3 nested windows (all inside window 0), the samples kept apart:
+    dge_loss_reduce_rows, dge_crop_pool_multi, per window dge_ssim_fwd_rows + per-sample LPIPS + the pooled gradient, then
+    dge_space_loss_finalize_rows and dge_space_loss_bwd_rows.  `gb` (or None) is WRITTEN with sum_k weights[k] * d loss_k[sample]/db
+    (need[k] False leaves window k out), `ga` (latents only) with the gradient w.r.t. a.  Returns out8 [B, nwin, 8]."""
+    import ctypes as C
+    B, Cc, H, W = a.shape
+    dev = a.device
+    L = lib()
+    nw = len(wins)
+    h0, w0 = wins[0][2], wins[0][3]
+    nblk = max(1, min(256, (h0 * w0 + 1023) // 1024))
+    wflat = (C.c_int * (4 * nw))(*[int(v) for win in wins for v in win])
+    part = torch.empty((B, nw, nblk, 8), dtype=torch.float32, device=dev)
+    check(L.dge_loss_reduce_rows(_f32(a), _f32(b), _p(part), B, Cc, H, W, wflat, nw, nblk, _stream()), "dge_loss_reduce_rows")
+    ops.log_kernel()
+    ks = [_pool_factor(win[2]) if image_space else 1 for win in wins]
+    ns = [float(Cc * win[2] * win[3]) for win in wins]
+    npools = [float(Cc * (win[2] // k) * (win[3] // k)) for win, k in zip(wins, ks)]
+    tiles, lps, gps = [None] * nw, [None] * nw, [None] * nw
+    want = [bool(gb is not None and need[i]) for i in range(nw)]
+    if image_space:
+        aps = [torch.empty((B, Cc, win[2] // k, win[3] // k), dtype=torch.float32, device=dev) for win, k in zip(wins, ks)]
+        bps = [torch.empty_like(t) for t in aps]
+        srcs = (C.c_void_p * (2 * nw))(*([a.data_ptr()] * nw + [b.data_ptr()] * nw))
+        dsts = (C.c_void_p * (2 * nw))(*([t.data_ptr() for t in aps] + [t.data_ptr() for t in bps]))
+        w2 = (C.c_int * (8 * nw))(*([int(v) for win in wins for v in win] * 2))
+        k2 = (C.c_int * (2 * nw))(*(ks * 2))
+        check(L.dge_crop_pool_multi(srcs, dsts, w2, k2, 2 * nw, B * Cc, H, W, _stream()), "dge_crop_pool_multi")
+        main, side = _window_streams(dev, lpips_model, nw, B * H * W)       # the windows' LPIPS launches fork as in _space_loss_windows3
+        for i in range(nw):
+            ap, bp = aps[i], bps[i]
+            hp, wp = ap.shape[2], ap.shape[3]
+            strm = side[i - 1] if (side and i > 0) else None
+            if strm is not None:
+                strm.wait_stream(main)
+            with (torch.cuda.stream(strm) if strm is not None else contextlib.nullcontext()):
+                dmap = torch.empty((3, B, Cc, hp, wp), dtype=torch.float32, device=dev) if want[i] else None
+                tiles[i] = torch.empty((B, Cc * ((hp + 15) // 16) * ((wp + 15) // 16)), dtype=torch.float32, device=dev)
+                check(L.dge_ssim_fwd_rows(_p(ap), _p(bp), _p(tiles[i]), _p(dmap), B * Cc, hp, wp, _stream()), "dge_ssim_fwd_rows")
+                ops.log_kernel()
+                g_lp = None
+                if lpips_model is not None:
+                    lps[i], g_lp = lpips_model.value_and_grad(ap, bp, need_grad=want[i], per_sample=True)
+                if want[i]:
+                    gps[i] = torch.empty_like(bp)
+                    check(L.dge_ssim_bwd(_p(ap), _p(bp), _p(dmap), _p(gps[i]), B * Cc, hp, wp, -1.0 / npools[i], 0, _stream()), "dge_ssim_bwd")
+                    if g_lp is not None:      # g_lp = d mean_b lpips / db = (1/B) d lpips[sample] / db; the loss holds 2 * lpips[sample]
+                        check(L.dge_axpy_scalar(_p(g_lp), None, _p(gps[i]), g_lp.numel(), 2.0 * B, 1, _stream()), "dge_axpy_scalar")
+            if strm is not None:            # results allocated on the side stream are read (and freed) under the caller's stream
+                for t in (dmap, tiles[i], lps[i], g_lp, gps[i]):
+                    if t is not None:
+                        t.record_stream(main)
+        for strm in side:
+            main.wait_stream(strm)
+        if lpips_model is not None:
+            lpips_model._streams_warm = True
+    ptrs = lambda ts: (C.c_void_p * nw)(*[(t.data_ptr() if t is not None else None) for t in ts])
+    sums7 = torch.empty((B, nw, 8), dtype=torch.float32, device=dev)
+    out8 = torch.empty((B, nw, 8), dtype=torch.float32, device=dev)
+    cnt = (C.c_int * nw)(*[(t.shape[1] if t is not None else 0) for t in tiles])
+    nn, pp = (C.c_float * nw)(*ns), (C.c_float * nw)(*npools)
+    check(L.dge_space_loss_finalize_rows(_p(part), nblk, ptrs(tiles) if image_space else None, cnt if image_space else None,
+                                         ptrs(lps) if image_space else None, _p(sums7), _p(out8), B, nw, nn, pp, 1 if image_space else 0,
+                                         _stream()), "dge_space_loss_finalize_rows")
+    ops.log_kernel()
+    kk = (C.c_int * nw)(*ks)
+    if gb is not None:
+        ww = (C.c_float * nw)(*[float(weights[i]) if want[i] else 0.0 for i in range(nw)])
+        check(L.dge_space_loss_bwd_rows(_f32(a), _f32(b), _p(sums7), ptrs(gps) if image_space else None, _p(gb), B, Cc, H, W, wflat, kk,
+                                        nn, ww, nw, 0, _stream()), "dge_space_loss_bwd_rows")
+        ops.log_kernel()
+    if ga is not None:
+        ww = (C.c_float * nw)(*[float(weights[i]) for i in range(nw)])
+        check(L.dge_space_loss_bwd_rows(_f32(b), _f32(a), _p(sums7), None, _p(ga), B, Cc, H, W, wflat, kk, nn, ww, nw, 1, _stream()),
+              "dge_space_loss_bwd_rows")
+        ops.log_kernel()
+    return out8
+
+
+def _no_global_batch(global_batch, what):
+    if global_batch is not None:
+        raise ValueError(f"{what} is not offered with global_batch: the samples of a data-parallel batch are independent already")
+
+
+def image_loss_tsa_rows(imgs1, imgs2, lpips_model=None, weights=(1.0, 5.0, 9.0), grad_windows=(True, True, True), global_batch=None):
+    """image_loss_tsa with every sample a loss of its own: loss_b is image_loss_tsa(imgs1[b:b+1], imgs2[b:b+1], ...).  Returns
+    (sum_b loss_b on device, carrying the analytic gradient - row b of it is d loss_b / d imgs2[b] -, info [B,3,8] on device: per
+    sample the rows and columns of image_loss_tsa's info).  The same kernels and bits in both reduction modes.  No host
+    synchronisation."""
+    _no_global_batch(global_batch, "image_loss_tsa_rows")
+    a = imgs1.detach().float().contiguous()
+    b = imgs2.detach().float().contiguous()
+    need = imgs2.requires_grad and torch.is_grad_enabled()
+    wins = attention_windows(a.shape[2], a.shape[3])
+    g = torch.empty_like(b) if need else None
+    info = _space_loss_rows(a, b, wins, True, lpips_model, weights, [bool(need and grad_windows[i]) for i in range(3)], gb=g)
+    loss = (info[:, 0, 0] * float(weights[0]) + info[:, 1, 0] * float(weights[1]) + info[:, 2, 0] * float(weights[2])).sum()
+    if need:
+        loss = _ScaledGrad.apply(imgs2, loss, g)
+    return loss, info
+
+
+def space_loss_rows(imgs1, imgs2, image_space=False, global_batch=None):
+    """space_loss on latents with every sample a loss of its own: loss_b is space_loss(imgs1[b:b+1], imgs2[b:b+1],
+    image_space=False) - one row is its own cosine vector and its own softmax group, whatever its rank.  Returns (sum_b loss_b on
+    device with the analytic gradient of both arguments attached where they carry one, info [B,8]).  No host synchronisation."""
+    _no_global_batch(global_batch, "space_loss_rows")
+    if image_space:
+        raise ValueError("space_loss_rows: latents only (images go through image_loss_tsa_rows)")
+    a = imgs1.detach().float().contiguous()
+    b = imgs2.detach().float().contiguous()
+    Bt = a.shape[0]
+    n_in = a.numel() // Bt
+    grad = torch.is_grad_enabled()
+    need_a, need_b = imgs1.requires_grad and grad, imgs2.requires_grad and grad
+    ga = torch.empty_like(a) if need_a else None
+    gb = torch.empty_like(b) if need_b else None
+    view = lambda t: t.view(Bt, 1, 1, n_in) if t is not None else None
+    info = _space_loss_rows(view(a), view(b), [(0, 0, 1, n_in)], False, None, [1.0], [True], ga=view(ga), gb=view(gb))[:, 0]
+    loss = info[:, 0].sum()
+    if need_a:
+        loss = _ScaledGrad2.apply(imgs1, imgs2, loss, ga, gb if need_b else torch.zeros_like(b))
+    elif need_b:
+        loss = _ScaledGrad.apply(imgs2, loss, gb)
+    return loss, info
+

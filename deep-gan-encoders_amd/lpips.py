@@ -144,9 +144,10 @@ class LPIPS(nn.Module):
         return hit[1], hit[2]
 
     # ---------------------------------------------------------------- forward (+ gradient w.r.t. b)
-    def value_and_grad(self, a, b, need_grad=True):
+    def value_and_grad(self, a, b, need_grad=True, per_sample=False):
         """a, b: [B,3,h,w] f32 in [-1,1].  Returns (mean over the batch of LPIPS(a,b) as a [1]
-        device tensor, d mean / d b  [B,3,h,w] f32 or None)."""
+        device tensor, d mean / d b  [B,3,h,w] f32 or None).  per_sample: the first result is LPIPS(a[i], b[i]) as a [B] device
+        tensor instead of its mean (the gradient is still d mean / d b: B times it is the gradient of the sum)."""
         dt = _dt(self.compute_dtype)
         if a.shape[1] == 1:
             # single-channel maps (the Grad-CAM masks of E_mis_align_cropping_s1.py:182): lpips' ScalingLayer broadcasts
@@ -191,8 +192,11 @@ class LPIPS(nn.Module):
             lin = getattr(self, f"lin{k}").model._modules["1"].weight.detach().reshape(-1).contiguous()
             check(L.dge_lpips_head(_p(f), _f32(lin), _p(val), _p(g1), B, fh * fw, fc, 1.0 / B, dt, _stream()), "dge_lpips_head")
             heads.append(g1)
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-        check(L.dge_mean(_p(val), _p(out), B, _stream()), "dge_mean")
+        if per_sample:
+            out = val
+        else:
+            out = torch.empty(1, dtype=torch.float32, device=dev)
+            check(L.dge_mean(_p(val), _p(out), B, _stream()), "dge_mean")
         if not need_grad:
             return out, None
         # ---- backward through VGG16 for the b half of the batch.  g_pre = gradient w.r.t. the PRE-activation of conv ci; the ReLU

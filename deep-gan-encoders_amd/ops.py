@@ -109,8 +109,11 @@ def noise_dp(rank, world):
 
 
 def noise_graph_begin(device):
-    """hipGraph mode: from now on the kernels read the seed from a device scalar that noise_seed() refreshes before each replay."""
-    NOISE.seed_dev = torch.zeros(1, dtype=torch.int64, device=device)
+    """hipGraph mode: from now on the kernels read the seed from a device scalar that noise_seed() refreshes before each replay.
+    The scalar is allocated once per device and kept: a captured graph holds its address, and a second capture in the process
+    must not free it under the first graph."""
+    if NOISE.seed_dev is None or NOISE.seed_dev.device != torch.empty(0, device=device).device:
+        NOISE.seed_dev = torch.zeros(1, dtype=torch.int64, device=device)
     NOISE.graph_base = NOISE.seed or 0
     if NOISE.seed is not None:
         noise_seed(NOISE.seed)
@@ -1351,3 +1354,53 @@ def embed_track(loss, norm, w, istate, fstate, best_loss_w, best_norm_w, events,
     check(lib().dge_embed_track(_f32(loss), _f32(norm), _f32(w.contiguous()), w.numel(), _p(istate), _f32(fstate), _f32(best_loss_w),
                                 _f32(best_norm_w), _f32(events), int(cap), int(arm_rule), int(arm_iter), float(loss_hyst),
                                 float(norm_hyst), _stream()), "dge_embed_track")
+
+
+# ---- a row per sample (LatentEmbedStep(independent=True)): row b is computed and tracked as the calls above do on w[b] alone
+def latent_pnorm_rows(w, p=2, out=None, out_l2=None):
+    """||w[b]||_p for every row of w [B, ...] -> [B]; `out_l2` (optional [B] f32) also receives ||w[b]||_2.  One workgroup per row,
+    fixed-order reduction."""
+    B = w.shape[0]
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=w.device)
+    check(lib().dge_latent_pnorm_rows_fwd(_f32(w.contiguous()), _p(out), _f32(out_l2), B, w.numel() // B, int(p), _stream()),
+          "dge_latent_pnorm_rows_fwd")
+    log_kernel()
+    return out
+
+
+def latent_l2_rows(w, out=None):
+    """||w[b]||_2 only -> [B]."""
+    B = w.shape[0]
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=w.device)
+    check(lib().dge_latent_pnorm_rows_fwd(_f32(w.contiguous()), None, _p(out), B, w.numel() // B, 2, _stream()), "dge_latent_pnorm_rows_fwd")
+    log_kernel()
+    return out
+
+
+def latent_pnorm_rows_bwd(w, norm, g, p=2, beta=1.0, gout=None):
+    """g[b] += beta * gout[b] * d||w[b]||_p/dw[b] (in place; g f32 contiguous, shape of w; norm, gout [B]); a row whose norm is 0 gets 0."""
+    B = w.shape[0]
+    check(lib().dge_latent_pnorm_rows_bwd(_f32(w.contiguous()), _f32(norm), _f32(gout), _f32(g), B, w.numel() // B, int(p), float(beta),
+                                          _stream()), "dge_latent_pnorm_rows_bwd")
+    log_kernel()
+    return g
+
+
+def embed_track_rows(loss, norm, w, istate, fstate, best_loss_w, best_norm_w, events, arm_rule, arm_iter, loss_hyst, norm_hyst):
+    """One update of B trackers (include/dge_hip.h dge_embed_track_rows): loss, norm [B], w [B, ...], istate [B,4] int32, fstate [B,2],
+    events [B,cap,4], best_* of w's shape; no host sync."""
+    if istate.dtype != torch.int32:
+        raise DgeError("embed_track_rows: istate must be int32")
+    B = w.shape[0]
+    if tuple(istate.shape) != (B, 4) or tuple(fstate.shape) != (B, 2) or events.shape[0] != B or loss.numel() != B or norm.numel() != B:
+        raise DgeError("embed_track_rows: state shapes do not match the batch")
+    for t in (loss, norm, istate, fstate, best_loss_w, best_norm_w, events):
+        if not t.is_contiguous():
+            raise DgeError("embed_track_rows: arguments must be contiguous")
+    check(lib().dge_embed_track_rows(_f32(loss), _f32(norm), _f32(w.contiguous()), B, w.numel() // B, _p(istate), _f32(fstate),
+                                     _f32(best_loss_w), _f32(best_norm_w), _f32(events), int(events.shape[1]), int(arm_rule),
+                                     int(arm_iter), float(loss_hyst), float(norm_hyst), _stream()), "dge_embed_track_rows")
+    log_kernel()
+

@@ -283,6 +283,27 @@ int dge_space_loss_bwd3(const float* a, const float* b, const float* const* sums
 int dge_space_loss_bwd_split(const float* a, const float* b, const float* const* sums7, const float* const* g_pooled, float* const* g,
                              int BC, int H, int W, const int* wins, const int* ks, const float* n, const float* weight, int nwin,
                              dge_stream_t stream);
+/* Per-sample forms of the four calls above: every sample b of the batch gets the loss the calls above return on a[b:b+1],
+ * b[b:b+1] (B independent inversions in one batch, dge_amd.embedding_v2 `independent`).  No atomics and no pre-zeroed buffer:
+ * every workgroup stores its partial sums to a slot of its own and the finaliser adds a sample's slots in a fixed order, so the
+ * results carry the same bits in both reduction modes.
+ *   dge_loss_reduce_rows: partials [B][nwin][nblk][8] (all WRITTEN) over workgroup grid (nblk, B); the 16-byte form for C == 3,
+ *     W % 4 == 0 and an aligned window 0 (dge_last_kernel "loss_reduce_rows_c3v4"), else "loss_reduce_rows".
+ *   dge_ssim_fwd_rows: dge_ssim_fwd's map and dmap; tile_sums [BC][ceil(h/16)*ceil(w/16)] (all WRITTEN) holds each tile's sum.
+ *   dge_space_loss_finalize_rows: workgroup grid (nwin, B); sums7 [B][nwin][8] (for dge_space_loss_bwd_rows) and out8 [B][nwin][8]
+ *     (layout of dge_space_loss_finalize's out8) from the partials, ssim_tiles[k] [B][ssim_cnt[k]] and lpips_val[k] [B] (the
+ *     per-sample LPIPS values; the array or an entry may be NULL); n[k], n_pooled[k] count the elements of ONE sample.
+ *   dge_space_loss_bwd_rows: dge_space_loss_bwd3 reading the sums of the sample a plane belongs to; g over window 0 is WRITTEN.
+ *     swap_ab != 0: the images are passed as (b, a) and g receives the gradient with respect to the first argument. */
+int dge_loss_reduce_rows(const float* a, const float* b, float* partials, int B, int C, int H, int W, const int* wins, int nwin, int nblk,
+                         dge_stream_t stream);
+int dge_ssim_fwd_rows(const float* a, const float* b, float* tile_sums, float* dmap, int BC, int h, int w, dge_stream_t stream);
+int dge_space_loss_finalize_rows(const float* partials, int nblk, const float* const* ssim_tiles, const int* ssim_cnt,
+                                 const float* const* lpips_val, float* sums7, float* out8, int B, int nwin, const float* n,
+                                 const float* n_pooled, int image_space, dge_stream_t stream);
+int dge_space_loss_bwd_rows(const float* a, const float* b, const float* sums7, const float* const* g_pooled, float* g, int B, int C,
+                            int H, int W, const int* wins, const int* ks, const float* n, const float* weight, int nwin, int swap_ab,
+                            dge_stream_t stream);
 /* y (+)= x * scalar[0] * extra  (scalar may be NULL) */
 int dge_axpy_scalar(const float* x, const float* scalar, float* y, long n, float extra, int accumulate, dge_stream_t stream);
 
@@ -644,6 +665,14 @@ int dge_wplus_lerp_bwd(const float* g, float psi, float* gw, long n, int accumul
 int dge_embed_track(const float* loss, const float* norm, const float* w, long n, int* istate, float* fstate, float* best_loss_w,
                     float* best_norm_w, float* events, int cap, int arm_rule, int arm_iter, float loss_hyst, float norm_hyst,
                     dge_stream_t stream);
+/* The three calls above with a row per sample (w [B][n]; out, out_l2, norm, gout, loss [B]; istate [B][4], fstate [B][2],
+ * events [B][cap][4], best_*_w [B][n]): row b is computed and tracked as the whole-tensor call does on w[b] alone. */
+int dge_latent_pnorm_rows_fwd(const float* w, float* out, float* out_l2, int B, long n, int p, dge_stream_t stream);
+int dge_latent_pnorm_rows_bwd(const float* w, const float* norm, const float* gout, float* g, int B, long n, int p, float beta,
+                              dge_stream_t stream);
+int dge_embed_track_rows(const float* loss, const float* norm, const float* w, int B, long n, int* istate, float* fstate,
+                         float* best_loss_w, float* best_norm_w, float* events, int cap, int arm_rule, int arm_iter, float loss_hyst,
+                         float norm_hyst, dge_stream_t stream);
 
 /* ---- Z-space encoder training (e_align_z.py; reference ablation_utils/1.E_align_z.py) --------------------------------------- */
 /* Data gradient of the StyleGAN1 mapping network, w+ = lerp(avg, broadcast_L(chain(pixel_norm(z))), coefs):
