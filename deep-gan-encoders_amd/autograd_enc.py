@@ -2,86 +2,15 @@
 (PyTorch only routes the gradient tensors; every kernel is in libdge_hip.so)."""
 import torch
 
-from . import ops
+from . import autograd_enc_bwd, ops
+from .enc_steps import BE_W_ROWS, blocks, conv_fwd, draw_noises, head_list, heads_forward, heads_table, slot_view
 from .stylegan2_generator import _dt
 from .weight_cache import pack_cache, packed
 
 
-def draw_noises(E, B, R, device):
-    """The encoder's per-layer noise tensors ([B,1,r,r], two per block, one for the last): one generator launch for all of
-    them, handed out as contiguous slices (the reference draws 17 separate CPU tensors, model/E/E.py:60,73 - quirk Q6).  Under
-    data parallelism each tensor is the rank's slice of the draw a single process would make for the global batch."""
-    shapes = []
-    for j in range(E.layer_count):
-        r = R >> j
-        shapes.append((B, 1, r, r))
-        if j != E.layer_count - 1:
-            shapes.append((B, 1, r, r))
-    if torch.device(device).type == "cpu":        # reference_noise mode: the reference's own sequence of CPU draws
-        return [torch.randn(*s) for s in shapes]
-    return ops.randn_rows(shapes, device)       # counter-based: the rank's rows of the global-batch draw (csrc/rng_kernels.hip)
-
-
 def heads_layout(E, B, dev):
-    """Static layout of the encoder's `inver_mod` heads for the grouped backward (dge_heads_bwd): entry order = (inver_mod1,
-    inver_mod2) per block; statistics / their gradients in one flat buffer, parameter gradients in another; the device-side
-    table holds the weight pointers (parameter storage does not move) and the column of each head in w (E.py:130-134).
-    One layout per (batch size, device), kept while the parameters stay where they are: a captured graph holds the address of its
-    table, and a call at another batch size on the same encoder must not free it under that graph."""
-    import numpy as np
-    lins = []
-    L = E.layer_count
-    for j, blk in enumerate(E.decode_block):
-        lins.append((blk.inver_mod1, 2 * (L - 1 - j) + 1))
-        lins.append((blk.inver_mod2, 2 * (L - 1 - j)))
-    key = (B, str(dev), tuple((l.weight.data_ptr(), l.bias.data_ptr()) for l, _ in lins))
-    cache = E.__dict__.setdefault("_heads_layout", {})
-    lay = cache.get(key[:2])
-    if lay is not None and lay["key"] == key:
-        return lay
-    O = lins[0][0].weight.shape[0]
-    rec = np.dtype([("W", "u8"), ("moff", "i8"), ("woff", "i8"), ("I", "i4"), ("gcol", "i4"), ("boff", "i4"), ("pad", "i4"), ("bias", "u8")])
-    assert rec.itemsize == ops.lib().dge_head_entry_size()
-    tab = np.zeros(len(lins), dtype=rec)
-    moff = woff = 0
-    items = []
-    for i, (lin, col) in enumerate(lins):
-        I = lin.weight.shape[1]
-        assert lin.weight.shape[0] == O and lin.weight.is_contiguous()
-        tab[i] = (lin.weight.data_ptr(), moff, woff, I, col * O, i * O, 0, lin.bias.data_ptr())
-        items.append((moff, woff, i * O, I))
-        moff += B * I
-        woff += O * I
-    lay = dict(key=key, tab=torch.from_numpy(tab.view(np.uint8).copy()).to(dev), items=items, n=len(lins), O=O, total_m=moff,
-               total_w=woff, max_I=max(it[3] for it in items))
-    cache[key[:2]] = lay
-    return lay
-
-
-# ------------------------------------------------------------------ tails shared by the hand-written backwards of the family
-def linear_backward(lin, gy, x, grads, name, params=True):
-    """Backward of the dense layer y = x @ W^T + b: returns g_x [B, I] (ops.linear_t); with `params`, the weight / bias gradients
-    (ops.dense_wgrad) go into grads[name + ".weight" / ".bias"].  params=False: the data gradient alone (frozen encoder)."""
-    W = lin.weight.detach()
-    gx = torch.empty((gy.shape[0], W.shape[1]), dtype=torch.float32, device=gy.device)
-    ops.linear_t(gy, W, gx)
-    if params:
-        gw, gb = torch.empty_like(W), torch.empty_like(lin.bias)
-        ops.dense_wgrad(gy, x, gw, gb)
-        grads[name + ".weight"], grads[name + ".bias"] = gw, gb
-    return gx
-
-
-def fromrgb_param_grads(E, saved, g_out, grads):
-    """FromRGB parameter gradients from the gradient of its output (ops.fromrgb_bwd, [C, 4] form)."""
-    fr = ops.fromrgb_bwd(g_out, saved["x0"], saved["img"].float())
-    grads["FromRGB.from_rgb.weight"] = fr[:, :3].reshape(E.startf, 3, 1, 1)
-    grads["FromRGB.from_rgb.bias"] = fr[:, 3]
-
-
-def grads_in_order(E, grads):
-    """`grads` (by parameter name) in E.named_parameters() order: contiguous, or None where there is no gradient."""
-    return [g.contiguous() if g is not None else None for g in (grads.get(name) for name, _ in E.named_parameters())]
+    """The one-column table of E.BE's heads (enc_steps.heads_table), one per (batch size, device)."""
+    return heads_table(E, head_list(E, BE_W_ROWS), B, dev, rows=False)
 
 
 def encoder_forward(E, img, noises=None, save=False):
@@ -102,28 +31,17 @@ def encoder_forward(E, img, noises=None, save=False):
     img4 = None
     if want4:
         x, img4 = x
-    saved = {"img": img, "x0": x, "blocks": [], "img4": img4} if save else None
-    ws, ni = [], 0
-    L = E.layer_count
     lay = heads_layout(E, B, dev)
     musig_all = torch.empty(lay["total_m"], dtype=torch.float32, device=dev)     # all (mean, std) vectors, flat: grouped backward
-    if save:
-        saved["musig_all"] = musig_all
-
-    def ms_slot(i):
-        moff, _, _, I = lay["items"][i]
-        return musig_all[moff:moff + B * I].view(B, I)
-    for j, blk in enumerate(E.decode_block):
-        Cc, C2 = blk.inputs, blk.outputs
-        H = R >> j
+    saved = {"img": img, "x0": x, "blocks": [], "img4": img4, "heads": lay, "musig_all": musig_all} if save else None
+    ni = 0
+    for j, blk, _, _, Cc, C2, H, N in blocks(E, R):
         last = not blk.has_last_conv
-        musig1, sc1, sh1 = ops.stats_finalize(stats, H * H, musig_out=ms_slot(2 * j))
+        musig1, sc1, sh1 = ops.stats_finalize(stats, N, musig_out=slot_view(lay, musig_all, 2 * j, B))
         n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
         st1 = zeros(Cc)
-        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
-                        noise_w=blk.noise_weight_1.detach().reshape(-1), bias=blk.bias_1.detach().reshape(-1),
-                        act=ops.ACT_LRELU, stats=st1)
-        musig2, sc2, sh2 = ops.stats_finalize(st1, H * H, musig_out=ms_slot(2 * j + 1))
+        x1 = conv_fwd(cache, blk, 1, x, Cc, dt, H, sc1, sh1, n1, stats=st1)
+        musig2, sc2, sh2 = ops.stats_finalize(st1, N, musig_out=slot_view(lay, musig_all, 2 * j + 1, B))
         rec = dict(x=x, musig1=musig1, sc1=sc1, sh1=sh1, n1=n1, x1=x1, musig2=musig2, sc2=sc2, sh2=sh2) if save else None
         has3 = Cc != C2
         nstats = zeros(C2) if not last else None
@@ -167,9 +85,7 @@ def encoder_forward(E, img, noises=None, save=False):
         x, stats = out, nstats
     # every inver_mod head (w_l = musig_l @ W_l^T + b_l, E.py:51-53,64-66) in one launch: none of them feeds the trunk; column order
     # of w per E.py:130-134 (later / deeper blocks first) comes from the table
-    w = torch.empty((B, 2 * L, lay["O"]), dtype=torch.float32, device=dev)
-    ops.check(ops.lib().dge_heads_fwd(ops._p(lay["tab"]), lay["n"], ops._f32(musig_all), ops._p(w), w.stride(0), B, lay["O"],
-                                      ops._stream()), "dge_heads_fwd")
+    w = heads_forward(lay, musig_all, torch.empty((B, 2 * E.layer_count, lay["O"]), dtype=torch.float32, device=dev))
     return ops.nhwc_to_nchw(x), w, saved
 
 
@@ -188,12 +104,11 @@ class EncoderFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_x, g_w):
-        from .autograd_enc_bwd import encoder_backward
         if g_x is not None:
             # a loss on the const output (space_loss(const2, const3) in embedding_v2_styleGAN2.py): refuse instead of dropping it
             raise ops.DgeError("E.BE: a gradient arrived through the encoder's activation output, which the hand-written backward "
                                "does not propagate (the E_align losses use w only, E_align_s2.py:203-221); detach it")
         if g_w is None:
             return (None, None, None) + (None,) * len(ctx.needs_input_grad[3:])
-        grads = encoder_backward(ctx.E, ctx.saved_acts, g_w.contiguous())
+        grads = autograd_enc_bwd.encoder_backward(ctx.E, ctx.saved_acts, g_w.contiguous())
         return (None, None, None) + tuple(grads)

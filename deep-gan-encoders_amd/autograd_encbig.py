@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import ops
-from .autograd_enc import draw_noises, fromrgb_param_grads, grads_in_order, linear_backward
+from .enc_steps import blocks, conv_bwd, conv_fwd, draw_noises, fromrgb_param_grads, grads_in_order, linear_backward, red_param_grads
 from .biggan_generator import sn_weight_grad, sn_prepare, sn_cbn_linears
 from .stylegan2_generator import _dt
 from .weight_cache import pack_cache, packed
@@ -39,13 +39,11 @@ def big_encoder_forward(E, img, cond_vector, noises=None, save=False, truncation
     x = ops.fromrgb(img.float(), fr.weight.detach(), fr.bias.detach(), dt, None)
     saved = {"img": img, "x0": x, "cond": cond, "blocks": []} if save else None
     ni = 0
-    for j, blk in enumerate(E.decode_block):
-        Cc, C2, H = blk.inputs, blk.outputs, R >> j
+    for j, blk, _, _, Cc, C2, H, _ in blocks(E, R):
         c1 = {} if save else None
         a1, b1 = blk.batch_norm_1.affine(truncation, cond, training, c1)
         n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=a1, in_shift=b1, noise=n1,
-                        noise_w=blk.noise_weight_1.detach().reshape(-1), bias=blk.bias_1.detach().reshape(-1), act=ops.ACT_LRELU)
+        x1 = conv_fwd(cache, blk, 1, x, Cc, dt, H, a1, b1, n1)
         rec = dict(x=x, a1=a1, b1=b1, c1=c1, n1=n1, x1=x1) if save else None
         if not blk.has_second_conv:
             if save:
@@ -55,8 +53,7 @@ def big_encoder_forward(E, img, cond_vector, noises=None, save=False, truncation
         c2 = {} if save else None
         a2, b2 = blk.batch_norm_2.affine(truncation, cond, training, c2)
         n2 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        x2 = ops.conv2d(x1, packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, in_scale=a2, in_shift=b2, noise=n2,
-                        noise_w=blk.noise_weight_2.detach().reshape(-1), bias=blk.bias_2.detach().reshape(-1), act=ops.ACT_LRELU)
+        x2 = conv_fwd(cache, blk, 2, x1, C2, dt, H, a2, b2, n2)
         xp = ops.blend(x, pool=True)                                  # avg_pool2d of the block input (residual branch)
         if Cc != C2:
             c3 = {} if save else None
@@ -183,11 +180,7 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
     L = len(saved["blocks"])
     C_last = E.decode_block[L - 1].inputs
     g_out = ops.nchw_to_nhwc(g_flat.view(B, C_last, R >> (L - 1), R >> (L - 1)), B, dt)
-    for j in range(L - 1, -1, -1):
-        blk, rec = E.decode_block[j], saved["blocks"][j]
-        pre = f"decode_block.{j}."
-        Cc, C2 = blk.inputs, blk.outputs
-        H = R >> j
+    for j, blk, rec, pre, Cc, C2, H, _ in blocks(E, R, saved):
         x, x1 = rec["x"], rec["x1"]
         red1 = ops.zeros((Cc, 2), dev)
         extra, extra_pool, extra_scale = None, False, 1.0
@@ -196,23 +189,14 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
             red2 = ops.zeros((C2, 2), dev)
             # x2 = lrelu(pre2) [then a second lrelu when has3: slope 0.2*0.2 on the negative side]; out = avg_pool(x2 + res)
             g_pre2 = ops.act_bwd(g_out, rec["x2"], rec["n2"], pool=True, scale=0.25, red=red2, slope=0.04 if has3 else 0.2)
-            grads[pre + "bias_2"] = red2[:, 0].reshape(1, C2, 1, 1)
-            grads[pre + "noise_weight_2"] = red2[:, 1].reshape(1, C2, 1, 1)
-            gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
-            ops.conv_wgrad(g_pre2, x1, gW2, rec["a2"], rec["b2"])
-            grads[pre + "conv_2.weight"] = gW2
-            dots2 = ops.zeros((B, Cc, 2), dev)
-            g_u2 = ops.conv2d(g_pre2, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
+            red_param_grads(grads, pre, 2, red2)
+            g_u2, dots2 = conv_bwd(cache, grads, pre + "conv_2", blk.conv_2, g_pre2, x1, dt, H, rec["a2"], rec["b2"])
             _cbn_param_grads(blk.batch_norm_2, rec["c2"], dots2, cond, grads, pre + "batch_norm_2", pend)
             g_pre1 = ops.in_bwd(g_u2, x1, _affine_coef(rec["a2"]), noise=rec["n1"], act=True, red=red1)
             if has3:
                 xp = rec["xp"]
                 grads[pre + "conv_3.bias"] = ops.chan_sum(g_out)
-                gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
-                ops.conv_wgrad(g_out, xp, gW3, rec["a3"], rec["b3"])
-                grads[pre + "conv_3.weight"] = gW3
-                dots3 = ops.zeros((B, Cc, 2), dev)
-                g_u3 = ops.conv2d(g_out, packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, stats=dots3, dot_src=xp)
+                g_u3, dots3 = conv_bwd(cache, grads, pre + "conv_3", blk.conv_3, g_out, xp, dt, None, rec["a3"], rec["b3"])
                 _cbn_param_grads(blk.batch_norm_3, rec["c3"], dots3, cond, grads, pre + "batch_norm_3", pend)
                 extra = ops.in_bwd(g_u3, xp, _affine_coef(rec["a3"]))          # a3 * g at the pooled resolution
             else:
@@ -220,13 +204,8 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
             extra_pool, extra_scale = True, 0.25
         else:
             g_pre1 = ops.act_bwd(g_out, x1, rec["n1"], pool=False, scale=1.0, red=red1)
-        grads[pre + "bias_1"] = red1[:, 0].reshape(1, Cc, 1, 1)
-        grads[pre + "noise_weight_1"] = red1[:, 1].reshape(1, Cc, 1, 1)
-        gW1 = ops.zeros(tuple(blk.conv_1.weight.shape), dev)
-        ops.conv_wgrad(g_pre1, x, gW1, rec["a1"], rec["b1"])
-        grads[pre + "conv_1.weight"] = gW1
-        dots1 = ops.zeros((B, Cc, 2), dev)
-        g_u1 = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
+        red_param_grads(grads, pre, 1, red1)
+        g_u1, dots1 = conv_bwd(cache, grads, pre + "conv_1", blk.conv_1, g_pre1, x, dt, H, rec["a1"], rec["b1"])
         _cbn_param_grads(blk.batch_norm_1, rec["c1"], dots1, cond, grads, pre + "batch_norm_1", pend)
         g_out = ops.in_bwd(g_u1, x, _affine_coef(rec["a1"]), extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
     _cbn_param_grads_flush(pend, cond, grads)

@@ -10,12 +10,17 @@ Block forward (not last): IN1 -> conv_1 +noise+bias -> lrelu (x1) -> IN2 -> blur
   else: conv3x3 +noise+bias -> lrelu -> avg_pool.
 out = 0.111*x2 + 0.889*(conv_3)(avg_pool(x)).  Last block: out = 0.111*IN2(x1) + 0.889*x.
 """
+import os
+
 import torch
 
 from . import ops
-from .autograd_enc import draw_noises, fromrgb_param_grads, grads_in_order, linear_backward
+from .enc_steps import (blocks, conv_bwd, conv_fwd, draw_noises, fromrgb_param_grads, grads_in_order, head_list, heads_backward,
+                        heads_forward, heads_table, linear_backward, red_param_grads, skip_bwd, slot_view)
 from .stylegan2_generator import _dt
 from .weight_cache import pack_cache, packed, version
+
+_DIRECT_ACCUMULATE = os.environ.get("DGE_AUTOGRAD_ACCUMULATE") != "1"
 
 
 def blur_noises(E, B, R, dev):
@@ -33,46 +38,9 @@ def blur_noises(E, B, R, dev):
 
 
 def heads_rows_layout(E, B, dev):
-    """Static layout of the heads of an encoder that declares `w_rows` (E_Blur_W, E_Blur_W_2) for the grouped launches
-    dge_heads_rows_fwd / dge_heads_rows_bwd, built once per encoder and cached like autograd_enc.heads_layout.  The (mean, std)
-    vectors of all blocks live in one flat buffer, slot 2j = block j's musig1, slot 2j + 1 = musig2; the statistics gradients use
-    the same offsets.  One table entry per head that feeds W+: weight / bias pointers (parameter storage does not move), I, its
-    slot offset, the offset of its weight / bias gradient in flat buffers, and its one or two rows of w [B, 2L, O]: block j owns
-    rows 2(L-1-j) and 2(L-1-j)+1 (later blocks first, E_Blur_W.py:130-134), `w_rows` gives the row(s) inside that pair.
-    One layout per (batch size, device), as autograd_enc.heads_layout keeps them (captured graphs hold the table's address)."""
-    import numpy as np
-    L = E.layer_count
-    heads = []                 # (state_dict prefix, module, slot, rows)
-    for j, blk in enumerate(E.decode_block):
-        for name, slot in (("inver_mod1", 2 * j), ("inver_mod2", 2 * j + 1)):
-            rows = E.w_rows.get(name)
-            if rows:
-                heads.append((f"decode_block.{j}.{name}", getattr(blk, name), slot, [2 * (L - 1 - j) + r for r in rows]))
-    key = (B, str(dev), tuple((h[1].weight.data_ptr(), h[1].bias.data_ptr()) for h in heads))
-    cache = E.__dict__.setdefault("_heads_rows_layout", {})
-    lay = cache.get(key[:2])
-    if lay is not None and lay["key"] == key:
-        return lay
-    slots, moff = [], 0
-    for blk in E.decode_block:
-        for _ in range(2):
-            slots.append((moff, 2 * blk.inputs)); moff += B * 2 * blk.inputs
-    O = heads[0][1].weight.shape[0]
-    rec = np.dtype([("W", "u8"), ("bias", "u8"), ("moff", "i8"), ("woff", "i8"), ("I", "i4"), ("row_a", "i4"), ("row_b", "i4"), ("boff", "i4")])
-    assert rec.itemsize == ops.lib().dge_head_rows_entry_size()
-    tab = np.zeros(len(heads), dtype=rec)
-    woff, items = 0, []
-    for i, (name, lin, slot, rows) in enumerate(heads):
-        so, I = slots[slot]
-        if tuple(lin.weight.shape) != (O, I) or not lin.weight.is_contiguous() or not 1 <= len(rows) <= 2 or max(rows) >= 2 * L:
-            raise ops.DgeError(f"heads_rows_layout: head {name} does not fit the table (weight {tuple(lin.weight.shape)}, rows {rows})")
-        tab[i] = (lin.weight.data_ptr(), lin.bias.data_ptr(), so, woff, I, rows[0], rows[1] if len(rows) == 2 else -1, i * O)
-        items.append((name, slot, woff, i * O, I))
-        woff += O * I
-    lay = dict(key=key, tab=torch.from_numpy(tab.view(np.uint8).copy()).to(dev), items=items, slots=slots, n=len(heads), O=O, total_m=moff,
-               total_w=woff, max_I=max(it[4] for it in items), by_slot={it[1] for it in items})
-    cache[key[:2]] = lay
-    return lay
+    """The row-list table of the heads of an encoder that declares `w_rows` (E_Blur_W, E_Blur_W_2; enc_steps.heads_table), one per
+    (batch size, device).  A head without rows (inver_mod1 of E_Blur_W_2) has no entry."""
+    return heads_table(E, head_list(E, E.w_rows), B, dev, rows=True)
 
 
 def blur_encoder_forward(E, img, noises=None, save=False):
@@ -84,12 +52,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
     # buffer of the blocks' (mean, std) vectors, and write their rows of w directly
     lay = heads_rows_layout(E, B, dev) if getattr(E, "w_rows", None) else None
     musig_all = torch.empty(lay["total_m"], dtype=torch.float32, device=dev) if lay else None
-
-    def ms_slot(i):
-        if lay is None:
-            return None
-        so, I = lay["slots"][i]
-        return musig_all[so:so + B * I].view(B, I)
+    ms_slot = lambda i: slot_view(lay, musig_all, i, B) if lay else None
     if lay:
         heads = False          # (the per-head launches below are BlurBE's)
     if noises is None and noise:
@@ -99,42 +62,34 @@ def blur_encoder_forward(E, img, noises=None, save=False):
     fr = E.FromRGB.from_rgb
     stats = zeros(E.startf)
     x = ops.fromrgb(img.float(), fr.weight.detach(), fr.bias.detach(), dt, stats)
-    saved = {"img": img, "x0": x, "blocks": [], "musig_all": musig_all} if save else None
+    saved = {"img": img, "x0": x, "blocks": [], "heads": lay, "musig_all": musig_all} if save else None
     ws, ni = [], 0
-    for j, blk in enumerate(E.decode_block):
-        Cc, C2, H = blk.inputs, blk.outputs, R >> j
+    for j, blk, _, _, Cc, C2, H, N in blocks(E, R):
         last = not blk.has_last_conv
         has3 = Cc != C2
-        musig1, sc1, sh1 = ops.stats_finalize(stats, H * H, musig_out=ms_slot(2 * j))
+        musig1, sc1, sh1 = ops.stats_finalize(stats, N, musig_out=ms_slot(2 * j))
         w1 = ops.linear(musig1, blk.inver_mod1.weight.detach(), blk.inver_mod1.bias.detach()) if heads else None
-        n1 = nw1 = None
+        n1 = None
         if noise:
             n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-            nw1 = blk.noise_weight_1.detach().reshape(-1)
         st1 = zeros(Cc)
-        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
-                        noise_w=nw1, bias=blk.bias_1.detach().reshape(-1), act=ops.ACT_LRELU, stats=st1)
-        musig2, sc2, sh2 = ops.stats_finalize(st1, H * H, musig_out=ms_slot(2 * j + 1))
+        x1 = conv_fwd(cache, blk, 1, x, Cc, dt, H, sc1, sh1, n1, stats=st1)
+        musig2, sc2, sh2 = ops.stats_finalize(st1, N, musig_out=ms_slot(2 * j + 1))
         w2 = ops.linear(musig2, blk.inver_mod2.weight.detach(), blk.inver_mod2.bias.detach()) if heads else None
         rec = dict(x=x, musig1=musig1, sc1=sc1, sh1=sh1, n1=n1, x1=x1, musig2=musig2, sc2=sc2, sh2=sh2) if save else None
         nstats = zeros(C2) if not last else None
         if not last:
             y2 = ops.blur_noise_act(ops.blend(x1, sc=sc2, sh=sh2), None, None, None, blur=True, act=False)   # blur(IN2(x1))
-            wpk = packed(cache, blk.conv_2, dt, ops.PACK_FWD, H)
-            n2 = nw2 = None
+            n2 = None
             if noise:
-                n2 = noises[ni]; ni += 1
-                nw2 = blk.noise_weight_2.detach().reshape(-1)
-            b2 = blk.bias_2.detach().reshape(-1)
+                r2 = H // 2 if blk.fused_scale else H
+                n2 = noises[ni].reshape(B, r2, r2).contiguous(); ni += 1
             if blk.fused_scale:        # conv(s2, transform_kernel) == pool(conv); noise/bias/lrelu at half resolution
-                if noise:
-                    n2 = n2.reshape(B, H // 2, H // 2).contiguous()
-                t = ops.blend(ops.conv2d(y2, wpk, C2, 3), pool=True)
-                a2 = x2 = ops.blur_noise_act(t, n2, nw2, b2, blur=False)
+                t = ops.blend(ops.conv2d(y2, packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3), pool=True)
+                a2 = x2 = ops.blur_noise_act(t, n2, blk.noise_weight_2.detach().reshape(-1) if noise else None,
+                                             blk.bias_2.detach().reshape(-1), blur=False)
             else:
-                if noise:
-                    n2 = n2.reshape(B, H, H).contiguous()
-                a2 = ops.conv2d(y2, wpk, C2, 3, noise=n2, noise_w=nw2, bias=b2, act=ops.ACT_LRELU)
+                a2 = conv_fwd(cache, blk, 2, y2, C2, dt, H, noise=n2)
                 x2 = ops.blend(a2, pool=True)
             xp = ops.blend(x, pool=True)
             if has3:
@@ -158,8 +113,7 @@ def blur_encoder_forward(E, img, noises=None, save=False):
         ws = [w2, w1] + ws
         x, stats = out, nstats
     if lay:
-        w = torch.empty((B, 2 * E.layer_count, lay["O"]), dtype=torch.float32, device=dev)
-        ops.heads_rows_fwd(lay["tab"], lay["n"], musig_all, w)
+        w = heads_forward(lay, musig_all, torch.empty((B, 2 * E.layer_count, lay["O"]), dtype=torch.float32, device=dev))
         return ops.nhwc_to_nchw(x), w, saved
     return ops.nhwc_to_nchw(x), (torch.stack(ws, dim=1) if heads else None), saved
 
@@ -177,42 +131,19 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
     no statistics gradient and None - not zeros - for its weight and bias."""
     cache = pack_cache(E)
     noise, heads = getattr(E, "noise", True), getattr(E, "heads", True)
-    lay = heads_rows_layout(E, saved["img"].shape[0], saved["img"].device) if getattr(E, "w_rows", None) else None
+    B, _, R, _ = saved["img"].shape
     dev = saved["img"].device
     L = E.layer_count
-    B = saved["img"].shape[0]
     grads = {}
-    R = saved["img"].shape[2]
     dt = ops.dtype_of(saved["x0"])
     g_out = None
     if g_const is not None:
         g_out = ops.nchw_to_nhwc(g_const.float().contiguous(), B, dt) if g_const.shape[0] == B else None
-    gms_all = None
-    if lay:
-        gms_all = torch.empty(lay["total_m"], dtype=torch.float32, device=dev)
-        gw_all = torch.empty(lay["total_w"], dtype=torch.float32, device=dev) if params else None
-        gb_all = torch.empty(lay["n"] * lay["O"], dtype=torch.float32, device=dev) if params else None
-        ops.heads_rows_bwd(lay["tab"], lay["n"], lay["max_I"], g_w, saved["musig_all"], gms_all, gw_all, gb_all)
-        if params:
-            for name, _, woff, boff, I in lay["items"]:
-                grads[name + ".weight"] = gw_all[woff:woff + lay["O"] * I].view(lay["O"], I)
-                grads[name + ".bias"] = gb_all[boff:boff + lay["O"]]
-
-    def gms_slot(i):
-        if i not in lay["by_slot"]:
-            return None
-        so, I = lay["slots"][i]
-        return gms_all[so:so + B * I].view(B, I)
-    for j in range(L - 1, -1, -1):
-        blk = E.decode_block[j]
-        rec = saved["blocks"][j]
-        pre = f"decode_block.{j}."
-        Cc, C2 = blk.inputs, blk.outputs
-        H = R >> j
-        N = H * H
+    gms_slot = heads_backward(saved["heads"], g_w, saved["musig_all"], grads, params) if saved["heads"] else None
+    for j, blk, rec, pre, Cc, C2, H, N in blocks(E, R, saved):
         last = not blk.has_last_conv
         has3 = Cc != C2
-        if lay:
+        if gms_slot:
             gms2, gms1 = gms_slot(2 * j + 1), gms_slot(2 * j)
         elif not heads:
             gms2 = gms1 = None
@@ -231,10 +162,9 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
                 g_c2 = ops.nearest_up2(g_t, 0.25)                                                  # adjoint of the 2x2 average
             else:
                 g_c2 = ops.act_bwd(g_out, rec["a2"], rec["n2"], pool=True, scale=0.111 * 0.25, red=red2)
+            sum_g = None
             if params:
-                grads[pre + "bias_2"] = red2[:, 0].reshape(1, C2, 1, 1)
-                if noise:
-                    grads[pre + "noise_weight_2"] = red2[:, 1].reshape(1, C2, 1, 1)
+                sum_g = red_param_grads(grads, pre, 2, red2, noise=noise)
                 gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
                 ops.conv_wgrad(g_c2, rec["y2"], gW2)
                 grads[pre + "conv_2.weight"] = gW2
@@ -247,12 +177,7 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
             g_y2 = ops.blur_noise_act(g_y2b, None, None, None, blur=True, act=False)                 # Blur is self-adjoint
             dots2 = ops.dot_stats(g_y2, x1)
             if has3:
-                if params:
-                    grads[pre + "conv_3.bias"] = red2[:, 2] * 0.889
-                    gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
-                    ops.conv_wgrad(g_out, rec["xp"], gW3)
-                    grads[pre + "conv_3.weight"] = ops.scale_(gW3, 0.889)
-                extra = ops.conv2d(g_out, packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1, gain=0.889)
+                extra = skip_bwd(cache, grads, pre, blk, g_out, rec["xp"], dt, sum_g, params)
                 extra_pool, extra_scale = True, 0.25
             else:
                 extra, extra_pool, extra_scale = g_out, True, 0.889 * 0.25
@@ -267,14 +192,8 @@ def blur_encoder_backward(E, saved, g_w, g_const=None, need_img=False, params=Tr
         red1 = ops.zeros((Cc, 2), dev) if params else None
         g_pre1 = ops.in_bwd(g_y2, x1, coef2, noise=rec["n1"], act=True, red=red1)
         if params:
-            grads[pre + "bias_1"] = red1[:, 0].reshape(1, Cc, 1, 1)
-            if noise:
-                grads[pre + "noise_weight_1"] = red1[:, 1].reshape(1, Cc, 1, 1)
-            gW1 = ops.zeros(tuple(blk.conv_1.weight.shape), dev)
-            ops.conv_wgrad(g_pre1, x, gW1, rec["sc1"], rec["sh1"])
-            grads[pre + "conv_1.weight"] = gW1
-        dots1 = ops.zeros((B, Cc, 2), dev)
-        g_y1 = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
+            red_param_grads(grads, pre, 1, red1, noise=noise)
+        g_y1, dots1 = conv_bwd(cache, grads, pre + "conv_1", blk.conv_1, g_pre1, x, dt, H, rec["sc1"], rec["sh1"], params)
         coef1 = ops.in_bwd_coef(dots1, gms1, rec["musig1"], rec["sc1"], rec["sh1"], N)
         g_out = ops.in_bwd(g_y1, x, coef1, extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
     if params:
@@ -304,12 +223,7 @@ class BlurEncoderFunction(torch.autograd.Function):
         if not (getattr(ctx.E, "w_rows", None) and g_w.stride(2) == 1):      # (the grouped head backward reads strided rows)
             g_w = g_w.contiguous()
         grads, g_img = blur_encoder_backward(ctx.E, ctx.saved_acts, g_w, g_x, need_img=ctx.need_img, params=not frozen)
-        if frozen:
-            return (None, g_img, None) + (None,) * len(grads)
-        if _DIRECT_ACCUMULATE:
-            accumulate_param_grads(ctx.E, grads)
-            return (None, g_img, None) + (None,) * len(grads)
-        return (None, g_img, None) + tuple(grads)
+        return (None, g_img, None) + _param_grads_out(ctx.E, grads, frozen)
 
 
 def _out_z_window(E, xo):
@@ -355,24 +269,26 @@ class BlurZEncoderFunction(torch.autograd.Function):
         g_x[:, :, :3, :3] = g_win.view(B, Cc, 3, 3)
         frozen = not any(ctx.needs_input_grad[2:])
         grads, g_img = blur_encoder_backward(E, ctx.saved_acts, None, g_x, need_img=ctx.need_img, params=not frozen)
-        if frozen:
-            return (None, g_img) + (None,) * len(grads)
-        gW = torch.empty_like(oz.weight)
-        gb = torch.empty_like(oz.bias)
-        ops.dense_wgrad(g, win, gW.view(Wz.shape), gb)
-        for k, (name, _) in enumerate(E.named_parameters()):
-            if name == "out_z.weight":
-                grads[k] = gW
-            elif name == "out_z.bias":
-                grads[k] = gb
-        if _DIRECT_ACCUMULATE:
+        if not frozen:
+            gW = torch.empty_like(oz.weight)
+            gb = torch.empty_like(oz.bias)
+            ops.dense_wgrad(g, win, gW.view(Wz.shape), gb)
+            for k, (name, _) in enumerate(E.named_parameters()):
+                if name == "out_z.weight":
+                    grads[k] = gW
+                elif name == "out_z.bias":
+                    grads[k] = gb
+        return (None, g_img) + _param_grads_out(E, grads, frozen)
+
+
+def _param_grads_out(E, grads, frozen):
+    """What a Function.backward of the family returns for the encoder's parameters: nothing for a frozen encoder, nothing when the
+    gradients are added to `.grad` here (accumulate_param_grads, the default), else the gradients for autograd to accumulate."""
+    if frozen or _DIRECT_ACCUMULATE:
+        if not frozen:
             accumulate_param_grads(E, grads)
-            return (None, g_img) + (None,) * len(grads)
-        return (None, g_img) + tuple(grads)
-
-
-import os as _os
-_DIRECT_ACCUMULATE = _os.environ.get("DGE_AUTOGRAD_ACCUMULATE") != "1"
+        return (None,) * len(grads)
+    return tuple(grads)
 
 
 def accumulate_param_grads(E, grads):
@@ -382,7 +298,6 @@ def accumulate_param_grads(E, grads):
     of ~4 us per backward at batch 1, where the loop is paced by launches (profiles/r05_embed_kernel_stats.txt).  Here: one
     multi-tensor copy into a persistent flat buffer for the parameters without a gradient, one multi-tensor add for those with one.
     Same sums in the same order (first call, then second)."""
-    import torch
     params = list(E.parameters())
     lay = E.__dict__.get("_grad_flat")
     total = sum(p.numel() for p in params)

@@ -13,7 +13,7 @@ gradients summed over the batch are the gamma / beta gradients.
 import torch
 
 from . import ops
-from .autograd_enc import draw_noises, fromrgb_param_grads, grads_in_order, linear_backward
+from .enc_steps import blocks, conv_bwd, conv_fwd, draw_noises, fromrgb_param_grads, grads_in_order, linear_backward, red_param_grads
 from .stylegan2_generator import _dt
 from .weight_cache import pack_cache, packed
 
@@ -31,28 +31,24 @@ def pg_encoder_forward(E, img, noises=None, save=False):
     x = ops.fromrgb(img.float(), fr.weight.detach(), fr.bias.detach(), dt, stats)
     saved = {"img": img, "x0": x, "blocks": []} if save else None
     ni = 0
-    for j, blk in enumerate(E.decode_block):
-        Cc, C2, H = blk.inputs, blk.outputs, R >> j
-        musig1, sc1, sh1 = ops.stats_finalize(stats, H * H)
+    for j, blk, _, _, Cc, C2, H, N in blocks(E, R):
+        musig1, sc1, sh1 = ops.stats_finalize(stats, N)
         st1 = zeros(Cc)
         n1 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        x1 = ops.conv2d(x, packed(cache, blk.conv_1, dt, ops.PACK_FWD, H), Cc, 3, in_scale=sc1, in_shift=sh1, noise=n1,
-                        noise_w=blk.noise_weight_1.detach().reshape(-1), bias=blk.bias_1.detach().reshape(-1),
-                        act=ops.ACT_LRELU, stats=st1)
+        x1 = conv_fwd(cache, blk, 1, x, Cc, dt, H, sc1, sh1, n1, stats=st1)
         rec = dict(x=x, musig1=musig1, sc1=sc1, sh1=sh1, n1=n1, x1=x1) if save else None
         if not blk.has_second_conv:
             if save:
                 saved["blocks"].append(rec)
             x = x1
             break
-        musig2, sc2, sh2 = ops.stats_finalize(st1, H * H)
+        musig2, sc2, sh2 = ops.stats_finalize(st1, N)
         n2 = noises[ni].reshape(B, H, H).contiguous(); ni += 1
-        pre2 = ops.conv2d(x1, packed(cache, blk.conv_2, dt, ops.PACK_FWD, H), C2, 3, in_scale=sc2, in_shift=sh2, noise=n2,
-                          noise_w=blk.noise_weight_2.detach().reshape(-1), bias=blk.bias_2.detach().reshape(-1))
+        pre2 = conv_fwd(cache, blk, 2, x1, C2, dt, H, sc2, sh2, n2, act=ops.ACT_NONE)
         if Cc != C2:
             st3 = zeros(C2)
             r3 = ops.conv2d(x, packed(cache, blk.conv_3, dt, ops.PACK_FWD), C2, 1, bias=blk.conv_3.bias.detach(), stats=st3)
-            _, sc3, sh3 = ops.stats_finalize(st3, H * H)
+            _, sc3, sh3 = ops.stats_finalize(st3, N)
             g, bta = blk.instance_norm_3.weight.detach(), blk.instance_norm_3.bias.detach()
             s = ops.blend(r3, z=pre2, sc=(sc3 * g).contiguous(), sh=(sh3 * g + bta).contiguous(), alpha=1.0, beta=1.0)
         else:
@@ -89,12 +85,7 @@ def pg_encoder_backward(E, saved, g_z):
     L = len(saved["blocks"])
     C_last = E.decode_block[L - 1].inputs
     g_out = ops.nchw_to_nhwc(g_flat.view(B, C_last, R >> (L - 1), R >> (L - 1)), B, dt)
-    for j in range(L - 1, -1, -1):
-        blk, rec = E.decode_block[j], saved["blocks"][j]
-        pre = f"decode_block.{j}."
-        Cc, C2 = blk.inputs, blk.outputs
-        H = R >> j
-        N = H * H
+    for j, blk, rec, pre, Cc, C2, H, N in blocks(E, R, saved):
         x, x1 = rec["x"], rec["x1"]
         red1 = ops.zeros((Cc, 2), dev)
         if blk.has_second_conv:
@@ -102,13 +93,8 @@ def pg_encoder_backward(E, saved, g_z):
             # s = pre2 + res ; a = lrelu(s) ; out = avg_pool(a)
             red2 = ops.zeros((C2, 2), dev)
             g_s = ops.act_bwd(g_out, rec["a"], rec["n2"], pool=True, scale=0.25, red=red2)
-            grads[pre + "bias_2"] = red2[:, 0].reshape(1, C2, 1, 1)
-            grads[pre + "noise_weight_2"] = red2[:, 1].reshape(1, C2, 1, 1)
-            gW2 = ops.zeros(tuple(blk.conv_2.weight.shape), dev)
-            ops.conv_wgrad(g_s, x1, gW2, rec["sc2"], rec["sh2"])
-            grads[pre + "conv_2.weight"] = gW2
-            dots2 = ops.zeros((B, Cc, 2), dev)
-            g_y2 = ops.conv2d(g_s, packed(cache, blk.conv_2, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots2, dot_src=x1)
+            red_param_grads(grads, pre, 2, red2)
+            g_y2, dots2 = conv_bwd(cache, grads, pre + "conv_2", blk.conv_2, g_s, x1, dt, H, rec["sc2"], rec["sh2"])
             coef2 = ops.in_bwd_coef(dots2, None, rec["musig2"], rec["sc2"], rec["sh2"], N)
             g_pre1 = ops.in_bwd(g_y2, x1, coef2, noise=rec["n1"], act=True, red=red1)
             if has3:
@@ -119,22 +105,14 @@ def pg_encoder_backward(E, saved, g_z):
                 grads[pre + "instance_norm_3.weight"], grads[pre + "instance_norm_3.bias"] = gsum[:C2], gsum[C2:]
                 g_r3 = ops.in_bwd(g_s, rec["r3"], coef3)
                 grads[pre + "conv_3.bias"] = ops.chan_sum(g_r3)
-                gW3 = ops.zeros(tuple(blk.conv_3.weight.shape), dev)
-                ops.conv_wgrad(g_r3, x, gW3)
-                grads[pre + "conv_3.weight"] = gW3
-                extra = ops.conv2d(g_r3, packed(cache, blk.conv_3, dt, ops.PACK_DGRAD), Cc, 1)
+                extra, _ = conv_bwd(cache, grads, pre + "conv_3", blk.conv_3, g_r3, x, dt, None, dots=False)
             else:
                 extra = g_s
         else:
             g_pre1 = ops.act_bwd(g_out, x1, rec["n1"], pool=False, scale=1.0, red=red1)
             extra = None
-        grads[pre + "bias_1"] = red1[:, 0].reshape(1, Cc, 1, 1)
-        grads[pre + "noise_weight_1"] = red1[:, 1].reshape(1, Cc, 1, 1)
-        gW1 = ops.zeros(tuple(blk.conv_1.weight.shape), dev)
-        ops.conv_wgrad(g_pre1, x, gW1, rec["sc1"], rec["sh1"])
-        grads[pre + "conv_1.weight"] = gW1
-        dots1 = ops.zeros((B, Cc, 2), dev)
-        g_y1 = ops.conv2d(g_pre1, packed(cache, blk.conv_1, dt, ops.PACK_DGRAD, H), Cc, 3, stats=dots1, dot_src=x)
+        red_param_grads(grads, pre, 1, red1)
+        g_y1, dots1 = conv_bwd(cache, grads, pre + "conv_1", blk.conv_1, g_pre1, x, dt, H, rec["sc1"], rec["sh1"])
         coef1 = ops.in_bwd_coef(dots1, None, rec["musig1"], rec["sc1"], rec["sh1"], N)
         g_out = ops.in_bwd(g_y1, x, coef1, extra=extra, extra_pool=False, extra_scale=1.0)
     fromrgb_param_grads(E, saved, g_out, grads)

@@ -1050,8 +1050,22 @@ def _rows_view(t, what):
     return C.c_void_p(t.data_ptr()), t.stride(0), t.stride(1), t.shape[1]
 
 
+def heads_fwd(tab, n, musig_all, w):
+    """Every head of a one-column table (enc_steps.heads_table) in one launch: w[b, col] = musig_l @ W_l^T + b_l into w [B, 2L, O]."""
+    check(lib().dge_heads_fwd(_p(tab), n, _f32(musig_all), _p(w), w.stride(0), w.shape[0], w.shape[2], _stream()), "dge_heads_fwd")
+    return w
+
+
+def heads_bwd(tab, n, max_I, g, musig_all, gms_all, gw_all, gb_all):
+    """Backward of heads_fwd from g = dL/dw [B, 2L, O] (rows O apart, batch stride free): gms_all, gw_all and gb_all, flat by the
+    table's moff / woff / boff.  Two launches, no atomics."""
+    check(lib().dge_heads_bwd(_p(tab), n, int(max_I), _f32(g), g.stride(0), _f32(musig_all), _p(gms_all), _p(gw_all), _p(gb_all),
+                              g.shape[0], g.shape[2], _stream()), "dge_heads_bwd")
+    return gms_all
+
+
 def heads_rows_fwd(tab, n, musig_all, w):
-    """Every head of a row-list table (autograd_encblur.heads_rows_layout) in one launch: w[b, row_a | row_b] = musig_l @ W_l^T + b_l,
+    """Every head of a row-list table (enc_steps.heads_table) in one launch: w[b, row_a | row_b] = musig_l @ W_l^T + b_l,
     written in place into w [B, rows, O] (a view with unit inner stride works); the bits of linear() per head."""
     wp, ldb, ldr, rows = _rows_view(w, "heads_rows_fwd")
     check(lib().dge_heads_rows_fwd(_p(tab), n, _f32(musig_all), wp, ldb, ldr, rows, w.shape[0], w.shape[2], _stream()), "dge_heads_rows_fwd")

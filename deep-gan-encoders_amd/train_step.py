@@ -71,7 +71,7 @@ class TrainStep:
 
     def _encoder_noises(self, R):
         """reference_noise: the encoder's noise tensors for R x R images, drawn on the CPU in the reference's order"""
-        from .autograd_enc import draw_noises
+        from .enc_steps import draw_noises
         return [n.to(self.dev) for n in draw_noises(self.E, self.batch_size, R, "cpu")]
 
     def _head(self, iteration, z, noises, gen_noises, new_z, *, synth_grad=True):
