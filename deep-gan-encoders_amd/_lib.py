@@ -91,7 +91,6 @@ SIGNATURES = {
     "dge_stats_finalize_slots": [_P, _I, _P, _P, _P, _I, _I, _I, _F, _P],
     "dge_blend": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P],
     "dge_loss_reduce": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    "dge_crop_pool": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "dge_ssim_fwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "dge_ssim_box7": [_P, _P, _P, _I, _I, _I, _F, _F, _F, _P],
     "dge_ssim_bwd": [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P],

@@ -62,20 +62,6 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
     block_atomic_sums(v, 7, sums, red);
 }
 
-// out[b,c,y,x] = mean over k x k of src[b,c,y0+ky.., x0+kx..]   (crop + repeated avg_pool2d(2), :81-84)
-__global__ void crop_pool_kernel(const float* __restrict__ src, float* __restrict__ dst, int BC, Crop cr, int k) {
-    const int oh = cr.h / k, ow = cr.w / k;
-    const long n = (long)BC * oh * ow;
-    const long idx = blockIdx.x * 256L + threadIdx.x;
-    if (idx >= n) return;
-    const int x = idx % ow; const long r = idx / ow; const int y = r % oh; const int bc = r / oh;
-    const float* p = src + (size_t)bc * cr.H * cr.W + (size_t)(cr.y0 + y * k) * cr.W + cr.x0 + x * k;
-    float s = 0.f;
-    for (int i = 0; i < k; i++)
-        for (int j = 0; j < k; j++) s += p[(size_t)i * cr.W + j];
-    dst[idx] = s / (float)(k * k);
-}
-
 struct Gauss11 { float g[11]; };
 
 // SSIM forward on [BC, h, w] planes: ssim_sum += sum of the SSIM map; optional derivative maps
@@ -612,7 +598,8 @@ extern "C" int dge_loss_reduce3(const float* a, const float* b, float* sums, int
     DGE_LAUNCH_CHECK("loss_reduce3");
     return 0;
 }
-// dge_crop_pool of up to 6 (source, window, pooling factor) entries in one launch; entry e: src[e] [BC,H,W] -> dst[e] [BC,h/k,w/k]
+// crop + k x k mean (crop + repeated avg_pool2d(2), :81-84) of up to 6 (source, window, pooling factor) entries in one launch;
+// entry e: dst[e] [BC,h/k,w/k] = mean over k x k of src[e] [BC,H,W] at (y0 + y*k .., x0 + x*k ..)
 extern "C" int dge_crop_pool_multi(const float* const* src, float* const* dst, const int* wins, const int* ks, int n, int BC, int H, int W,
                                    hipStream_t s) {
     DGE_CHECK(n >= 1 && n <= 6 && src && dst && wins && ks, "crop_pool_multi: 1..6 entries");
@@ -758,15 +745,6 @@ extern "C" int dge_space_loss_bwd_rows(const float* a, const float* b, const flo
         dge_note_kernel("space_loss_bwd_rows");
     }
     DGE_LAUNCH_CHECK("space_loss_bwd_rows");
-    return 0;
-}
-
-extern "C" int dge_crop_pool(const float* src, float* dst, int BC, int H, int W, int y0, int x0, int h, int w, int k,
-                             hipStream_t s) {
-    DGE_CHECK(k >= 1 && h % k == 0 && w % k == 0, "crop_pool: %dx%d not divisible by %d", h, w, k);
-    const long n = (long)BC * (h / k) * (w / k);
-    hipLaunchKernelGGL(crop_pool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, BC, mk(H, W, y0, x0, h, w), k);
-    DGE_LAUNCH_CHECK("crop_pool");
     return 0;
 }
 

@@ -2,10 +2,16 @@
 E_align_s2.py:185-203 on the HIP kernels, as autograd Functions whose forward also produces the
 analytic gradient w.r.t. the second argument (the only one that carries grad in E_align).
 
-image_loss_tsa_rows / space_loss_rows are the per-sample forms (embedding_v2 `independent`): sample b's loss is what image_loss_tsa
-/ space_loss return on the one-row slices, the result is their sum over b (so the gradient of row b is the gradient of its own
-loss) and the info tensors keep a row per sample."""
+Every form walks its one to three nested windows through the same middle, _pooled_stage: one dge_crop_pool_multi launch, then per
+window SSIM, LPIPS value and gradient and the pooled-image gradient, forked to side streams where that pays.  Around it there are
+two ends.  _coupled_losses: the sums run over the (global) batch - dge_loss_reduce3 or dge_loss_reduce per window, one exchange of
+the packed sums, dge_space_loss_finalize; the gradient is one of _bwd3 (image_loss_tsa), _bwd_each (space_loss, and
+image_loss_tsa in deterministic mode) and _bwd_split (image_losses_split).  _rows_losses: the per-sample forms image_loss_tsa_rows
+/ space_loss_rows (embedding_v2 `independent`): sample b's loss is what image_loss_tsa / space_loss return on the one-row slices,
+the result is their sum over b (so the gradient of row b is the gradient of its own loss) and the info tensors keep a row per
+sample."""
 import contextlib
+import ctypes as C
 import os
 
 import torch
@@ -46,70 +52,34 @@ def attention_windows(H, W):
 _PK = 48          # floats per window in the packed reduction buffer: [0:8] the 8 sums, [8:40] SSIM slot copies, [40] LPIPS mean
 
 
-def _window_reduce(a, b, win, image_space, lpips_model, need_grad, pk, world):
-    """Pass 1 of one space_loss window: every per-rank partial sum goes into the packed row `pk` ([_PK] view, pre-zeroed), so
-    that a data-parallel run exchanges ALL windows of a phase in one all-reduce.  Returns the state pass 2 needs."""
-    B, Cc, H, W = a.shape
-    y0, x0, h, w = win
-    dev = a.device
-    L = lib()
-    slots = ops.zeros((16, 8), dev)         # 16 slot copies of the 8 sums (atomics contention), added up below
-    check(L.dge_loss_reduce(_f32(a), _f32(b), _p(slots), B, Cc, H, W, y0, x0, h, w, _stream()), "dge_loss_reduce")
-    ops._sum_over_batch(slots, pk[0:8])
-    st = dict(win=win, pk=pk, k=1, npool=1.0, n=float(B * Cc * h * w) * world, lp=None, ap=None)
-    if image_space:
-        k = _pool_factor(h)
-        hp, wp = h // k, w // k
-        ap = torch.empty((B, Cc, hp, wp), dtype=torch.float32, device=dev)
-        bp = torch.empty_like(ap)
-        check(L.dge_crop_pool(_f32(a), _p(ap), B * Cc, H, W, y0, x0, h, w, k, _stream()), "dge_crop_pool")
-        check(L.dge_crop_pool(_f32(b), _p(bp), B * Cc, H, W, y0, x0, h, w, k, _stream()), "dge_crop_pool")
-        dmap = torch.empty((3, B, Cc, hp, wp), dtype=torch.float32, device=dev) if need_grad else None
-        # pk[8:40]: 32 slot copies of the SSIM sum (atomics contention), added up by the finaliser
-        check(L.dge_ssim_fwd(_p(ap), _p(bp), _p(pk[8:40]), _p(dmap), B * Cc, hp, wp, _stream()), "dge_ssim_fwd")
-        st.update(k=k, npool=float(B * Cc * hp * wp) * world, ap=ap, bp=bp, dmap=dmap, g_lp=None)
-        if lpips_model is not None:
-            lp, st["g_lp"] = lpips_model.value_and_grad(ap, bp, need_grad=need_grad)       # mean over the rank's batch, d/dbp
-            if world > 1:      # global mean = sum over ranks of (rank mean / world): joins the packed exchange
-                check(L.dge_axpy_scalar(_p(lp), None, _p(pk[40:41]), 1, 1.0 / world, 0, _stream()), "dge_axpy_scalar")
-                lp = pk[40:41]
-            st["lp"] = lp
-    return st
+# ------------------------------------------------------------------ ctypes tables of the multi-window entry points
+def _ptrs(ts):
+    return (C.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
 
 
-def _window_finish(a, b, st, image_space, weight, g_out, accumulate, world):
-    """Pass 2: loss terms from the (globally reduced) sums and, when g_out is given, weight * dloss/db added into it."""
-    B, Cc, H, W = a.shape
-    y0, x0, h, w = st["win"]
-    dev = a.device
-    L = lib()
-    pk = st["pk"]
-    out8 = torch.empty(8, dtype=torch.float32, device=dev)
-    gp = None
-    if image_space and g_out is not None:
-        bp = st["bp"]
-        gp = torch.empty_like(bp)
-        check(L.dge_ssim_bwd(_p(st["ap"]), _p(bp), _p(st["dmap"]), _p(gp), B * Cc, bp.shape[2], bp.shape[3], -1.0 / st["npool"], 0,
-                             _stream()), "dge_ssim_bwd")
-        if st["g_lp"] is not None:
-            check(L.dge_axpy_scalar(_p(st["g_lp"]), None, _p(gp), gp.numel(), 2.0 / world, 1, _stream()), "dge_axpy_scalar")
-    check(L.dge_space_loss_finalize(_p(pk[0:8]), _p(pk[8:40]) if image_space else None, _p(st["lp"]), _p(out8), st["n"], st["npool"],
-                                    1 if image_space else 0, _stream()), "dge_space_loss_finalize")
-    if g_out is not None:
-        check(L.dge_space_loss_bwd(_f32(a), _f32(b), _p(pk[0:8]), _p(gp), _p(g_out), B * Cc, H, W, y0, x0, h, w, st["k"], st["n"],
-                                   float(weight), 1 if accumulate else 0, _stream()), "dge_space_loss_bwd")
-    return out8
+def _ints(vs):
+    return (C.c_int * len(vs))(*vs)
 
 
-def _space_loss_windows(a, b, wins, image_space, lpips_model, weights, g_outs, accumulate, gb=None):
-    """space_loss on several windows of a, b [B,C,H,W] (training_utils.py:54-99 each): all reductions first, ONE exchange of the
-    packed partial sums in a data-parallel run (`gb`), then the loss terms and gradients.  Returns the list of out8 tensors."""
-    world = gb.world if gb is not None else 1
-    pack = ops.zeros((len(wins), _PK), a.device)
-    sts = [_window_reduce(a, b, win, image_space, lpips_model, g_outs[i] is not None, pack[i], world) for i, win in enumerate(wins)]
-    if gb is not None:
-        gb.reduce(pack)
-    return [_window_finish(a, b, st, image_space, weights[i], g_outs[i], accumulate, world) for i, st in enumerate(sts)]
+def _floats(vs):
+    return (C.c_float * len(vs))(*vs)
+
+
+def _wflat(wins):
+    return _ints([int(v) for win in wins for v in win])
+
+
+# ------------------------------------------------------------------ the pooled stage (all forms)
+class _Win:
+    """What the ends need of one window: the pooled images ap, bp and the pooling factor k, the element counts n / npool the means
+    of the full-size / pooled terms run over, the LPIPS value lp, the pooled-image gradient gp (SSIM + LPIPS; None: no gradient).
+    sums (coupled forms): the window's 8 sums in the packed buffer; tiles (rows form): its SSIM tile sums per sample."""
+    __slots__ = ("ap", "bp", "k", "n", "npool", "lp", "gp", "sums", "tiles")
+
+    def __init__(self, win, k, planes):
+        self.k = k
+        self.n, self.npool = float(planes * win[2] * win[3]), float(planes * (win[2] // k) * (win[3] // k))
+        self.ap = self.bp = self.lp = self.gp = self.sums = self.tiles = None
 
 
 # DGE_SIDE_STREAMS=0: everything on the caller's stream (PMC counter collection serialises kernels; profiles of single stages)
@@ -137,143 +107,159 @@ def _window_streams(dev, lpips_model, nw, npix):
     return main, (_side_streams(dev, nw - 1) if fork else [])
 
 
-def _space_loss_windows3(a, b, wins, lpips_model, weights, g, need, gb=None, g_split=None):
-    """The three nested attention windows of image_loss_tsa with every image pass merged (dge_loss_reduce3, dge_crop_pool_multi,
-    dge_space_loss_bwd3): `g` (or None) is WRITTEN with the weighted sum of the windows' gradients; need[i] False leaves window i
-    out of the gradient.  Same arithmetic as _window_reduce / _window_finish per window.
-    `g_split` (image_losses_split; `g` is None then): one full-size image or None per window, each WRITTEN with its own window's
-    weighted gradient (dge_space_loss_bwd_split) instead of the sum."""
-    import ctypes as C
+def _pooled_stage(a, b, wins, ks, lpips_model, want, planes, pack=None, world=1):
+    """The pooled part of space_loss on the windows `wins` of a, b [B,C,H,W], pooled by `ks`: one dge_crop_pool_multi launch for the
+    2 * nwin pooled images, then per window SSIM forward, LPIPS value and gradient and, where want[i], the pooled-image gradient
+    gp = d(1 - ssim + 2 * lpips)/d bp (neither term needs the global sums).  Returns a _Win per window.
+    Coupled forms: `pack` is their [nwin, _PK] buffer - window i's SSIM slot copies go to pack[i, 8:40], its LPIPS mean (world > 1:
+    the rank's share of the global mean) to pack[i, 40:41]; `planes` = B * C * world.  Rows form (pack None): SSIM tile sums and
+    LPIPS values per sample, `planes` = C."""
     B, Cc, H, W = a.shape
     dev = a.device
     L = lib()
-    world = gb.world if gb is not None else 1
     nw = len(wins)
-    pack = ops.zeros((nw, _PK), dev)
-    slots = ops.zeros((nw, 16, 8), dev)
-    wflat = (C.c_int * (4 * nw))(*[int(v) for win in wins for v in win])
-    check(L.dge_loss_reduce3(_f32(a), _f32(b), _p(slots), B, Cc, H, W, wflat, nw, _stream()), "dge_loss_reduce3")
-    sums = ops.DeferredSums()
-    for i in range(nw):
-        sums.add(slots[i].view(16, 8, 1), pack[i, 0:8])      # [nslot, C = 8, NS = 1] -> the 8 sums of window i
-    sums.flush()
-    ks = [_pool_factor(win[2]) for win in wins]
+    rows = pack is None
+    # d lpips / d bp as value_and_grad returns it is that of the batch MEAN: the rows form holds 2 * lpips[sample] = 2 * B * its share
+    lp_scale = 2.0 * B if rows else 2.0 / world
     aps = [torch.empty((B, Cc, win[2] // k, win[3] // k), dtype=torch.float32, device=dev) for win, k in zip(wins, ks)]
     bps = [torch.empty_like(t) for t in aps]
-    srcs = (C.c_void_p * (2 * nw))(*([a.data_ptr()] * nw + [b.data_ptr()] * nw))
-    dsts = (C.c_void_p * (2 * nw))(*([t.data_ptr() for t in aps] + [t.data_ptr() for t in bps]))
-    w2 = (C.c_int * (8 * nw))(*([int(v) for win in wins for v in win] * 2))
-    k2 = (C.c_int * (2 * nw))(*(ks * 2))
-    check(L.dge_crop_pool_multi(srcs, dsts, w2, k2, 2 * nw, B * Cc, H, W, _stream()), "dge_crop_pool_multi")
-    sts = []
+    check(L.dge_crop_pool_multi(_ptrs([a] * nw + [b] * nw), _ptrs(aps + bps), _wflat(list(wins) * 2), _ints(list(ks) * 2), 2 * nw, B * Cc,
+                                H, W, _stream()), "dge_crop_pool_multi")
     # The windows are independent from here to the join below, and their LPIPS launches are small (conv3 - conv5 on 16^2 .. 64^2
     # features: 256 - 1152 workgroups, one or two per CU, each a serial weight stream): on one stream they run one after the
     # other on a half-empty chip.  Each window gets its own stream (forked off the caller's, joined before the results are
     # read); the first call stays on one stream (it fills the LPIPS weight-pack cache), so does the deterministic mode (its
     # slot workspace belongs to one stream at a time).
     main, side = _window_streams(dev, lpips_model, nw, B * H * W)
-    fork = bool(side)
+    sts = []
     for i, win in enumerate(wins):
-        y0, x0, h, w = win
-        ap, bp, k = aps[i], bps[i], ks[i]
-        hp, wp = h // k, w // k
-        ng = (g is not None or g_split is not None) and need[i]
-        strm = side[i - 1] if (fork and i > 0) else None
+        st = _Win(win, ks[i], planes)
+        ap, bp = st.ap, st.bp = aps[i], bps[i]
+        hp, wp = ap.shape[2], ap.shape[3]
+        strm = side[i - 1] if (side and i > 0) else None
         if strm is not None:
             strm.wait_stream(main)
         with (torch.cuda.stream(strm) if strm is not None else contextlib.nullcontext()):
-            dmap = torch.empty((3, B, Cc, hp, wp), dtype=torch.float32, device=dev) if ng else None
-            check(L.dge_ssim_fwd(_p(ap), _p(bp), _p(pack[i, 8:40]), _p(dmap), B * Cc, hp, wp, _stream()), "dge_ssim_fwd")
-            st = dict(win=win, pk=pack[i], k=k, npool=float(B * Cc * hp * wp) * world, n=float(B * Cc * h * w) * world, ap=ap, bp=bp,
-                      dmap=dmap, g_lp=None, lp=None, ng=ng)
-            if lpips_model is not None:
-                lp, st["g_lp"] = lpips_model.value_and_grad(ap, bp, need_grad=ng)
-                if world > 1:
-                    check(L.dge_axpy_scalar(_p(lp), None, _p(pack[i, 40:41]), 1, 1.0 / world, 0, _stream()), "dge_axpy_scalar")
-                    lp = pack[i, 40:41]
-                st["lp"] = lp
-            # the window's pooled-image gradient (SSIM + LPIPS; neither needs the global sums) in the window's stream too
-            st["gp"] = None
-            if ng:
-                gp = torch.empty_like(bp)
-                check(L.dge_ssim_bwd(_p(ap), _p(bp), _p(dmap), _p(gp), B * Cc, hp, wp, -1.0 / st["npool"], 0, _stream()), "dge_ssim_bwd")
-                if st["g_lp"] is not None:
-                    check(L.dge_axpy_scalar(_p(st["g_lp"]), None, _p(gp), gp.numel(), 2.0 / world, 1, _stream()), "dge_axpy_scalar")
-                st["gp"] = gp
+            dmap = torch.empty((3, B, Cc, hp, wp), dtype=torch.float32, device=dev) if want[i] else None
+            g_lp = None
+            if rows:
+                st.tiles = torch.empty((B, Cc * ((hp + 15) // 16) * ((wp + 15) // 16)), dtype=torch.float32, device=dev)
+                check(L.dge_ssim_fwd_rows(_p(ap), _p(bp), _p(st.tiles), _p(dmap), B * Cc, hp, wp, _stream()), "dge_ssim_fwd_rows")
+                ops.log_kernel()
+                if lpips_model is not None:
+                    st.lp, g_lp = lpips_model.value_and_grad(ap, bp, need_grad=want[i], per_sample=True)
+            else:
+                # pack[i, 8:40]: 32 slot copies of the SSIM sum (atomics contention), added up by the finaliser
+                check(L.dge_ssim_fwd(_p(ap), _p(bp), _p(pack[i, 8:40]), _p(dmap), B * Cc, hp, wp, _stream()), "dge_ssim_fwd")
+                if lpips_model is not None:
+                    st.lp, g_lp = lpips_model.value_and_grad(ap, bp, need_grad=want[i])      # mean over the rank's batch, d/dbp
+                    if world > 1:      # global mean = sum over ranks of (rank mean / world): joins the packed exchange
+                        check(L.dge_axpy_scalar(_p(st.lp), None, _p(pack[i, 40:41]), 1, 1.0 / world, 0, _stream()), "dge_axpy_scalar")
+                        st.lp = pack[i, 40:41]
+            if want[i]:
+                st.gp = torch.empty_like(bp)
+                check(L.dge_ssim_bwd(_p(ap), _p(bp), _p(dmap), _p(st.gp), B * Cc, hp, wp, -1.0 / st.npool, 0, _stream()), "dge_ssim_bwd")
+                if g_lp is not None:
+                    check(L.dge_axpy_scalar(_p(g_lp), None, _p(st.gp), g_lp.numel(), lp_scale, 1, _stream()), "dge_axpy_scalar")
         if strm is not None:            # results allocated on the side stream are read (and freed) under the caller's stream
-            for t in (dmap, st["g_lp"], st["lp"], st["gp"]):
+            for t in (dmap, st.tiles, st.lp, g_lp, st.gp):
                 if t is not None:
                     t.record_stream(main)
         sts.append(st)
     for strm in side:
         main.wait_stream(strm)
-    if lpips_model is not None:
+    # the next call may fork: this one ran the LPIPS kernels of a forking call on one stream (the rows form runs the same ones in
+    # both reduction modes, the coupled forms fork - and mark - only outside the deterministic mode)
+    if lpips_model is not None and nw > 1 and (rows or not ops.is_deterministic()):
         lpips_model._streams_warm = True
+    return sts
+
+
+# ------------------------------------------------------------------ coupled forms: the sums run over the (global) batch
+def batch_sums(a, b, win, out=None):
+    """The 8 sums of dge_loss_reduce over window `win` of a, b [B,C,H,W]: 16 slot copies (atomics contention), added up into `out`
+    (pre-zeroed) or a new [8] tensor."""
+    B, Cc, H, W = a.shape
+    slots = ops.zeros((16, 8), a.device)
+    check(lib().dge_loss_reduce(_f32(a), _f32(b), _p(slots), B, Cc, H, W, *win, _stream()), "dge_loss_reduce")
+    return ops._sum_over_batch(slots, out)
+
+
+def _coupled_losses(a, b, wins, image_space, lpips_model, want, gb=None):
+    """space_loss on the windows `wins` of a, b [B,C,H,W] (training_utils.py:54-99 each) up to the loss terms: every per-rank partial
+    sum goes into one packed buffer, a data-parallel run (`gb`) exchanges ALL windows in one all-reduce, then the finaliser runs
+    per window.  Several windows take every image pass merged (dge_loss_reduce3; not offered in deterministic mode, which reduces
+    window by window).  Returns (a _Win per window for the gradient, the list of out8 tensors)."""
+    B, Cc, H, W = a.shape
+    dev = a.device
+    L = lib()
+    nw = len(wins)
+    world = gb.world if gb is not None else 1
+    pack = ops.zeros((nw, _PK), dev)
+    if nw > 1 and not ops.is_deterministic():
+        slots = ops.zeros((nw, 16, 8), dev)
+        check(L.dge_loss_reduce3(_f32(a), _f32(b), _p(slots), B, Cc, H, W, _wflat(wins), nw, _stream()), "dge_loss_reduce3")
+        sums = ops.DeferredSums()
+        for i in range(nw):
+            sums.add(slots[i].view(16, 8, 1), pack[i, 0:8])      # [nslot, C = 8, NS = 1] -> the 8 sums of window i
+        sums.flush()
+    else:
+        for i, win in enumerate(wins):
+            batch_sums(a, b, win, pack[i, 0:8])
+    if image_space:
+        sts = _pooled_stage(a, b, wins, [_pool_factor(win[2]) for win in wins], lpips_model, want, B * Cc * world, pack, world)
+    else:
+        sts = [_Win(win, 1, B * Cc * world) for win in wins]
     if gb is not None:
         gb.reduce(pack)
-    outs, gps = [], []
+    outs = []
     for i, st in enumerate(sts):
-        gps.append(st["gp"])
+        st.sums = pack[i, 0:8]
         out8 = torch.empty(8, dtype=torch.float32, device=dev)
-        check(L.dge_space_loss_finalize(_p(pack[i, 0:8]), _p(pack[i, 8:40]), _p(st["lp"]), _p(out8), st["n"], st["npool"], 1, _stream()),
-              "dge_space_loss_finalize")
+        check(L.dge_space_loss_finalize(_p(st.sums), _p(pack[i, 8:40]) if image_space else None, _p(st.lp), _p(out8), st.n, st.npool,
+                                        1 if image_space else 0, _stream()), "dge_space_loss_finalize")
         outs.append(out8)
-    if g is not None:
-        sp = (C.c_void_p * nw)(*[pack[i, 0:8].data_ptr() for i in range(nw)])
-        gpp = (C.c_void_p * nw)(*[(t.data_ptr() if t is not None else None) for t in gps])
-        nn = (C.c_float * nw)(*[st["n"] for st in sts])
-        ww = (C.c_float * nw)(*[float(weights[i]) if sts[i]["ng"] else 0.0 for i in range(nw)])
-        kk = (C.c_int * nw)(*ks)
-        check(L.dge_space_loss_bwd3(_f32(a), _f32(b), sp, gpp, _p(g), B * Cc, H, W, wflat, kk, nn, ww, nw, _stream()), "dge_space_loss_bwd3")
-    if g_split is not None:
-        _bwd_split(a, b, wins, [pack[i, 0:8] for i in range(nw)], gps, ks, [st["n"] for st in sts],
-                   [float(weights[i]) if sts[i]["ng"] else 0.0 for i in range(nw)], g_split)
-    return outs
+    return sts, outs
 
 
-def _bwd_split(a, b, wins, sums, gps, ks, ns, wts, outs):
-    """One dge_space_loss_bwd_split launch: outs[k] (or None) is WRITTEN with wts[k] * (window k's gradient), zeros outside it."""
-    import ctypes as C
+def _bwd_each(a, b, wins, sts, weights, want, g, accumulate):
+    """dge_space_loss_bwd per wanted window: weights[k] * (window k's gradient) is written into that window of g, or added to it."""
+    B, Cc, H, W = a.shape
+    for win, st, wt, on in zip(wins, sts, weights, want):
+        if on:
+            check(lib().dge_space_loss_bwd(_f32(a), _f32(b), _p(st.sums), _p(st.gp), _p(g), B * Cc, H, W, *win, st.k, st.n, float(wt),
+                                           1 if accumulate else 0, _stream()), "dge_space_loss_bwd")
+
+
+def _bwd_tables(a, wins, sts, weights, want):
+    """The arguments dge_space_loss_bwd3 and dge_space_loss_bwd_split share, before and after the gradient image(s)"""
+    B, Cc, H, W = a.shape
+    wts = [float(wt) if on else 0.0 for wt, on in zip(weights, want)]
+    return ((_ptrs([st.sums for st in sts]), _ptrs([st.gp for st in sts])),
+            (B * Cc, H, W, _wflat(wins), _ints([st.k for st in sts]), _floats([st.n for st in sts]), _floats(wts), len(wins), _stream()))
+
+
+def _bwd3(a, b, wins, sts, weights, want, g):
+    """One dge_space_loss_bwd3 launch: g is WRITTEN with the weighted sum of the wanted windows' gradients."""
+    src, dims = _bwd_tables(a, wins, sts, weights, want)
+    check(lib().dge_space_loss_bwd3(_f32(a), _f32(b), *src, _p(g), *dims), "dge_space_loss_bwd3")
+
+
+def _bwd_split(a, b, wins, sts, weights, want, outs):
+    """One dge_space_loss_bwd_split launch: outs[k] (or None) is WRITTEN with weights[k] * (window k's gradient), zeros outside it."""
     if all(t is None for t in outs):
         return
-    B, Cc, H, W = a.shape
-    nw = len(wins)
-    ptrs = lambda ts: (C.c_void_p * nw)(*[(t.data_ptr() if t is not None else None) for t in ts])
-    wflat = (C.c_int * (4 * nw))(*[int(v) for win in wins for v in win])
-    check(lib().dge_space_loss_bwd_split(_f32(a), _f32(b), ptrs(sums), ptrs(gps), ptrs(outs), B * Cc, H, W, wflat, (C.c_int * nw)(*ks),
-                                         (C.c_float * nw)(*ns), (C.c_float * nw)(*wts), nw, _stream()), "dge_space_loss_bwd_split")
+    src, dims = _bwd_tables(a, wins, sts, weights, want)
+    check(lib().dge_space_loss_bwd_split(_f32(a), _f32(b), *src, _ptrs(outs), *dims), "dge_space_loss_bwd_split")
     ops.log_kernel()
 
 
-def _space_loss_windows_split(a, b, wins, lpips_model, weights, g_split, gb=None):
-    """_space_loss_windows3 with g_split in deterministic mode: the per-window reductions of _window_reduce (dge_loss_reduce3 is
-    not offered there), the pooled gradients of _window_finish, then the same single dge_space_loss_bwd_split launch."""
-    B, Cc = a.shape[:2]
-    L = lib()
-    world = gb.world if gb is not None else 1
-    pack = ops.zeros((len(wins), _PK), a.device)
-    sts = [_window_reduce(a, b, win, True, lpips_model, g_split[i] is not None, pack[i], world) for i, win in enumerate(wins)]
-    if gb is not None:
-        gb.reduce(pack)
-    outs, gps = [], []
-    for i, st in enumerate(sts):
-        gp = None
-        if g_split[i] is not None:
-            bp = st["bp"]
-            gp = torch.empty_like(bp)
-            check(L.dge_ssim_bwd(_p(st["ap"]), _p(bp), _p(st["dmap"]), _p(gp), B * Cc, bp.shape[2], bp.shape[3], -1.0 / st["npool"], 0,
-                                 _stream()), "dge_ssim_bwd")
-            if st["g_lp"] is not None:
-                check(L.dge_axpy_scalar(_p(st["g_lp"]), None, _p(gp), gp.numel(), 2.0 / world, 1, _stream()), "dge_axpy_scalar")
-        gps.append(gp)
-        outs.append(_window_finish(a, b, st, True, weights[i], None, False, world))
-    _bwd_split(a, b, wins, [pack[i, 0:8] for i in range(len(wins))], gps, [st["k"] for st in sts], [st["n"] for st in sts],
-               [float(weights[i]) if g_split[i] is not None else 0.0 for i in range(len(wins))], g_split)
-    return outs
-
-
-def _space_loss_window(a, b, win, image_space, lpips_model, weight, g_out, accumulate, gb=None):
-    return _space_loss_windows(a, b, [win], image_space, lpips_model, [weight], [g_out], accumulate, gb)[0]
+def _space_loss_window(a, b, win, image_space, lpips_model, g, gb=None):
+    """space_loss on one window of a, b [B,C,H,W]; g (or None) is WRITTEN with dloss/db.  Returns out8."""
+    want = [g is not None]
+    sts, outs = _coupled_losses(a, b, [win], image_space, lpips_model, want, gb)
+    _bwd_each(a, b, [win], sts, [1.0], want, g, accumulate=False)
+    return outs[0]
 
 
 class _ScaledGrad(torch.autograd.Function):
@@ -320,13 +306,14 @@ def image_loss_tsa(imgs1, imgs2, lpips_model=None, weights=(1.0, 5.0, 9.0), glob
     need = imgs2.requires_grad and torch.is_grad_enabled()
     wins = attention_windows(a.shape[2], a.shape[3])
     # grad_windows[i] False: the window enters the loss VALUE only (embedding_img.py:95-107 detaches both crops)
-    if not ops.is_deterministic():       # every pass over the two images merged over the three windows
-        g = torch.empty_like(b) if need else None
-        infos = _space_loss_windows3(a, b, wins, lpips_model, weights, g, [bool(need and grad_windows[i]) for i in range(3)], gb=global_batch)
-    else:
-        g = torch.zeros_like(b) if need else None
-        infos = _space_loss_windows(a, b, wins, True, lpips_model, weights,
-                                    [g if (need and grad_windows[i]) else None for i in range(3)], accumulate=True, gb=global_batch)
+    want = [bool(need and grad_windows[i]) for i in range(3)]
+    det = ops.is_deterministic()
+    g = (torch.zeros_like(b) if det else torch.empty_like(b)) if need else None
+    sts, infos = _coupled_losses(a, b, wins, True, lpips_model, want, global_batch)
+    if need and det:          # (dge_space_loss_bwd3's 16-byte form multiplies by reciprocals: not the bits of the single-window kernel)
+        _bwd_each(a, b, wins, sts, weights, want, g, accumulate=True)
+    elif need:
+        _bwd3(a, b, wins, sts, weights, want, g)
     info = torch.stack(infos)
     loss = info[0, 0] * float(weights[0]) + info[1, 0] * float(weights[1]) + info[2, 0] * float(weights[2])   # no host->device copy
     if need:
@@ -346,10 +333,8 @@ def image_losses_split(imgs1, imgs2, lpips_model=None, weights=(1.0, 5.0, 9.0), 
     wins = attention_windows(a.shape[2], a.shape[3])
     want = [bool(need and windows[i]) for i in range(3)]
     gs = [torch.empty_like(b) if want[i] else None for i in range(3)]
-    if not ops.is_deterministic():
-        infos = _space_loss_windows3(a, b, wins, lpips_model, weights, None, want, gb=global_batch, g_split=gs)
-    else:
-        infos = _space_loss_windows_split(a, b, wins, lpips_model, weights, gs, gb=global_batch)
+    sts, infos = _coupled_losses(a, b, wins, True, lpips_model, want, global_batch)
+    _bwd_split(a, b, wins, sts, weights, want, gs)
     info = torch.stack(infos)
     out = []
     for i in range(3):
@@ -367,25 +352,25 @@ def space_loss(imgs1, imgs2, image_space=True, lpips_model=None, global_batch=No
     g = torch.empty_like(b) if need else None
     if image_space:
         B, Cc, H, W = a.shape
-        out8 = _space_loss_window(a, b, (0, 0, H, W), True, lpips_model, 1.0, g, accumulate=False, gb=global_batch)
+        out8 = _space_loss_window(a, b, (0, 0, H, W), True, lpips_model, g, gb=global_batch)
     else:
         # 3-D latents: the implicit softmax dim is 0 (the batch) -> planes = batch (training_utils.py:67)
         Bt = a.shape[0]
         n_in = a.numel() // Bt
         if a.dim() == 2:
             # 2-D latents (PGGAN / BigGAN z): the implicit softmax dim is 1 -> one softmax per sample over the features
-            out8 = _space_loss_window(a.view(Bt, n_in, 1, 1), b.view(Bt, n_in, 1, 1), (0, 0, 1, 1), False, None, 1.0,
-                                      g.view(Bt, n_in, 1, 1) if need else None, accumulate=False, gb=global_batch)
+            out8 = _space_loss_window(a.view(Bt, n_in, 1, 1), b.view(Bt, n_in, 1, 1), (0, 0, 1, 1), False, None,
+                                      g.view(Bt, n_in, 1, 1) if need else None, gb=global_batch)
             loss = out8[0]
             return (_ScaledGrad.apply(imgs2, loss, g) if need else loss), out8
-        out8 = _space_loss_window(a.view(1, Bt, 1, n_in), b.view(1, Bt, 1, n_in), (0, 0, 1, n_in), False, None, 1.0,
-                                  g.view(1, Bt, 1, n_in) if need else None, accumulate=False, gb=global_batch)
+        out8 = _space_loss_window(a.view(1, Bt, 1, n_in), b.view(1, Bt, 1, n_in), (0, 0, 1, n_in), False, None,
+                                  g.view(1, Bt, 1, n_in) if need else None, gb=global_batch)
         if imgs1.requires_grad and torch.is_grad_enabled():
             # the first argument carries a gradient too: 5*mse + 3*cos is symmetric, so d/da is the same kernel with
             # the arguments exchanged (the logged-only KL term is not, and is taken from the first evaluation)
             ga = torch.empty_like(a)
-            _space_loss_window(b.view(1, Bt, 1, n_in), a.view(1, Bt, 1, n_in), (0, 0, 1, n_in), False, None, 1.0,
-                               ga.view(1, Bt, 1, n_in), accumulate=False, gb=global_batch)
+            _space_loss_window(b.view(1, Bt, 1, n_in), a.view(1, Bt, 1, n_in), (0, 0, 1, n_in), False, None,
+                               ga.view(1, Bt, 1, n_in), gb=global_batch)
             gbt = g if need else torch.zeros_like(b)
             return _ScaledGrad2.apply(imgs1, imgs2, out8[0], ga, gbt), out8
     loss = out8[0]
@@ -395,80 +380,42 @@ def space_loss(imgs1, imgs2, image_space=True, lpips_model=None, global_batch=No
 
 
 # ------------------------------------------------------------------ per-sample forms
-def _space_loss_rows(a, b, wins, image_space, lpips_model, weights, need, ga=None, gb=None):
+def _rows_losses(a, b, wins, image_space, lpips_model, weights, need, ga=None, gb=None):
     """space_loss of every sample of a, b [B,C,H,W] on up to 3 nested windows (all inside window 0), the samples kept apart:
-    dge_loss_reduce_rows, dge_crop_pool_multi, per window dge_ssim_fwd_rows + per-sample LPIPS + the pooled gradient, then
-    dge_space_loss_finalize_rows and dge_space_loss_bwd_rows.  `gb` (or None) is WRITTEN with sum_k weights[k] * d loss_k[sample]/db
-    (need[k] False leaves window k out), `ga` (latents only) with the gradient w.r.t. a.  Returns out8 [B, nwin, 8]."""
-    import ctypes as C
+    dge_loss_reduce_rows, the pooled stage in its rows form (images only), then dge_space_loss_finalize_rows and
+    dge_space_loss_bwd_rows.  `gb` (or None) is WRITTEN with sum_k weights[k] * d loss_k[sample]/db (need[k] False leaves window k
+    out), `ga` (latents only) with the gradient w.r.t. a.  Returns out8 [B, nwin, 8]."""
     B, Cc, H, W = a.shape
     dev = a.device
     L = lib()
     nw = len(wins)
     h0, w0 = wins[0][2], wins[0][3]
     nblk = max(1, min(256, (h0 * w0 + 1023) // 1024))
-    wflat = (C.c_int * (4 * nw))(*[int(v) for win in wins for v in win])
+    wflat = _wflat(wins)
     part = torch.empty((B, nw, nblk, 8), dtype=torch.float32, device=dev)
     check(L.dge_loss_reduce_rows(_f32(a), _f32(b), _p(part), B, Cc, H, W, wflat, nw, nblk, _stream()), "dge_loss_reduce_rows")
     ops.log_kernel()
-    ks = [_pool_factor(win[2]) if image_space else 1 for win in wins]
-    ns = [float(Cc * win[2] * win[3]) for win in wins]
-    npools = [float(Cc * (win[2] // k) * (win[3] // k)) for win, k in zip(wins, ks)]
-    tiles, lps, gps = [None] * nw, [None] * nw, [None] * nw
     want = [bool(gb is not None and need[i]) for i in range(nw)]
+    tiles = cnt = lps = gps = None
     if image_space:
-        aps = [torch.empty((B, Cc, win[2] // k, win[3] // k), dtype=torch.float32, device=dev) for win, k in zip(wins, ks)]
-        bps = [torch.empty_like(t) for t in aps]
-        srcs = (C.c_void_p * (2 * nw))(*([a.data_ptr()] * nw + [b.data_ptr()] * nw))
-        dsts = (C.c_void_p * (2 * nw))(*([t.data_ptr() for t in aps] + [t.data_ptr() for t in bps]))
-        w2 = (C.c_int * (8 * nw))(*([int(v) for win in wins for v in win] * 2))
-        k2 = (C.c_int * (2 * nw))(*(ks * 2))
-        check(L.dge_crop_pool_multi(srcs, dsts, w2, k2, 2 * nw, B * Cc, H, W, _stream()), "dge_crop_pool_multi")
-        main, side = _window_streams(dev, lpips_model, nw, B * H * W)       # the windows' LPIPS launches fork as in _space_loss_windows3
-        for i in range(nw):
-            ap, bp = aps[i], bps[i]
-            hp, wp = ap.shape[2], ap.shape[3]
-            strm = side[i - 1] if (side and i > 0) else None
-            if strm is not None:
-                strm.wait_stream(main)
-            with (torch.cuda.stream(strm) if strm is not None else contextlib.nullcontext()):
-                dmap = torch.empty((3, B, Cc, hp, wp), dtype=torch.float32, device=dev) if want[i] else None
-                tiles[i] = torch.empty((B, Cc * ((hp + 15) // 16) * ((wp + 15) // 16)), dtype=torch.float32, device=dev)
-                check(L.dge_ssim_fwd_rows(_p(ap), _p(bp), _p(tiles[i]), _p(dmap), B * Cc, hp, wp, _stream()), "dge_ssim_fwd_rows")
-                ops.log_kernel()
-                g_lp = None
-                if lpips_model is not None:
-                    lps[i], g_lp = lpips_model.value_and_grad(ap, bp, need_grad=want[i], per_sample=True)
-                if want[i]:
-                    gps[i] = torch.empty_like(bp)
-                    check(L.dge_ssim_bwd(_p(ap), _p(bp), _p(dmap), _p(gps[i]), B * Cc, hp, wp, -1.0 / npools[i], 0, _stream()), "dge_ssim_bwd")
-                    if g_lp is not None:      # g_lp = d mean_b lpips / db = (1/B) d lpips[sample] / db; the loss holds 2 * lpips[sample]
-                        check(L.dge_axpy_scalar(_p(g_lp), None, _p(gps[i]), g_lp.numel(), 2.0 * B, 1, _stream()), "dge_axpy_scalar")
-            if strm is not None:            # results allocated on the side stream are read (and freed) under the caller's stream
-                for t in (dmap, tiles[i], lps[i], g_lp, gps[i]):
-                    if t is not None:
-                        t.record_stream(main)
-        for strm in side:
-            main.wait_stream(strm)
-        if lpips_model is not None:
-            lpips_model._streams_warm = True
-    ptrs = lambda ts: (C.c_void_p * nw)(*[(t.data_ptr() if t is not None else None) for t in ts])
+        sts = _pooled_stage(a, b, wins, [_pool_factor(win[2]) for win in wins], lpips_model, want, Cc)
+        tiles, lps, gps = _ptrs([st.tiles for st in sts]), _ptrs([st.lp for st in sts]), _ptrs([st.gp for st in sts])
+        cnt = _ints([st.tiles.shape[1] for st in sts])
+    else:
+        sts = [_Win(win, 1, Cc) for win in wins]
     sums7 = torch.empty((B, nw, 8), dtype=torch.float32, device=dev)
     out8 = torch.empty((B, nw, 8), dtype=torch.float32, device=dev)
-    cnt = (C.c_int * nw)(*[(t.shape[1] if t is not None else 0) for t in tiles])
-    nn, pp = (C.c_float * nw)(*ns), (C.c_float * nw)(*npools)
-    check(L.dge_space_loss_finalize_rows(_p(part), nblk, ptrs(tiles) if image_space else None, cnt if image_space else None,
-                                         ptrs(lps) if image_space else None, _p(sums7), _p(out8), B, nw, nn, pp, 1 if image_space else 0,
-                                         _stream()), "dge_space_loss_finalize_rows")
+    nn, kk = _floats([st.n for st in sts]), _ints([st.k for st in sts])
+    check(L.dge_space_loss_finalize_rows(_p(part), nblk, tiles, cnt, lps, _p(sums7), _p(out8), B, nw, nn, _floats([st.npool for st in sts]),
+                                         1 if image_space else 0, _stream()), "dge_space_loss_finalize_rows")
     ops.log_kernel()
-    kk = (C.c_int * nw)(*ks)
     if gb is not None:
-        ww = (C.c_float * nw)(*[float(weights[i]) if want[i] else 0.0 for i in range(nw)])
-        check(L.dge_space_loss_bwd_rows(_f32(a), _f32(b), _p(sums7), ptrs(gps) if image_space else None, _p(gb), B, Cc, H, W, wflat, kk,
-                                        nn, ww, nw, 0, _stream()), "dge_space_loss_bwd_rows")
+        ww = _floats([float(weights[i]) if want[i] else 0.0 for i in range(nw)])
+        check(L.dge_space_loss_bwd_rows(_f32(a), _f32(b), _p(sums7), gps, _p(gb), B, Cc, H, W, wflat, kk, nn, ww, nw, 0, _stream()),
+              "dge_space_loss_bwd_rows")
         ops.log_kernel()
     if ga is not None:
-        ww = (C.c_float * nw)(*[float(weights[i]) for i in range(nw)])
+        ww = _floats([float(weights[i]) for i in range(nw)])
         check(L.dge_space_loss_bwd_rows(_f32(b), _f32(a), _p(sums7), None, _p(ga), B, Cc, H, W, wflat, kk, nn, ww, nw, 1, _stream()),
               "dge_space_loss_bwd_rows")
         ops.log_kernel()
@@ -491,7 +438,7 @@ def image_loss_tsa_rows(imgs1, imgs2, lpips_model=None, weights=(1.0, 5.0, 9.0),
     need = imgs2.requires_grad and torch.is_grad_enabled()
     wins = attention_windows(a.shape[2], a.shape[3])
     g = torch.empty_like(b) if need else None
-    info = _space_loss_rows(a, b, wins, True, lpips_model, weights, [bool(need and grad_windows[i]) for i in range(3)], gb=g)
+    info = _rows_losses(a, b, wins, True, lpips_model, weights, [bool(need and grad_windows[i]) for i in range(3)], gb=g)
     loss = (info[:, 0, 0] * float(weights[0]) + info[:, 1, 0] * float(weights[1]) + info[:, 2, 0] * float(weights[2])).sum()
     if need:
         loss = _ScaledGrad.apply(imgs2, loss, g)
@@ -514,7 +461,7 @@ def space_loss_rows(imgs1, imgs2, image_space=False, global_batch=None):
     ga = torch.empty_like(a) if need_a else None
     gb = torch.empty_like(b) if need_b else None
     view = lambda t: t.view(Bt, 1, 1, n_in) if t is not None else None
-    info = _space_loss_rows(view(a), view(b), [(0, 0, 1, n_in)], False, None, [1.0], [True], ga=view(ga), gb=view(gb))[:, 0]
+    info = _rows_losses(view(a), view(b), [(0, 0, 1, n_in)], False, None, [1.0], [True], ga=view(ga), gb=view(gb))[:, 0]
     loss = info[:, 0].sum()
     if need_a:
         loss = _ScaledGrad2.apply(imgs1, imgs2, loss, ga, gb if need_b else torch.zeros_like(b))

@@ -250,8 +250,6 @@ int dge_blend(const void* x, const void* z, void* y, const float* sc, const floa
  * sum softmax_C(a)*(log softmax_C(a)-log softmax_C(b)) }  -> mse :63, mean/std terms :64-65, KL :67-71, cosine :73-75. */
 int dge_loss_reduce(const float* a, const float* b, float* sums7, int B, int C, int H, int W, int y0, int x0, int h, int w,
                     dge_stream_t stream);
-/* crop + k x k mean (the `while H > 256: avg_pool2d(2)` loop of :81-84 collapsed) on BC planes */
-int dge_crop_pool(const float* src, float* dst, int BC, int H, int W, int y0, int x0, int h, int w, int k, dge_stream_t stream);
 /* ssim_sum [32] (pre-zeroed slot copies; their total is the sum, dge_space_loss_finalize adds them) += sum of the SSIM map of a,b [BC,h,w]; dmap (optional, [3][BC][h][w]) receives dS/dmu2,
  * dS/dE[b^2], dS/dE[ab] for dge_ssim_bwd, which writes g = scale * dSum/db. */
 int dge_ssim_fwd(const float* a, const float* b, float* ssim_sum, float* dmap, int BC, int h, int w, dge_stream_t stream);
@@ -269,8 +267,9 @@ int dge_space_loss_bwd(const float* a, const float* b, const float* sums7, const
                        int W, int y0, int x0, int h, int w, int k, float n, float weight, int accumulate, dge_stream_t stream);
 /* The same three kernels for the nested attention windows of E_align_s2.py:185-203 (full image, AT1, AT2), every pixel touched
  * once: wins = nwin x (y0, x0, h, w), all inside window 0.  dge_loss_reduce3: sums [nwin][16][8] slot copies (pre-zeroed; add
- * them with dge_sum_slots; not offered in deterministic mode).  dge_crop_pool_multi: n <= 6 (source plane set, window, pooling
- * factor) entries.  dge_space_loss_bwd3: g over window 0 is WRITTEN with sum_k weight[k] * gradient of window k. */
+ * them with dge_sum_slots; not offered in deterministic mode).  dge_crop_pool_multi: crop + k x k mean (the `while H > 256:
+ * avg_pool2d(2)` loop of :81-84 collapsed) on BC planes, for n <= 6 (source plane set, window, pooling factor) entries; it serves
+ * every form of the loss, a single window included.  dge_space_loss_bwd3: g over window 0 is WRITTEN with sum_k weight[k] * gradient of window k. */
 int dge_loss_reduce3(const float* a, const float* b, float* sums, int B, int C, int H, int W, const int* wins, int nwin, dge_stream_t stream);
 int dge_crop_pool_multi(const float* const* src, float* const* dst, const int* wins, const int* ks, int n, int BC, int H, int W,
                         dge_stream_t stream);

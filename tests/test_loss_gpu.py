@@ -80,6 +80,33 @@ def test_tsa_loss_and_gradient_vs_oracle(B, H, W):
     assert err < 2e-3, err
 
 
+def test_crop_pool_multi_vs_avg_pool():
+    """One dge_crop_pool_multi launch with four entries on src [BC=2, 24, 32]: the 16-byte branch, k = 4 at an unaligned x0 (scalar
+    branch), pooling factor 2 and no pooling, each against avg_pool2d of the crop in float64.  Bound 2e-6 * max|src|: an f32 sum of
+    at most 16 terms errs by at most 15 * 2^-24 * max|x| (about 9e-7) after the division, and the bound is twice that.  Nothing is
+    written past an entry's BC * (h/k) * (w/k) elements."""
+    import ctypes as C
+    from dge_amd._lib import lib, check
+    BC, H, W = 2, 24, 32
+    entries = [(0, 0, 24, 32, 4), (4, 2, 16, 28, 4), (2, 4, 20, 24, 2), (0, 0, 24, 32, 1)]
+    src = R.randn("loss.crop_pool.src", (BC, H, W), 4, 0.5)
+    dsrc = src.cuda()
+    pad, sentinel = 64, -7.5
+    dsts = [torch.full((BC * (h // k) * (w // k) + pad,), sentinel, device="cuda") for _, _, h, w, k in entries]
+    n = len(entries)
+    check(lib().dge_crop_pool_multi((C.c_void_p * n)(*[dsrc.data_ptr()] * n), (C.c_void_p * n)(*[t.data_ptr() for t in dsts]),
+                                    (C.c_int * (4 * n))(*[v for e in entries for v in e[:4]]), (C.c_int * n)(*[e[4] for e in entries]),
+                                    n, BC, H, W, torch.cuda.current_stream().cuda_stream), "dge_crop_pool_multi")
+    bound = 2e-6 * src.abs().max().item()
+    for (y0, x0, h, w, k), dst in zip(entries, dsts):
+        ref = torch.nn.functional.avg_pool2d(src.double()[None, :, y0:y0 + h, x0:x0 + w], k)[0]
+        got = dst.cpu()
+        err = (got[:ref.numel()].double() - ref.reshape(-1)).abs().max().item()
+        print(f"crop_pool_multi {(y0, x0, h, w, k)}: max err {err:.3e} (bound {bound:.3e})")
+        assert err <= bound, ((y0, x0, h, w, k), err, bound)
+        assert torch.all(got[ref.numel():] == sentinel), (y0, x0, h, w, k)
+
+
 def test_lreq_adam_vs_reference_golden():
     from dge_amd.custom_adam import LREQAdam
     g = golden("adam.npz")
