@@ -13,8 +13,9 @@ def heads_layout(E, B, dev):
     return heads_table(E, head_list(E, BE_W_ROWS), B, dev, rows=False)
 
 
-def encoder_forward(E, img, noises=None, save=False):
-    """BE.forward (reference model/E/E.py:122-136) + BEBlock.forward (:50-85)."""
+def encoder_forward(E, img, noises=None, save=False, want_img4=True):
+    """BE.forward (reference model/E/E.py:122-136) + BEBlock.forward (:50-85).  want_img4=False: the pixel-major image copy for the
+    backward's FromRGB reduction is not emitted (a backward that wants the image gradient, or none for the parameters, never reads it)."""
     dt = _dt(E.compute_dtype)
     dev = img.device
     B, _, R, _ = img.shape
@@ -26,7 +27,7 @@ def encoder_forward(E, img, noises=None, save=False):
     stats = zeros(E.startf)
     # (training: the image also leaves in pixel-major form - the last data gradient of the backward reduces the FromRGB parameter
     #  gradients against it, autograd_enc_bwd.py)
-    want4 = save and E.startf == 16 and not ops.is_deterministic() and ops.conv_in_bwd_fromrgb_supported(B, R, R, 16, 16, dt)
+    want4 = save and want_img4 and E.startf == 16 and not ops.is_deterministic() and ops.conv_in_bwd_fromrgb_supported(B, R, R, 16, 16, dt)
     x = ops.fromrgb(img.float(), fr.weight.detach(), fr.bias.detach(), dt, stats.plain(), img4=want4)
     img4 = None
     if want4:
@@ -90,25 +91,23 @@ def encoder_forward(E, img, noises=None, save=False):
 
 
 class EncoderFunction(torch.autograd.Function):
+    """E.BE on the HIP path.  The backward takes gradients through both outputs (w and the const activation) and gives them to the
+    parameters and, where it requires one, the input image (embedding_v2 back-propagates through E(imgs2) into the generator)."""
+
     @staticmethod
     def forward(ctx, E, img, noises, *params):
-        if ctx.needs_input_grad[1]:
-            # embedding_v2_styleGAN2.py back-propagates through E(imgs2) into G: only E_Blur has the image gradient here
-            raise ops.DgeError("E.BE: the gradient w.r.t. the input image is not implemented on the HIP path (E_Blur provides it); "
-                               "detach the image or call under torch.no_grad()")
-        need = any(ctx.needs_input_grad[3:])
-        xo, w, saved = encoder_forward(E, img.detach(), noises, save=need)
+        need_img, need_params = ctx.needs_input_grad[1], any(ctx.needs_input_grad[3:])
+        xo, w, saved = encoder_forward(E, img.detach(), noises, save=need_img or need_params, want_img4=need_params and not need_img)
         ctx.E, ctx.saved_acts = E, saved
         ctx.set_materialize_grads(False)      # an output that no loss uses arrives as None in backward
         return xo, w
 
     @staticmethod
     def backward(ctx, g_x, g_w):
-        if g_x is not None:
-            # a loss on the const output (space_loss(const2, const3) in embedding_v2_styleGAN2.py): refuse instead of dropping it
-            raise ops.DgeError("E.BE: a gradient arrived through the encoder's activation output, which the hand-written backward "
-                               "does not propagate (the E_align losses use w only, E_align_s2.py:203-221); detach it")
-        if g_w is None:
-            return (None, None, None) + (None,) * len(ctx.needs_input_grad[3:])
-        grads = autograd_enc_bwd.encoder_backward(ctx.E, ctx.saved_acts, g_w.contiguous())
-        return (None, None, None) + tuple(grads)
+        nparams = len(ctx.needs_input_grad[3:])
+        if g_x is None and g_w is None:
+            return (None, None, None) + (None,) * nparams
+        frozen = not any(ctx.needs_input_grad[3:])      # no encoder parameter requires a gradient: data gradient only
+        grads, g_img = autograd_enc_bwd.encoder_backward(ctx.E, ctx.saved_acts, g_w.float().contiguous() if g_w is not None else None,
+                                                         g_x, need_img=ctx.needs_input_grad[1], params=not frozen)
+        return (None, g_img, None) + (tuple(grads) if not frozen else (None,) * nparams)

@@ -679,6 +679,135 @@ __global__ __launch_bounds__(256) void fromrgb_dgrad_kernel(const T* __restrict_
     }
 }
 
+// The last launch of the encoder backward when the encoder's INPUT carries a gradient (embedding_v2: E(imgs2) of a generated image):
+// in_bwd_kernel (coefficients computed in the launch, act = 0) + fromrgb_dgrad_kernel (+ fromrgb_bwd_kernel with FR) over one read
+// of gy and x0.  g = A*gy + Bc*x0 + Cc + extra_scale*extra[q(p)] stays in f32 registers and is never stored (the composed passes
+// round it to T in between);  gp = g*lrelu'(x0);  gimg[b,k,p] = sum_c w[c][k]*gp[c];  FR: fr_out as in_bwd_kernel<T, true>.
+// The channel chunks of a pixel sit in consecutive lanes (cpt is a power of two): their three partial sums are combined by an xor
+// butterfly inside the wave and, where a pixel spans several waves (cpt = 128, 256), through LDS in wave order - a fixed order
+// either way, so gimg is the same bits run to run in both modes.
+template <typename T, bool FR>
+__global__ __launch_bounds__(256) void in_bwd_fromrgb_img_kernel(const T* __restrict__ gy, const T* __restrict__ X, const T* __restrict__ extra,
+                                                                  const float* __restrict__ w, const float* __restrict__ img,
+                                                                  float* __restrict__ fr_out, float* __restrict__ gimg, int H, int W, int C,
+                                                                  int extra_pool, float extra_scale, InCoefSrc cs) {
+    constexpr int EP = Elem<T>::PER16;
+    constexpr int NS = FR ? 4 : 1;
+    __shared__ float red[FR ? 256 * 4 * EP : 4];
+    __shared__ float lcoef[3 * 512];
+    __shared__ float xw[2 * 4 * 3];                     // [pixel of the pair][wave][k]: pixels that span waves
+    const int b = blockIdx.y;
+    const int cpt = C / EP, ppi = 256 / cpt;
+    const int chunk = threadIdx.x % cpt, slot = threadIdx.x / cpt;
+    const int HW = H * W, UW = extra_pool ? W / 2 : W, UHW = extra_pool ? HW / 4 : HW;
+    float s[NS][EP], A[EP], Bc[EP], Cc[EP], wr[3][EP];
+    // the math of in_bwd_coef_kernel for the C channels of sample b, as in in_bwd_kernel
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const int idx = b * C + c;
+        const float r = cs.sc[idx], sft = cs.sh[idx];
+        float S2 = 0.f, S1 = 0.f;
+        if (cs.dots) { const float2 ss = sum_slot_pairs(cs.dots + (size_t)idx * 2, (size_t)cs.B * C * 2, cs.nslot); S2 = ss.x; S1 = ss.y; }
+        const float m1 = S1 * cs.inv_n, m2 = (r * S2 + sft * S1) * cs.inv_n;
+        const float mu = cs.musig[(size_t)b * 2 * C + c], sg = cs.musig[(size_t)b * 2 * C + C + c];
+        const float gmu = cs.gms ? cs.gms[(size_t)b * 2 * C + c] : 0.f, gsg = cs.gms ? cs.gms[(size_t)b * 2 * C + C + c] : 0.f;
+        const float k = sg > 0.f ? gsg * cs.inv_n / sg : 0.f;
+        lcoef[c * 3 + 0] = r;
+        lcoef[c * 3 + 1] = -r * r * m2 + k;
+        lcoef[c * 3 + 2] = -r * m1 - r * m2 * sft + gmu * cs.inv_n - k * mu;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < EP; e++) {
+#pragma unroll
+        for (int k = 0; k < NS; k++) s[k][e] = 0.f;
+        const int c = chunk * EP + e;
+        A[e] = lcoef[c * 3]; Bc[e] = lcoef[c * 3 + 1]; Cc[e] = lcoef[c * 3 + 2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) wr[k][e] = w[(size_t)c * 3 + k];
+    }
+    // two pixels per thread and iteration, all loads issued before the arithmetic; the trip count is uniform over the workgroup
+    const int stride = gridDim.x * ppi;
+    for (int p0 = blockIdx.x * ppi; p0 < HW; p0 += 2 * stride) {
+        const int pp[2] = {p0 + slot, p0 + slot + stride};
+        bool ok[2]; uint4 gv[2], xq[2], ev[2]; float im[2][3];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            ok[h] = pp[h] < HW;
+            gv[h] = xq[h] = ev[h] = make_uint4(0, 0, 0, 0);
+            im[h][0] = im[h][1] = im[h][2] = 0.f;
+            if (ok[h]) {
+                const size_t o = ((size_t)b * HW + pp[h]) * C + chunk * EP;
+                gv[h] = *(const uint4*)(gy + o); xq[h] = *(const uint4*)(X + o);
+                if (extra) {
+                    const int q = extra_pool ? (pp[h] / W / 2) * UW + (pp[h] % W) / 2 : pp[h];
+                    ev[h] = *(const uint4*)(extra + ((size_t)b * UHW + q) * C + chunk * EP);
+                }
+                if constexpr (FR) {
+                    const float* ib = img + (size_t)b * 3 * HW;
+#pragma unroll
+                    for (int k = 0; k < 3; k++) im[h][k] = ib[(size_t)k * HW + pp[h]];
+                }
+            }
+        }
+        float a[2][3];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            float g[EP], xv[EP], ex[EP];
+            unpack16(gv[h], g, (T*)nullptr);
+            unpack16(xq[h], xv, (T*)nullptr);
+            unpack16(ev[h], ex, (T*)nullptr);
+            a[h][0] = a[h][1] = a[h][2] = 0.f;
+            if (ok[h]) {                                 // (a pixel out of range contributes zeros to the butterfly below)
+#pragma unroll
+                for (int e = 0; e < EP; e++) {
+                    float ge = A[e] * g[e] + Bc[e] * xv[e] + Cc[e];
+                    if (extra) ge += extra_scale * ex[e];
+                    const float gp = ge * (xv[e] > 0.f ? 1.f : 0.2f);
+                    a[h][0] += gp * wr[0][e]; a[h][1] += gp * wr[1][e]; a[h][2] += gp * wr[2][e];
+                    if constexpr (FR) { s[0][e] += gp * im[h][0]; s[1][e] += gp * im[h][1]; s[2][e] += gp * im[h][2]; s[3][e] += gp; }
+                }
+            }
+        }
+        // every lane takes part: the partners of a lane hold chunks of the same pixel, in range or not together
+        for (int m = 1; m < cpt && m < 64; m <<= 1) {
+#pragma unroll
+            for (int h = 0; h < 2; h++)
+#pragma unroll
+                for (int k = 0; k < 3; k++) a[h][k] += __shfl_xor(a[h][k], m, 64);
+        }
+        if (cpt > 64) {                                 // uniform over the workgroup: cpt / 64 waves per pixel
+            const int wave = threadIdx.x >> 6, wpp = cpt >> 6;
+            if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                for (int h = 0; h < 2; h++)
+#pragma unroll
+                    for (int k = 0; k < 3; k++) xw[(h * 4 + wave) * 3 + k] = a[h][k];
+            }
+            __syncthreads();
+            if (chunk == 0) {
+#pragma unroll
+                for (int h = 0; h < 2; h++)
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        float t = 0.f;
+                        for (int j = 0; j < wpp; j++) t += xw[(h * 4 + wave + j) * 3 + k];
+                        a[h][k] = t;
+                    }
+            }
+            __syncthreads();
+        }
+        if (chunk == 0) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                if (!ok[h]) continue;
+#pragma unroll
+                for (int k = 0; k < 3; k++) gimg[((size_t)b * 3 + k) * HW + pp[h]] = a[h][k];
+            }
+        }
+    }
+    if constexpr (FR) block_chan_flush<EP, 4>(s, cpt, ppi, fr_out + (size_t)b * C * 4, C, red);
+}
+
 // upscale2d (nearest x2) materialised: y[b,2y+dy,2x+dx,c] = scale * x[b,y,x,c]
 template <typename T>
 __global__ __launch_bounds__(256) void nearest_up2_kernel(const T* __restrict__ x, T* __restrict__ y, int H, int W, int C, float scale, long total16) {
@@ -1055,6 +1184,30 @@ extern "C" int dge_fromrgb_dgrad(const void* gx, const void* x0, const float* w,
     if (dtype == DGE_BF16) hipLaunchKernelGGL(fromrgb_dgrad_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)gx, (const bf16_t*)x0, w, gimg, HW, C);
     else hipLaunchKernelGGL(fromrgb_dgrad_kernel<float>, grid, dim3(256), 0, s, (const float*)gx, (const float*)x0, w, gimg, HW, C);
     DGE_LAUNCH_CHECK("fromrgb_dgrad");
+    return 0;
+}
+
+// dge_in_bwd_fused (act = 0) + dge_fromrgb_dgrad (+ dge_fromrgb_bwd when img / out4 are given) in one launch: the gradient w.r.t. the
+// FromRGB output is neither stored nor rounded
+extern "C" int dge_in_bwd_fromrgb_img(const void* gy, const void* x0, const float* dots, int nslot, const float* gms, const float* musig,
+                                      const float* sc, const float* sh, int npix, const void* extra, const float* w, const float* img,
+                                      float* out4, float* gimg, int B, int H, int W, int C, int extra_pool, float extra_scale, int dtype,
+                                      hipStream_t s) {
+    DGE_CHECK(gy && x0 && w && gimg && C <= 512 && nslot >= 1 && musig && sc && sh && npix > 0,
+              "in_bwd_fromrgb_img: needs gy, x0, w, gimg, C <= 512, musig, sc, sh");
+    DGE_CHECK((img == nullptr) == (out4 == nullptr), "in_bwd_fromrgb_img: img and out4 go together");
+    DGE_CHECK(B >= 1 && H >= 1 && W >= 1 && (!extra || !extra_pool || (H % 2 == 0 && W % 2 == 0)), "in_bwd_fromrgb_img: bad shape %d x %d x %d", B, H, W);
+    const int ep = dtype == DGE_BF16 ? 8 : 4;
+    DGE_CHECK(CHAN_OK(C, ep), "in_bwd_fromrgb_img: unsupported channel count %d", C);
+    dim3 grid(dge_stream_grid(H * W, 256 / (C / ep), B), B);
+    DGE_CHECK(!out4 || dge_det_fits(B, grid.x, (long long)C * 4), "in_bwd_fromrgb_img: deterministic workspace too small");
+    InCoefSrc cs{dots, gms, musig, sc, sh, nslot, B, 1.0f / (float)npix};
+#define DGE_IBI(T, FR) hipLaunchKernelGGL((in_bwd_fromrgb_img_kernel<T, FR>), grid, dim3(256), 0, s, (const T*)gy, (const T*)x0, (const T*)extra, w, img, out4, gimg, H, W, C, extra_pool, extra_scale, cs)
+    if (out4) { if (dtype == DGE_BF16) DGE_IBI(bf16_t, true); else DGE_IBI(float, true); }
+    else { if (dtype == DGE_BF16) DGE_IBI(bf16_t, false); else DGE_IBI(float, false); }
+#undef DGE_IBI
+    dge_note_kernel("in_bwd_fromrgb_img<%s,%s>", dtype == DGE_BF16 ? "bf16" : "f32", out4 ? "fr" : "data");
+    DGE_LAUNCH_CHECK("in_bwd_fromrgb_img");
     return 0;
 }
 

@@ -1,5 +1,6 @@
 """Real-image inversion of the reference's v2 scripts (embedding_v2_styleGAN1.py:71-189, embedding_v2_styleGAN2.py:82-210) on the
-HIP path, for StyleGAN1 (`--mtype 1`: Gs + E_Blur) and StyleGAN2 (`--mtype 2`: StyleGAN2 synthesis + E_Blur), in two modes:
+HIP path, for StyleGAN1 (`--mtype 1`: Gs + E_Blur) and StyleGAN2 (`--mtype 2`: StyleGAN2 synthesis + E_Blur), in two modes
+(`--encoder be` puts E.BE, the encoder E_align trains, in E_Blur's place):
 
   mode "E" (--optimizeE true):  the encoder is re-loaded per image group and fine-tuned; w1 = E(imgs1) every iteration.
   mode "W" (--optimizeE false): the encoder is frozen and the W+ code w1 itself is optimised (LREQAdam on the leaf w1).
@@ -434,15 +435,29 @@ def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=Non
     return r
 
 
+ENCODERS = ("blur", "be")
+
+
+def _be_encoder(img_size, start_features, compute_dtype, device, maxf):
+    """E.BE (encoder.BE, the encoder E_align trains) sized for `img_size`: its checkpoints load unchanged."""
+    from .encoder import BE
+    return BE(start_features, maxf or 512, int(math.log2(img_size) - 1), compute_dtype=compute_dtype).to(device)
+
+
 def build_models_v2(mtype, img_size=1024, start_features=16, compute_dtype="bf16", device="cuda", seed=0, lpips=True,
-                    fmaps_base=None, fmaps_max=None, enc_maxf=None):
+                    fmaps_base=None, fmaps_max=None, enc_maxf=None, encoder="blur"):
     """mtype 1: StyleGAN1 Gs + E_Blur (embedding.build_models); mtype 2: StyleGAN2Generator (eval, frozen, fixed noise) +
-    BlurBE(layer_count = log2(res) - 1) - 18 W+ rows at 1024^2, 10 at 64^2.  Seeded random-init weights."""
+    BlurBE(layer_count = log2(res) - 1) - 18 W+ rows at 1024^2, 10 at 64^2.  Seeded random-init weights.
+    encoder="be": E.BE(start_features, enc_maxf or 512, log2(res) - 1) in place of E_Blur, for both mtypes."""
     from .lpips import LPIPS
+    if encoder not in ENCODERS:
+        raise ValueError(f"embedding_v2: encoder must be one of {ENCODERS}, got {encoder!r}")
     torch.manual_seed(seed)
     if mtype == 1:
         from .embedding import build_models
         G, E, LP = build_models(img_size, start_features, compute_dtype, device=device, seed=seed)
+        if encoder == "be":
+            E = _be_encoder(img_size, start_features, compute_dtype, device, enc_maxf)
         return G, E, (LP if lpips else None)
     if mtype != 2:
         raise ValueError("embedding_v2: --mtype 1 (StyleGAN1) or 2 (StyleGAN2); BigGAN / PGGAN inversion is not offered")
@@ -452,7 +467,10 @@ def build_models_v2(mtype, img_size=1024, start_features=16, compute_dtype="bf16
     G.eval()
     for p in G.parameters():
         p.requires_grad_(False)
-    E = blur_encoder(img_size, start_features, compute_dtype, device, maxf=enc_maxf or 512)
+    if encoder == "be":
+        E = _be_encoder(img_size, start_features, compute_dtype, device, enc_maxf)
+    else:
+        E = blur_encoder(img_size, start_features, compute_dtype, device, maxf=enc_maxf or 512)
     LP = LPIPS(compute_dtype=compute_dtype).to(device) if lpips else None
     return G, E, LP
 
@@ -493,6 +511,8 @@ def make_parser():
     p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise W+ directly")
     p.add_argument("--independent", type=strict_bool, default=False,
                    help="true (with --optimizeE false): every image of a batch is an inversion of its own, equal to its batch-1 run")
+    p.add_argument("--encoder", choices=ENCODERS, default="blur",
+                   help="blur: E_Blur; be: E.BE, the encoder E_align trains (--checkpoint_dir_E then takes its checkpoints)")
     p.add_argument("--beta", type=float, default=None, help="weight of ||w1||_p: default 1e-3 (mtype 1), 3e-4 (mtype 2)")
     p.add_argument("--norm_p", type=int, default=None, help="p of ||w1||_p (default 2)")
     p.add_argument("--truncation", type=float, default=None, help="StyleGAN2: psi of avg + psi*(w1 - avg) (default 0.7; 1: none)")
@@ -534,7 +554,7 @@ def main(argv=None):
     from .infer import save_image_grid
     dev = "cuda"
     G, E, LP = build_models_v2(args.mtype, args.img_size, args.start_features, args.compute_dtype, device=dev, seed=args.seed,
-                               fmaps_base=args.fmaps_base, fmaps_max=args.fmaps_max, enc_maxf=args.enc_maxf)
+                               fmaps_base=args.fmaps_base, fmaps_max=args.fmaps_max, enc_maxf=args.enc_maxf, encoder=args.encoder)
     load_checkpoints(G, E, args.mtype, args.checkpoint_dir_GAN, args.checkpoint_dir_E)
     load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
     out = args.experiment_dir or "./realimg_embedding_result/7"

@@ -1000,6 +1000,33 @@ def in_bwd_fromrgb(gy, x0, coef, img, extra=None, extra_pool=False, extra_scale=
     return _sum_planar(part, torch.empty((4, Cc), dtype=torch.float32, device=x0.device), defer)
 
 
+def in_bwd_fromrgb_img_supported(Cc, dtype):
+    """Whether dge_in_bwd_fromrgb_img takes the channel count (its own checks: C <= 512, 16-byte chunks that tile a workgroup)."""
+    cpt, rem = divmod(int(Cc), 8 if dtype == BF16 else 4)
+    return rem == 0 and 1 <= cpt <= 256 and 256 % cpt == 0 and Cc <= 512
+
+
+def in_bwd_fromrgb_img(gy, x0, coef, w, img=None, extra=None, extra_pool=False, extra_scale=1.0, defer=None):
+    """Last step of the encoder backward when the image carries a gradient: in_bwd (`coef` = (dots, gms, musig, sc, sh, npix)) on the
+    FromRGB output x0, the FromRGB data gradient of the result -> g_img [B,3,H,W] f32 and, with `img`, the FromRGB parameter
+    gradients [4, C] as in_bwd_fromrgb gives them (None without).  The gradient w.r.t. x0 is never stored.  w: FromRGB's weight."""
+    B, H, W, Cc = x0.shape
+    dots, gms, musig, sc, sh, npix = coef
+    nslot = 1
+    if isinstance(dots, SlotStats):
+        nslot, dots = dots.nslot, dots.buf
+    gimg = torch.empty((B, 3, H, W), dtype=torch.float32, device=x0.device)
+    part = zeros((B, Cc, 4), x0.device) if img is not None else None
+    check(lib().dge_in_bwd_fromrgb_img(_p(gy), _p(x0), _f32(dots), nslot, _f32(gms), _f32(musig), _f32(sc), _f32(sh), int(npix), _p(extra),
+                                       _f32(w.reshape(Cc, 3).contiguous()), _f32(img.contiguous()) if img is not None else None, _p(part),
+                                       _p(gimg), B, H, W, Cc, 1 if extra_pool else 0, float(extra_scale), dtype_of(x0), _stream()),
+          "dge_in_bwd_fromrgb_img")
+    log_kernel()
+    if part is None:
+        return gimg, None
+    return gimg, _sum_planar(part, torch.empty((4, Cc), dtype=torch.float32, device=x0.device), defer)
+
+
 def conv_pool_supported(B, H, W, cin, cout, ksize, dtype):
     return bool(lib().dge_conv_pool_supported(B, H, W, cin, cout, ksize, dtype))
 

@@ -415,6 +415,13 @@ int dge_fromrgb_bwd(const void* gx, const void* x0, const float* img, float* out
 int dge_in_bwd_fromrgb(const void* gy, const void* x0, const float* dots, int nslot, const float* gms, const float* musig,
                        const float* sc, const float* sh, int npix, const void* extra, const float* img, float* out4,
                        int B, int H, int W, int C, int extra_pool, float extra_scale, int dtype, dge_stream_t stream);
+/* dge_in_bwd_fused (act = 0), dge_fromrgb_dgrad and - with img / out4, NULL as a pair - dge_fromrgb_bwd as ONE launch: the last step
+ * of the encoder backward when the input image carries a gradient (embedding_v2: E(imgs2)).  The gradient w.r.t. x0 stays in f32
+ * registers; gimg [B,3,HW] f32 = sum_c w[c][k] * g_x0 * lrelu'(x0), w [C,3] f32; out4 [B,C,4] (pre-zeroed) as dge_in_bwd_fromrgb.
+ * C <= 512.  gimg is the same bits run to run; out4 is in deterministic mode. */
+int dge_in_bwd_fromrgb_img(const void* gy, const void* x0, const float* dots, int nslot, const float* gms, const float* musig,
+                           const float* sc, const float* sh, int npix, const void* extra, const float* w, const float* img, float* out4,
+                           float* gimg, int B, int H, int W, int C, int extra_pool, float extra_scale, int dtype, dge_stream_t stream);
 /* Forward of every inver_mod head of the encoder in one launch (E.py:51-53,64-66): w[b, gcol_l + o] = musig_l[b,:] . W_l[o,:] + bias_l[o]
  * over the same entry table as dge_heads_bwd (entries carry the bias pointer); w [B, ldw]. */
 int dge_heads_fwd(const void* dev_entries, int n, const float* musig_all, float* w, int ldw, int B, int O, dge_stream_t stream);

@@ -4,7 +4,15 @@ launch, W+ optimisation and encoder fine-tuning - dev/bench tool.  Random-init w
 --independent: W mode under hipGraph replay instead - batch 1 on the coupled path against B independent rows per iteration
 (--batches 2,4,8), one process, the configurations alternating, medians over --rounds rounds; then the loss stage of one iteration
 apart: the per-sample kernels (losses.image_loss_tsa_rows) against the per-row composition (image_loss_tsa on every one-row slice).
-    python tools/bench_embed_v2.py --independent [--batches 2,4,8] [--rounds 5]"""
+    python tools/bench_embed_v2.py --independent [--batches 2,4,8] [--rounds 5]
+--encoder be: E.BE (the encoder E_align trains) in E_Blur's place, in every mode above.
+--compare-encoders: W mode under hipGraph replay, E.BE against E_Blur at batch 1 (coupled) and --batches independent rows, one
+process, the configurations alternating, medians over --rounds rounds.
+--last-stage: the last stage of E.BE's backward alone when the image carries a gradient, at [B,1024,1024,16] for B in --batches:
+the one launch (ops.in_bwd_fromrgb_img) against the passes it replaces (in_bwd -> fromrgb_dgrad [-> fromrgb_bwd]), frozen and
+trained encoder, alternating, medians over --rounds rounds.
+    python tools/bench_embed_v2.py --compare-encoders --batches 8
+    python tools/bench_embed_v2.py --last-stage --batches 1,8"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,9 +22,12 @@ from dge_amd.embedding_v2 import LatentEmbedStep, build_models_v2
 ap = argparse.ArgumentParser()
 ap.add_argument("--img-size", type=int, default=1024); ap.add_argument("--start-features", type=int, default=16)
 ap.add_argument("--iters", type=int, default=20); ap.add_argument("--dtype", default="bf16")
+ap.add_argument("--encoder", choices=("blur", "be"), default="blur"); ap.add_argument("--compare-encoders", action="store_true")
+ap.add_argument("--last-stage", action="store_true")
 ap.add_argument("--independent", action="store_true"); ap.add_argument("--batches", default="2,4,8"); ap.add_argument("--rounds", type=int, default=5)
 a = ap.parse_args()
 res = {}
+ENC_NAME = {"blur": "E_Blur", "be": "E.BE"}
 
 
 def timed(run, n):
@@ -37,7 +48,7 @@ def bench_independent():
     from dge_amd import losses
     from dge_amd.embedding_v2 import IMG_WEIGHTS
     batches = [int(v) for v in a.batches.split(",")]
-    G, E, LP = build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0)
+    G, E, LP = build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0, encoder=a.encoder)
     with torch.no_grad():
         imgs = G.synthesis(torch.randn(max(batches), G.synthesis.num_layers, 512, device="cuda"))["image"].detach().clamp(-1, 1).contiguous()
     runs = {}
@@ -55,7 +66,7 @@ def bench_independent():
     for name, (st, B) in runs.items():
         m = median(ms[name])
         res[name] = dict(ms_per_iteration=round(m, 3), ms_per_image_iteration=round(m / B, 3), rounds=[round(v, 3) for v in ms[name]])
-        print(f"embedding_v2 W replay, StyleGAN2-{a.img_size} + E_Blur, {a.dtype}, {name}: {m:.2f} ms/iteration, {m / B:.2f} ms/image-iteration", flush=True)
+        print(f"embedding_v2 W replay, StyleGAN2-{a.img_size} + {ENC_NAME[a.encoder]}, {a.dtype}, {name}: {m:.2f} ms/iteration, {m / B:.2f} ms/image-iteration", flush=True)
     runs.clear()
     # the loss stage of one iteration (value + analytic gradient of the three windows), eager launches
     for B in batches:
@@ -75,11 +86,76 @@ def bench_independent():
     print(json.dumps(res))
 
 
+def bench_compare_encoders():
+    batches = [int(v) for v in a.batches.split(",")]
+    models = {enc: build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0, encoder=enc) for enc in ("blur", "be")}
+    G = models["blur"][0]
+    with torch.no_grad():
+        imgs = G.synthesis(torch.randn(max(batches + [1]), G.synthesis.num_layers, 512, device="cuda"))["image"].detach().clamp(-1, 1).contiguous()
+    runs = {}
+    for name, B, ind in [("B1_coupled", 1, False)] + [(f"B{B}_independent", B, True) for B in batches]:
+        for enc, (Gm, E, LP) in models.items():
+            st = LatentEmbedStep(Gm, E, LP, mode="W", generator="sg2", independent=ind)
+            st.begin_image(imgs[:B].contiguous())
+            st.capture(imgs[:B].contiguous(), warmup=1)
+            for _ in range(3):
+                st.replay()
+            runs[f"{name}_{enc}"] = (st, B)
+    ms = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for name, (st, B) in runs.items():
+            ms[name].append(timed(st.replay, a.iters))
+    for name, (st, B) in runs.items():
+        m = median(ms[name])
+        res[name] = dict(ms_per_iteration=round(m, 3), ms_per_image_iteration=round(m / B, 3), rounds=[round(v, 3) for v in ms[name]])
+        print(f"embedding_v2 W replay, StyleGAN2-{a.img_size}, {a.dtype}, {name}: {m:.2f} ms/iteration, {m / B:.2f} ms/image-iteration", flush=True)
+    print(json.dumps(res))
+
+
+def bench_last_stage():
+    """Synthetic operands of block 0's last stage (conv_1's data gradient g_y1, the FromRGB output x0, the pooled skip gradient)."""
+    from dge_amd import ops
+    R_, C = a.img_size, a.start_features
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    for B in [int(v) for v in a.batches.split(",")]:
+        gen = torch.Generator(device="cuda").manual_seed(B)
+        rn = lambda *s: torch.randn(*s, device="cuda", generator=gen)
+        gy, x0, extra = rn(B, R_, R_, C).to(dt), rn(B, R_, R_, C).to(dt), rn(B, R_ // 2, R_ // 2, C).to(dt)
+        coef = (rn(B, C, 2), rn(B, 2 * C), torch.cat((rn(B, C), rn(B, C).abs() + 0.5), 1), rn(B, C).abs() + 0.5, rn(B, C), R_ * R_)
+        w, img = rn(C, 3, 1, 1), rn(B, 3, R_, R_)
+        kw = dict(extra=extra, extra_pool=True, extra_scale=0.25)
+
+        def composed(params):
+            gx0 = ops.in_bwd(gy, x0, coef, **kw)
+            ops.fromrgb_dgrad(gx0, x0, w)
+            if params:
+                ops.fromrgb_bwd(gx0, x0, img, planar=True)
+        cfg = {"frozen_fused": lambda: ops.in_bwd_fromrgb_img(gy, x0, coef, w, None, **kw), "frozen_composed": lambda: composed(False),
+               "trained_fused": lambda: ops.in_bwd_fromrgb_img(gy, x0, coef, w, img, **kw), "trained_composed": lambda: composed(True)}
+        for f in cfg.values():
+            for _ in range(3):
+                f()
+        t = {k: [] for k in cfg}
+        for _ in range(a.rounds):
+            for k, f in cfg.items():
+                t[k].append(timed(f, a.iters) * 1e3)
+        res[f"last_stage_B{B}"] = {k: dict(us=round(median(v), 1), rounds=[round(q, 1) for q in v]) for k, v in t.items()}
+        print(f"last backward stage [{B},{R_},{R_},{C}] {a.dtype} (us, host-timed over {a.iters} back-to-back launches): "
+              + ", ".join(f"{k} {median(v):.1f}" for k, v in t.items()), flush=True)
+    print(json.dumps(res))
+
+
 if a.independent:
     bench_independent()
     sys.exit(0)
+if a.compare_encoders:
+    bench_compare_encoders()
+    sys.exit(0)
+if a.last_stage:
+    bench_last_stage()
+    sys.exit(0)
 for mode in ("W", "E"):
-    G, E, LP = build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0)
+    G, E, LP = build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0, encoder=a.encoder)
     with torch.no_grad():
         imgs1 = G.synthesis(torch.randn(1, G.synthesis.num_layers, 512, device="cuda"))["image"].detach().clamp(-1, 1).contiguous()
     for launch in ("eager", "graph"):
@@ -99,7 +175,7 @@ for mode in ("W", "E"):
         torch.cuda.synchronize()
         dt = (time.time() - t0) / a.iters
         res[f"{mode}_{launch}_ms"] = round(dt * 1e3, 2)
-        print(f"embedding_v2 loop, StyleGAN2-{a.img_size} + E_Blur, batch 1, {a.dtype}, mode {mode}, {launch}: {dt * 1e3:.2f} ms/iteration",
+        print(f"embedding_v2 loop, StyleGAN2-{a.img_size} + {ENC_NAME[a.encoder]}, batch 1, {a.dtype}, mode {mode}, {launch}: {dt * 1e3:.2f} ms/iteration",
               flush=True)
         del st
 print(json.dumps(res))

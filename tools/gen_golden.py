@@ -1241,15 +1241,17 @@ def gen_latent_fixtures():
 
 SECTIONS["latent"] = gen_latent_fixtures
 
-def gen_embed_v2():
+def gen_embed_v2(enc_cls=None, cases=None, name="embed_v2.npz"):
     """Two iterations of the reference's v2 inversion loop body (embedding_v2_styleGAN1.py:82-131, embedding_v2_styleGAN2.py:86-149) for
     StyleGAN1 / StyleGAN2 x encoder / W+ optimisation, batch 1, 64x64, restated with the decisions of embedding_v2.py's docstring:
     all three image windows carry gradient, StyleGAN1 encodes imgs2 before the phase-1 step and StyleGAN2 after it, W-mode
     StyleGAN1 const2 is a constant, W-mode StyleGAN2 has no const term, the StyleGAN2 generator is synthesis(avg + 0.7*(w - avg))
-    with its fixed noise.  Every noise tensor is captured (names embed_v2.<case>.it<k>.noise<i>)."""
+    with its fixed noise.  Every noise tensor is captured (names embed_v2.<case>.it<k>.noise<i>).
+    enc_cls: the reference encoder class (default E_Blur.BE); cases: the "<gen>_<mode>" cases to run (default all four)."""
     import warnings
     import model.stylegan1.net as SG1
     import model.E.E_Blur as EB
+    enc_cls = enc_cls or EB.BE
     from model.stylegan2_generator import StyleGAN2Generator
     import training_utils as TU
     from model.utils.custom_adam import LREQAdam
@@ -1264,6 +1266,8 @@ def gen_embed_v2():
     for gen in ("sg1", "sg2"):
         for mode in ("E", "W"):
             tag = f"{gen}_{mode}"
+            if cases is not None and tag not in cases:
+                continue
             if gen == "sg1":
                 Gs = SG1.Generator(startf=16, maxf=64, layer_count=L, latent_size=512, channels=3)
                 sd = R.fill_encoder(shapes_of(Gs.state_dict()), seed=43)
@@ -1284,7 +1288,7 @@ def gen_embed_v2():
                 avg = G2.truncation.w_avg
                 gfun = lambda w: G2.synthesis(avg + 0.7 * (w - avg), randomize_noise=False)["image"]
                 beta = 3e-4
-            E = EB.BE(startf=16, maxf=64, layer_count=L)
+            E = enc_cls(startf=16, maxf=64, layer_count=L)
             esd = R.fill_encoder(shapes_of(E.state_dict()), seed=71)
             for k in esd:
                 if k.endswith("blur.weight"):
@@ -1369,10 +1373,50 @@ def gen_embed_v2():
                 else:
                     ck = R.checksum({"w1": w1.detach()})
                 out[f"{pre}_param_checksum"] = np.array(ck)
-    save_npz("embed_v2.npz", **out)
+    save_npz(name, **out)
 
 
 SECTIONS["embed_v2"] = gen_embed_v2
+
+
+def gen_embed_v2_be():
+    """gen_embed_v2 with the reference E.BE (model/E/E.py) as the encoder: what `embedding_v2 --encoder be` runs."""
+    import model.E.E as EE
+    gen_embed_v2(EE.BE, ("sg2_E", "sg2_W", "sg1_E"), "embed_v2_be.npz")
+
+
+SECTIONS["embed_v2_be"] = gen_embed_v2_be
+
+
+def gen_encgrad_be():
+    """Gradients of the reference E.BE w.r.t. every parameter AND the input image for a seeded linear functional of both outputs
+    (x, w) - what embedding_v2_styleGAN2.py back-propagates through E(imgs2).  As gen_encblurgrad."""
+    import model.E.E as EE
+    E = EE.BE(16, 64, 5)
+    E.load_state_dict(R.fill_encoder(shapes_of(E.state_dict()), seed=81))
+    img = R.randn("ebe.img", (2, 3, 64, 64), 81, 0.5).requires_grad_(True)
+
+    def run():
+        with _NoiseFeeder("ebe", 81):
+            return E(img)
+    nudged, margin = clear_kinks([run], *enc_kink_owners(E, "has_last_conv"))
+    with _NoiseFeeder("ebe", 81) as nf:
+        x, w = E(img)
+    gx, gw = R.randn("ebe.gx", tuple(x.shape), 83), R.randn("ebe.gw", tuple(w.shape), 83)
+    loss = (x * gx).sum() + (w * gw).sum()
+    loss.backward()
+    out = {"loss": loss.detach(), "g_img": img.grad, "x": x.detach(), "w": w.detach(), "noise_shapes": np.array([list(s_) for s_ in nf.log]),
+           "kink_margin": np.array(margin), **{"param:" + k: v for k, v in nudged.items()}}
+    for k, p_ in E.named_parameters():
+        if p_.grad is None:
+            continue
+        g = p_.grad
+        out["norm:" + k] = g.norm()
+        out["grad:" + k] = g if g.numel() <= 4096 else g.flatten()[:4096]      # (the norm pins the rest: keeps the file small)
+    save_npz("enc_be_grad.npz", **out)
+
+
+SECTIONS["encgrad_be"] = gen_encgrad_be
 
 def _grad_entries(model, out, full_max=16384):
     for k, p_ in model.named_parameters():
