@@ -172,6 +172,7 @@ SIGNATURES = {
     "dge_space_loss_bwd_split": [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "dge_in_bwd_fromrgb": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "dge_in_bwd_fromrgb_img": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "dge_affine_bwd_fromrgb_img": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
     "dge_in_bwd_fused": [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P],
     "dge_sum_slots_planar_multi": [C.POINTER(SumPlanarEntry), _I, _P],
     "dge_heads_fwd": [_P, _I, _P, _P, _I, _I, _I, _P],

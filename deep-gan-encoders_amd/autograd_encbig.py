@@ -162,7 +162,19 @@ def _affine_coef(a):
     return torch.stack((a.float(), z, z), dim=-1)
 
 
-def big_encoder_backward(E, saved, g_z, g_cv=None):
+FUSE_IMG_GRAD = True          # block 0's last stage with an image gradient: one launch (False: the composed passes, for timing)
+
+
+def big_encoder_backward(E, saved, g_z, g_cv=None, need_img=False, params=True):
+    """-> the gradients for E.parameters() in registration order; with need_img the pair (those, g_img [B,3,R,R] f32).
+    need_img: the input image carries a gradient (embedding_v2_biggan: E(imgs2) of a generated image).  Block 0's last stage is then
+    ops.affine_bwd_fromrgb_img - a1 * g_u1 + the pooled skip gradient, the FromRGB data gradient and (trained encoder) the FromRGB
+    parameter reductions over one read of g_u1 and x0 - or, where its kernel refuses the channel count, in_bwd -> fromrgb_dgrad
+    (-> fromrgb_bwd).
+    params=False (frozen encoder: the W inversion mode): the data gradient alone.  No weight gradient, bias / noise-weight reduction,
+    conditional-batch-norm parameter gradient, dots epilogue (g_x = a * g needs none), FromRGB reduction or head weight gradient is
+    launched, and every parameter gradient is None.
+    The default call issues the launches of E_align_s2 --mtype 4's backward, in their order."""
     if saved is None:
         raise RuntimeError("E_BIG forward ran without saved activations")
     cache = pack_cache(E)
@@ -173,57 +185,84 @@ def big_encoder_backward(E, saved, g_z, g_cv=None):
     cond = saved["cond"]
     grads = {}
     pend = []          # conditional-batch-norm parameter gradients: recorded per norm, run grouped behind the block loop
-    g_cvt = linear_backward(E.new_final_2, g_z.float().contiguous(), saved["c_v"], grads, "new_final_2")
+    dots = None if params else False
+    g_cvt = linear_backward(E.new_final_2, g_z.float().contiguous(), saved["c_v"], grads, "new_final_2", params)
     if g_cv is not None:
         g_cvt = g_cvt + g_cv.float()
-    g_flat = linear_backward(E.new_final_1, g_cvt.contiguous(), saved["flat"], grads, "new_final_1")
+    g_flat = linear_backward(E.new_final_1, g_cvt.contiguous(), saved["flat"], grads, "new_final_1", params)
     L = len(saved["blocks"])
     C_last = E.decode_block[L - 1].inputs
     g_out = ops.nchw_to_nhwc(g_flat.view(B, C_last, R >> (L - 1), R >> (L - 1)), B, dt)
+    g_img = fr = None
     for j, blk, rec, pre, Cc, C2, H, _ in blocks(E, R, saved):
         x, x1 = rec["x"], rec["x1"]
-        red1 = ops.zeros((Cc, 2), dev)
+        red1 = ops.zeros((Cc, 2), dev) if params else None
         extra, extra_pool, extra_scale = None, False, 1.0
         if blk.has_second_conv:
             has3 = Cc != C2
-            red2 = ops.zeros((C2, 2), dev)
+            red2 = ops.zeros((C2, 2), dev) if params else None
             # x2 = lrelu(pre2) [then a second lrelu when has3: slope 0.2*0.2 on the negative side]; out = avg_pool(x2 + res)
             g_pre2 = ops.act_bwd(g_out, rec["x2"], rec["n2"], pool=True, scale=0.25, red=red2, slope=0.04 if has3 else 0.2)
-            red_param_grads(grads, pre, 2, red2)
-            g_u2, dots2 = conv_bwd(cache, grads, pre + "conv_2", blk.conv_2, g_pre2, x1, dt, H, rec["a2"], rec["b2"])
-            _cbn_param_grads(blk.batch_norm_2, rec["c2"], dots2, cond, grads, pre + "batch_norm_2", pend)
+            if params:
+                red_param_grads(grads, pre, 2, red2)
+            g_u2, dots2 = conv_bwd(cache, grads, pre + "conv_2", blk.conv_2, g_pre2, x1, dt, H, rec["a2"], rec["b2"], params, dots=dots)
+            if params:
+                _cbn_param_grads(blk.batch_norm_2, rec["c2"], dots2, cond, grads, pre + "batch_norm_2", pend)
             g_pre1 = ops.in_bwd(g_u2, x1, _affine_coef(rec["a2"]), noise=rec["n1"], act=True, red=red1)
             if has3:
                 xp = rec["xp"]
-                grads[pre + "conv_3.bias"] = ops.chan_sum(g_out)
-                g_u3, dots3 = conv_bwd(cache, grads, pre + "conv_3", blk.conv_3, g_out, xp, dt, None, rec["a3"], rec["b3"])
-                _cbn_param_grads(blk.batch_norm_3, rec["c3"], dots3, cond, grads, pre + "batch_norm_3", pend)
+                if params:
+                    grads[pre + "conv_3.bias"] = ops.chan_sum(g_out)
+                g_u3, dots3 = conv_bwd(cache, grads, pre + "conv_3", blk.conv_3, g_out, xp, dt, None, rec["a3"], rec["b3"], params, dots=dots)
+                if params:
+                    _cbn_param_grads(blk.batch_norm_3, rec["c3"], dots3, cond, grads, pre + "batch_norm_3", pend)
                 extra = ops.in_bwd(g_u3, xp, _affine_coef(rec["a3"]))          # a3 * g at the pooled resolution
             else:
                 extra = g_out
             extra_pool, extra_scale = True, 0.25
         else:
             g_pre1 = ops.act_bwd(g_out, x1, rec["n1"], pool=False, scale=1.0, red=red1)
-        red_param_grads(grads, pre, 1, red1)
-        g_u1, dots1 = conv_bwd(cache, grads, pre + "conv_1", blk.conv_1, g_pre1, x, dt, H, rec["a1"], rec["b1"])
-        _cbn_param_grads(blk.batch_norm_1, rec["c1"], dots1, cond, grads, pre + "batch_norm_1", pend)
-        g_out = ops.in_bwd(g_u1, x, _affine_coef(rec["a1"]), extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
-    _cbn_param_grads_flush(pend, cond, grads)
-    fromrgb_param_grads(E, saved, g_out, grads)
-    return grads_in_order(E, grads)
+        if params:
+            red_param_grads(grads, pre, 1, red1)
+        g_u1, dots1 = conv_bwd(cache, grads, pre + "conv_1", blk.conv_1, g_pre1, x, dt, H, rec["a1"], rec["b1"], params, dots=dots)
+        if params:
+            _cbn_param_grads(blk.batch_norm_1, rec["c1"], dots1, cond, grads, pre + "batch_norm_1", pend)
+        if j == 0 and need_img and FUSE_IMG_GRAD and ops.affine_bwd_fromrgb_img_supported(Cc, dt):
+            # x is the FromRGB output and the image carries a gradient: a1 * g_u1 + the skip gradient, the FromRGB data gradient and
+            # (trained encoder) the FromRGB parameter reductions in one launch; the gradient w.r.t. x is neither stored nor rounded
+            g_img, fr = ops.affine_bwd_fromrgb_img(g_u1, x, rec["a1"], E.FromRGB.from_rgb.weight.detach(), saved["img"].float() if params else None,
+                                                   extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
+            g_out = None
+        else:
+            g_out = ops.in_bwd(g_u1, x, _affine_coef(rec["a1"]), extra=extra, extra_pool=extra_pool, extra_scale=extra_scale)
+    if need_img and g_img is None:         # the composed passes: g_out is the stored gradient w.r.t. the FromRGB output
+        g_img = ops.fromrgb_dgrad(g_out, saved["x0"], E.FromRGB.from_rgb.weight.detach())
+    if params:
+        _cbn_param_grads_flush(pend, cond, grads)
+        if fr is None:
+            fromrgb_param_grads(E, saved, g_out, grads)
+        else:
+            grads["FromRGB.from_rgb.weight"] = fr[:3].t().reshape(E.startf, 3, 1, 1)
+            grads["FromRGB.from_rgb.bias"] = fr[3]
+    out = grads_in_order(E, grads)
+    return (out, g_img) if need_img else out
 
 
 class BigEncoderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, E, img, cond_vector, noises, *params):
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            raise ops.DgeError("E_BIG: gradients w.r.t. the input image / condition vector are not implemented on the HIP path; "
-                               "detach them")
-        need = any(ctx.needs_input_grad[4:])
-        _, c_v, z, saved = big_encoder_forward(E, img.detach(), cond_vector, noises, save=need)
-        ctx.E, ctx.saved_acts = E, saved
+        if ctx.needs_input_grad[2]:
+            raise ops.DgeError("E_BIG: the gradient w.r.t. the condition vector is not implemented on the HIP path; detach it")
+        need_params = any(ctx.needs_input_grad[4:])
+        need_img = bool(ctx.needs_input_grad[1])
+        _, c_v, z, saved = big_encoder_forward(E, img.detach(), cond_vector, noises, save=need_params or need_img)
+        ctx.E, ctx.saved_acts, ctx.need_img, ctx.need_params = E, saved, need_img, need_params
         return c_v, z
 
     @staticmethod
     def backward(ctx, g_cv, g_z):
-        return (None, None, None, None) + tuple(big_encoder_backward(ctx.E, ctx.saved_acts, g_z, g_cv))
+        out = big_encoder_backward(ctx.E, ctx.saved_acts, g_z, g_cv, need_img=ctx.need_img, params=ctx.need_params)
+        grads, g_img = out if ctx.need_img else (out, None)
+        if g_img is not None:
+            g_img = g_img.to(ctx.saved_acts["img"].dtype)
+        return (None, g_img, None, None) + tuple(grads)

@@ -686,7 +686,9 @@ __global__ __launch_bounds__(256) void fromrgb_dgrad_kernel(const T* __restrict_
 // The channel chunks of a pixel sit in consecutive lanes (cpt is a power of two): their three partial sums are combined by an xor
 // butterfly inside the wave and, where a pixel spans several waves (cpt = 128, 256), through LDS in wave order - a fixed order
 // either way, so gimg is the same bits run to run in both modes.
-template <typename T, bool FR>
+// AFF (E_BIG: the conditional batch norm in front of block 0's conv_1 is a per-(b,c) affine, its backward g = a*gy): cs.sc holds
+// a [B,C] and is the only coefficient - no coefficient math, no LDS table, no Bc*x0 + Cc terms.
+template <typename T, bool FR, bool AFF = false>
 __global__ __launch_bounds__(256) void in_bwd_fromrgb_img_kernel(const T* __restrict__ gy, const T* __restrict__ X, const T* __restrict__ extra,
                                                                   const float* __restrict__ w, const float* __restrict__ img,
                                                                   float* __restrict__ fr_out, float* __restrict__ gimg, int H, int W, int C,
@@ -694,7 +696,7 @@ __global__ __launch_bounds__(256) void in_bwd_fromrgb_img_kernel(const T* __rest
     constexpr int EP = Elem<T>::PER16;
     constexpr int NS = FR ? 4 : 1;
     __shared__ float red[FR ? 256 * 4 * EP : 4];
-    __shared__ float lcoef[3 * 512];
+    __shared__ float lcoef[AFF ? 1 : 3 * 512];
     __shared__ float xw[2 * 4 * 3];                     // [pixel of the pair][wave][k]: pixels that span waves
     const int b = blockIdx.y;
     const int cpt = C / EP, ppi = 256 / cpt;
@@ -702,26 +704,29 @@ __global__ __launch_bounds__(256) void in_bwd_fromrgb_img_kernel(const T* __rest
     const int HW = H * W, UW = extra_pool ? W / 2 : W, UHW = extra_pool ? HW / 4 : HW;
     float s[NS][EP], A[EP], Bc[EP], Cc[EP], wr[3][EP];
     // the math of in_bwd_coef_kernel for the C channels of sample b, as in in_bwd_kernel
-    for (int c = threadIdx.x; c < C; c += 256) {
-        const int idx = b * C + c;
-        const float r = cs.sc[idx], sft = cs.sh[idx];
-        float S2 = 0.f, S1 = 0.f;
-        if (cs.dots) { const float2 ss = sum_slot_pairs(cs.dots + (size_t)idx * 2, (size_t)cs.B * C * 2, cs.nslot); S2 = ss.x; S1 = ss.y; }
-        const float m1 = S1 * cs.inv_n, m2 = (r * S2 + sft * S1) * cs.inv_n;
-        const float mu = cs.musig[(size_t)b * 2 * C + c], sg = cs.musig[(size_t)b * 2 * C + C + c];
-        const float gmu = cs.gms ? cs.gms[(size_t)b * 2 * C + c] : 0.f, gsg = cs.gms ? cs.gms[(size_t)b * 2 * C + C + c] : 0.f;
-        const float k = sg > 0.f ? gsg * cs.inv_n / sg : 0.f;
-        lcoef[c * 3 + 0] = r;
-        lcoef[c * 3 + 1] = -r * r * m2 + k;
-        lcoef[c * 3 + 2] = -r * m1 - r * m2 * sft + gmu * cs.inv_n - k * mu;
+    if constexpr (!AFF) {
+        for (int c = threadIdx.x; c < C; c += 256) {
+            const int idx = b * C + c;
+            const float r = cs.sc[idx], sft = cs.sh[idx];
+            float S2 = 0.f, S1 = 0.f;
+            if (cs.dots) { const float2 ss = sum_slot_pairs(cs.dots + (size_t)idx * 2, (size_t)cs.B * C * 2, cs.nslot); S2 = ss.x; S1 = ss.y; }
+            const float m1 = S1 * cs.inv_n, m2 = (r * S2 + sft * S1) * cs.inv_n;
+            const float mu = cs.musig[(size_t)b * 2 * C + c], sg = cs.musig[(size_t)b * 2 * C + C + c];
+            const float gmu = cs.gms ? cs.gms[(size_t)b * 2 * C + c] : 0.f, gsg = cs.gms ? cs.gms[(size_t)b * 2 * C + C + c] : 0.f;
+            const float k = sg > 0.f ? gsg * cs.inv_n / sg : 0.f;
+            lcoef[c * 3 + 0] = r;
+            lcoef[c * 3 + 1] = -r * r * m2 + k;
+            lcoef[c * 3 + 2] = -r * m1 - r * m2 * sft + gmu * cs.inv_n - k * mu;
+        }
+        __syncthreads();
     }
-    __syncthreads();
 #pragma unroll
     for (int e = 0; e < EP; e++) {
 #pragma unroll
         for (int k = 0; k < NS; k++) s[k][e] = 0.f;
         const int c = chunk * EP + e;
-        A[e] = lcoef[c * 3]; Bc[e] = lcoef[c * 3 + 1]; Cc[e] = lcoef[c * 3 + 2];
+        if constexpr (AFF) { A[e] = cs.sc[(size_t)b * C + c]; Bc[e] = Cc[e] = 0.f; }
+        else { A[e] = lcoef[c * 3]; Bc[e] = lcoef[c * 3 + 1]; Cc[e] = lcoef[c * 3 + 2]; }
 #pragma unroll
         for (int k = 0; k < 3; k++) wr[k][e] = w[(size_t)c * 3 + k];
     }
@@ -760,7 +765,9 @@ __global__ __launch_bounds__(256) void in_bwd_fromrgb_img_kernel(const T* __rest
             if (ok[h]) {                                 // (a pixel out of range contributes zeros to the butterfly below)
 #pragma unroll
                 for (int e = 0; e < EP; e++) {
-                    float ge = A[e] * g[e] + Bc[e] * xv[e] + Cc[e];
+                    float ge;
+                    if constexpr (AFF) ge = A[e] * g[e];
+                    else ge = A[e] * g[e] + Bc[e] * xv[e] + Cc[e];
                     if (extra) ge += extra_scale * ex[e];
                     const float gp = ge * (xv[e] > 0.f ? 1.f : 0.2f);
                     a[h][0] += gp * wr[0][e]; a[h][1] += gp * wr[1][e]; a[h][2] += gp * wr[2][e];
@@ -1208,6 +1215,28 @@ extern "C" int dge_in_bwd_fromrgb_img(const void* gy, const void* x0, const floa
 #undef DGE_IBI
     dge_note_kernel("in_bwd_fromrgb_img<%s,%s>", dtype == DGE_BF16 ? "bf16" : "f32", out4 ? "fr" : "data");
     DGE_LAUNCH_CHECK("in_bwd_fromrgb_img");
+    return 0;
+}
+
+// dge_in_bwd (coefficients (a, 0, 0): the backward of a per-(b,c) affine, E_BIG's conditional batch norm) + dge_fromrgb_dgrad
+// (+ dge_fromrgb_bwd when img / out4 are given) in one launch: the gradient w.r.t. the FromRGB output is neither stored nor rounded
+extern "C" int dge_affine_bwd_fromrgb_img(const void* gy, const void* x0, const float* a, const void* extra, const float* w, const float* img,
+                                          float* out4, float* gimg, int B, int H, int W, int C, int extra_pool, float extra_scale, int dtype,
+                                          hipStream_t s) {
+    DGE_CHECK(gy && x0 && a && w && gimg && C <= 512, "affine_bwd_fromrgb_img: needs gy, x0, a, w, gimg, C <= 512");
+    DGE_CHECK((img == nullptr) == (out4 == nullptr), "affine_bwd_fromrgb_img: img and out4 go together");
+    DGE_CHECK(B >= 1 && H >= 1 && W >= 1 && (!extra || !extra_pool || (H % 2 == 0 && W % 2 == 0)), "affine_bwd_fromrgb_img: bad shape %d x %d x %d", B, H, W);
+    const int ep = dtype == DGE_BF16 ? 8 : 4;
+    DGE_CHECK(CHAN_OK(C, ep), "affine_bwd_fromrgb_img: unsupported channel count %d", C);
+    dim3 grid(dge_stream_grid(H * W, 256 / (C / ep), B), B);
+    DGE_CHECK(!out4 || dge_det_fits(B, grid.x, (long long)C * 4), "affine_bwd_fromrgb_img: deterministic workspace too small");
+    InCoefSrc cs{nullptr, nullptr, nullptr, a, nullptr, 1, B, 0.f};
+#define DGE_ABI(T, FR) hipLaunchKernelGGL((in_bwd_fromrgb_img_kernel<T, FR, true>), grid, dim3(256), 0, s, (const T*)gy, (const T*)x0, (const T*)extra, w, img, out4, gimg, H, W, C, extra_pool, extra_scale, cs)
+    if (out4) { if (dtype == DGE_BF16) DGE_ABI(bf16_t, true); else DGE_ABI(float, true); }
+    else { if (dtype == DGE_BF16) DGE_ABI(bf16_t, false); else DGE_ABI(float, false); }
+#undef DGE_ABI
+    dge_note_kernel("affine_bwd_fromrgb_img<%s,%s>", dtype == DGE_BF16 ? "bf16" : "f32", out4 ? "fr" : "data");
+    DGE_LAUNCH_CHECK("affine_bwd_fromrgb_img");
     return 0;
 }
 

@@ -1,0 +1,362 @@
+"""Real-image inversion of the reference's embedding_v2_BigGAN.py:25-230 on the HIP path: BigGAN-deep (BASELINE config 4's
+generator) with the conditional-BN encoder E_BIG, in two modes:
+
+  mode "E" (--optimizeE true):  the encoder is re-loaded per image group and fine-tuned; const1, w1 = E(imgs1, cond) every iteration.
+  mode "W" (--optimizeE false): the encoder is frozen and the latent w1 [B,128] itself is optimised (LREQAdam on the leaf w1).
+
+Once:      embed = G.embeddings(one_hot(label));  z0 = truncated_noise_sample(0.4, B, seed=iterations % 30000)
+           cond_vector = cat(z0, embed)            (a constant: E's condition in every call)
+Per group: [W] const1, w1 = E(imgs1, cond_vector) detached -> leaf w1, fresh LREQAdam on it
+           [E] the encoder checkpoint is re-loaded, the Adam state cleared
+Per iteration:
+    [E] const1, w1 = E(imgs1, cond_vector)
+    imgs2, _ = G(w1, conditions, truncation);   const2, w2 = E(imgs2, cond_vector)
+    loss_msiv = space_loss(imgs1, imgs2) [+ space_loss(mask_1, mask_2) + space_loss(cam_1, cam_2)]
+    zero_grad; loss_msiv.backward(retain_graph=True); step
+    loss_msLv = 0.01 * space_loss(w1, w2);  zero_grad; backward; step
+    tracker: armed at iteration == iterations // 2, then a save whenever min > loss_msiv * 1.05
+
+Decisions:
+  * Phase 2.  w2 = E(imgs2) is evaluated before the phase-1 step, as the script does.  Phase 2 back-propagates through this
+    iteration's graphs (E(imgs2) -> imgs2 -> G -> w1 [-> E(imgs1)]) with the live weights the phase-1 step left (the
+    reference's `p.data` Adam update), and its direct term sees the updated w1, as in embedding_v2.LatentEmbedStep.  The image
+    gradient of E(imgs2) is the E_BIG backward's need_img form (autograd_encbig, ops.affine_bwd_fromrgb_img).  loss_c2 =
+    space_loss(const1, const2) is logged only.
+  * Train mode.  G and E stay in train mode in both modes, as in the script (no .eval() anywhere): every forward runs one
+    spectral-norm power iteration, E's conditional batch norms included.
+  * Frozen W mode.  The E parameters are frozen (requires_grad_(False)); the encoder backward then runs with params=False: the data
+    gradient alone.
+  * Attention terms.  The script builds them from .detach().clone(): they are values.  They are computed under no_grad with
+    grad_cam.GradCamPlusPlus and mask2cam, as mis_align.MisAlignStep does; GuidedBackPropagation is constructed on the shared
+    network as in the script (:56-57: from then on every backward of that network is the guided one, the masks' too) but never
+    called: the guided-backprop gradients and the heat maps the script also computes are unused and are not produced.
+    attention=True is the default (it needs the vgg16 network); --attention false leaves the two terms out.
+  * Tracker.  The device-side dge_embed_track with embedding_v2.tracker_rules("sg1", iterations): armed at iterations // 2,
+    hysteresis 1.05, no norm tracker, minima restart per group; files through embedding_v2.write_tracker_files (the script's names).
+  * Not offered, each a ValueError / SystemExit with a clear message: capture() / hipGraph replay (the power iterations are
+    host-sequenced; --mtype 4 is excluded from capture elsewhere too), independent=True, more than one process, and --beta /
+    --norm_p (the norm term is commented out in the script, :163).
+  * --optimizeE parses true / false strictly (the reference's `type=bool` cannot be switched off).
+  * Without --config_dir the generator is BigGAN-deep-256 (BIGGAN_DEEP256, the released configuration).
+"""
+import argparse
+import collections
+import os
+
+import torch
+
+from . import losses, ops, weight_cache
+from .custom_adam import LREQAdam
+from .embedding_v2 import _load_imgs, strict_bool, tracker_rules, write_tracker_files
+from .generators import truncated_noise_sample
+from .models import add_model_args, load_lpips_weights
+
+DEFAULTS = dict(iterations=1501, lr=0.0003, beta_1=0.0, batch_size=1, img_size=256, z_dim=128, start_features=64, label=30,
+                truncation=0.4)
+BIGGAN_DEEP256 = dict(output_dim=256, z_dim=128, class_embed_dim=128, channel_width=128, num_classes=1000,
+                      layers=[[False, 16, 16], [True, 16, 16], [False, 16, 16], [True, 16, 8], [False, 8, 8], [True, 8, 8],
+                              [False, 8, 8], [True, 8, 4], [False, 4, 4], [True, 4, 2], [False, 2, 2], [True, 2, 1]],
+                      attention_layer_position=8, eps=1e-4, n_stats=51)
+
+MSG_CAPTURE = ("BigEmbedStep: hipGraph capture / replay is not offered - every forward of G and E runs host-sequenced spectral-norm "
+               "power iterations (train mode); run step()")
+MSG_INDEPENDENT = "BigEmbedStep: independent=True is not offered (the script couples the rows of a batch; run batch_size 1 per image)"
+MSG_DIST = "BigEmbedStep: more than one process is not offered (the inversion loop is a single-process loop)"
+MSG_NORM = "embedding_v2_biggan: --beta / --norm_p are not offered (the norm term is commented out in embedding_v2_BigGAN.py:163)"
+
+
+class BigEmbedStep:
+    def __init__(self, G, E, lpips_model, mode="E", vgg16=None, attention=True, label=30, lr=0.0003, beta_1=0.0, truncation=0.4,
+                 iterations=1501, arm_iter=None, events_cap=256, independent=False):
+        """`vgg16`: dge_amd.grad_cam.VGG16 (torchvision vgg16 layout) for the attention terms; needed unless attention=False."""
+        if mode not in ("E", "W"):
+            raise ValueError(f"mode must be 'E' or 'W', got {mode!r}")
+        if independent:
+            raise ValueError(MSG_INDEPENDENT)
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise ValueError(MSG_DIST)
+        if attention and vgg16 is None:
+            raise ValueError("BigEmbedStep: attention=True needs the vgg16 network (dge_amd.grad_cam.VGG16); pass attention=False to "
+                             "leave the attention terms out")
+        self.G, self.E, self.lpips = G, E, lpips_model
+        self.mode, self.attention = mode, bool(attention)
+        self.label, self.lr, self.beta_1 = int(label), lr, beta_1
+        self.truncation = torch.tensor(float(truncation), dtype=torch.float)      # float32 tensor, on the host (generators.BigGANAdapter)
+        self.z_truncation = float(truncation)
+        self.iterations = int(iterations)
+        self.rules = tracker_rules("sg1", self.iterations)
+        if arm_iter is not None:
+            self.rules["arm_iter"] = int(arm_iter)
+        self.events_cap = int(events_cap)
+        self.group = -1
+        self.last = {}
+        self.w1 = self._const1 = self._track = None
+        self.conditions = self.cond_vector = None
+        for p in G.parameters():
+            p.requires_grad_(False)
+        G.train(); E.train()                    # the script never leaves train mode
+        if self.attention:
+            from .grad_cam import GradCamPlusPlus, GuidedBackPropagation
+            self.grad_cam_plus_plus = GradCamPlusPlus(vgg16, vgg16.final_layer)
+            self.gbp = GuidedBackPropagation(vgg16)          # shared network: the masks' backward is the guided one, as in the script
+        if mode == "E":
+            self.opt = LREQAdam([{"params": E.parameters()}], lr=lr, betas=(beta_1, 0.99), weight_decay=0)
+            self._ckpt = {k: v.detach().clone() for k, v in E.state_dict().items()}
+        else:
+            for p in E.parameters():          # frozen: the encoder backward computes the data gradient only
+                p.requires_grad_(False)
+            self.opt = None
+
+    captured = False
+
+    def capture(self, *a, **kw):
+        raise ValueError(MSG_CAPTURE)
+
+    replay = capture
+
+    # ------------------------------------------------------------------ once per batch size
+    def _setup(self, B, dev):
+        """embedding_v2_BigGAN.py:37-47: the class condition, its embedding and the constant condition vector of the encoder."""
+        if self.cond_vector is not None and self.cond_vector.shape[0] == B and self.cond_vector.device == dev:
+            return
+        cfg = self.G.config
+        self.conditions = torch.zeros(B, cfg.num_classes, device=dev)
+        self.conditions[:, self.label] = 1.0
+        with torch.no_grad():
+            embed = ops.linear(self.conditions, self.G.embeddings.weight.detach())
+        z0 = truncated_noise_sample(truncation=self.z_truncation, batch_size=B, dim_z=cfg.z_dim, seed=self.iterations % 30000)
+        self.cond_vector = torch.cat((torch.tensor(z0, dtype=torch.float).to(dev), embed), dim=1).contiguous()
+
+    # ------------------------------------------------------------------ per image group
+    def begin_image(self, imgs1, w_init=None, noises=None):
+        """Start an image group.  Mode E re-loads the encoder checkpoint and clears the Adam state; mode W starts the leaf w1 from
+        E(imgs1, cond_vector) (or `w_init`) with a fresh Adam state, const1 of that call stays as the logged constant.  The tracker
+        restarts.  `noises`: optional noise list of the W-mode E(imgs1) (parity runs)."""
+        dev = imgs1.device
+        B = imgs1.shape[0]
+        self._setup(B, dev)
+        self.group += 1
+        shape = (B, self.G.config.z_dim)
+        if self.mode == "E":
+            self.E.load_state_dict(self._ckpt)
+            weight_cache.written(self.E.parameters())
+            self.opt.state = collections.defaultdict(dict)
+        else:
+            with torch.no_grad():
+                c0, w0 = self.E(imgs1, self.cond_vector, noises=noises)
+                self._const1 = c0.detach().clone()
+                if w_init is not None:
+                    w0 = w_init.to(dev, torch.float32).reshape(shape)
+            self.w1 = w0.detach().clone().requires_grad_(True)
+            self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
+        t = self._track
+        if t is None or t["best_loss"].shape != shape or t["fstate"].device != dev:
+            self._track = t = dict(istate=torch.zeros(4, dtype=torch.int32, device=dev),
+                                   fstate=torch.zeros(2, dtype=torch.float32, device=dev),
+                                   best_loss=torch.zeros(shape, dtype=torch.float32, device=dev),
+                                   best_norm=torch.zeros(shape, dtype=torch.float32, device=dev),
+                                   events=torch.zeros((self.events_cap, 4), dtype=torch.float32, device=dev),
+                                   l2=torch.zeros((), dtype=torch.float32, device=dev))
+        t["istate"].zero_()
+        t["events"].zero_()
+        t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32))          # minima restart per group (:88)
+
+    # ------------------------------------------------------------------ one iteration
+    def _attention_terms(self, imgs1, imgs2):
+        """space_loss(mask_1, mask_2) and space_loss(cam_1, cam_2) as values (:96-107,129-140)."""
+        from .grad_cam import mask2cam
+        with torch.no_grad():
+            mask_1 = self.grad_cam_plus_plus(imgs1.detach(), None)
+            mask_2 = self.grad_cam_plus_plus(imgs2.detach(), None)
+            _, cam_1 = mask2cam(mask_1, imgs1)
+            _, cam_2 = mask2cam(mask_2, imgs2)
+            l_mask, info_mask = losses.space_loss(mask_1, mask_2, lpips_model=self.lpips)
+            l_cam, info_cam = losses.space_loss(cam_1, cam_2, lpips_model=self.lpips)
+        return dict(mask_1=mask_1, mask_2=mask_2, cam_1=cam_1, cam_2=cam_2, loss_mask=l_mask, loss_Gcam=l_cam, info_mask=info_mask,
+                    info_Gcam=info_cam)
+
+    def step(self, imgs1, noises=(None, None)):
+        """One iteration; `noises` = optional (E(imgs1), E(imgs2)) noise lists for parity runs (mode W: E(imgs1)'s is unused)."""
+        E, t = self.E, self._track
+        if t is None:
+            raise RuntimeError("BigEmbedStep.step: call begin_image() first")
+        ops.zero_arena_begin(imgs1.device)
+        if self.mode == "E":
+            const1, w1 = E(imgs1, self.cond_vector, noises=noises[0])
+        else:
+            w1, const1 = self.w1, self._const1
+        imgs2, _ = self.G(w1, self.conditions, self.truncation)
+        const2, w2 = E(imgs2, self.cond_vector, noises=noises[1])
+        loss_imgs, info_imgs = losses.space_loss(imgs1, imgs2, lpips_model=self.lpips)
+        loss_msiv, att = loss_imgs, {}
+        if self.attention:
+            att = self._attention_terms(imgs1, imgs2)
+            loss_msiv = loss_imgs + att["loss_mask"] + att["loss_Gcam"]
+        self.opt.zero_grad()
+        loss_msiv.backward(retain_graph=True)
+        self.opt.step()
+        loss_w, info_w = losses.space_loss(w1, w2, image_space=False)
+        with torch.no_grad():
+            loss_c2, info_c2 = losses.space_loss(const1, const2, image_space=False)          # logged only
+        loss_mslv = loss_w * 0.01
+        self.opt.zero_grad()
+        loss_mslv.backward()
+        self.opt.step()
+        w1d = w1.detach()
+        r = self.rules
+        ops.latent_l2(w1d, out=t["l2"])
+        ops.embed_track(loss_msiv.detach(), t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
+                        r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
+        ops.zero_arena_end()
+        self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const1=const1.detach(), const2=const2.detach(),
+                         loss_msiv=loss_msiv.detach(), loss_imgs=loss_imgs.detach(), info_imgs=info_imgs, loss_w=loss_w.detach(),
+                         info_w=info_w, loss_c2=loss_c2.detach(), info_c2=info_c2, loss_mslv=loss_mslv.detach(), w_norm=t["l2"], **att)
+        return self.last
+
+    # ------------------------------------------------------------------ tracker read-out (one host read)
+    def tracker(self):
+        t = self._track
+        ist = t["istate"].cpu().tolist()
+        cnt, cap = ist[1], self.events_cap
+        ev = t["events"].cpu()
+        idx = [k % cap for k in range(max(0, cnt - cap), cnt)]
+        events = [(int(ev[i, 0]), int(ev[i, 1]), float(ev[i, 2]), float(ev[i, 3])) for i in idx]
+        return dict(iteration=ist[0], events=events, dropped=ist[2], min_loss=float(t["fstate"][0]), min_norm=float(t["fstate"][1]),
+                    best_loss=t["best_loss"].clone(), best_norm=t["best_norm"].clone())
+
+
+def _info_line(info):
+    v = [float(x) for x in info.cpu()]
+    return "[[%s, %s, %s], %s, %s, %s, %s]" % tuple(v[1:8])
+
+
+def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0):
+    """`iterations` iterations on one image group (eager: there is no captured form).  With `out_dir` the script's
+    every-`save_every` dumps (image pair, per-row w1, Loss.txt: one host read per dump) and, at the end, the tracker's files.
+    Returns the last result dict with the tracker read-out under "tracker"."""
+    from .infer import save_image_grid
+    st.begin_image(imgs1)
+    B = imgs1.shape[0]
+    r = st.last
+    for i in range(iterations):
+        r = st.step(imgs1)
+        if out_dir is not None and save_every and i % save_every == 0:
+            norm = float(r["w_norm"])
+            save_image_grid(torch.cat((imgs1[:B], r["imgs2"][:B])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f.jpg" % (group, i, norm)),
+                            nrow=2)
+            with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
+                print("id_" + str(group) + "_____i_" + str(i), file=f)
+                print("[loss_imgs_mse[img,img_mean,img_std], loss_imgs_kl, loss_imgs_cosine, loss_imgs_ssim, loss_imgs_lpips]", file=f)
+                print("---------ImageSpace--------", file=f)
+                if st.attention:
+                    print("loss_small_info: %s" % _info_line(r["info_mask"]), file=f)
+                    print("loss_medium_info: %s" % _info_line(r["info_Gcam"]), file=f)
+                print("loss_imgs_info: %s" % _info_line(r["info_imgs"]), file=f)
+                print("---------LatentSpace--------", file=f)
+                print("loss_w_info: %s" % _info_line(r["info_w"]), file=f)
+                print("loss_c2_info: %s" % _info_line(r["info_c2"]), file=f)
+                print("Img_loss: %s" % float(r["loss_msiv"]), file=f)
+            for k, row in enumerate(r["w1"]):
+                torch.save(row.unsqueeze(0).clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f.pt" % (group, k, i, norm)))
+    tr = st.tracker()
+    if out_dir is not None:
+        write_tracker_files(tr, group, os.path.join(out_dir, "models"), out_dir)
+    r = dict(r)
+    r["tracker"] = tr
+    return r
+
+
+def build_models_big_v2(config=None, img_size=256, start_features=64, compute_dtype="bf16", device="cuda", seed=0, attention=True):
+    """BigGAN-deep (`config`: a BigGANConfig, default BigGAN-deep-256) + E_BIG + LPIPS through models.build_models_big, and the vgg16
+    network of the attention terms (None without them).  Seeded random-init weights."""
+    from .biggan_generator import BigGANConfig
+    from .models import build_models_big
+    G, E, LP = build_models_big(config or BigGANConfig.from_dict(BIGGAN_DEEP256), img_size, start_features, compute_dtype, device=device,
+                                seed=seed)
+    vgg = None
+    if attention:
+        from .grad_cam import VGG16
+        vgg = VGG16(compute_dtype=compute_dtype).to(device)
+    return G, E, LP, vgg
+
+
+# ------------------------------------------------------------------ CLI
+def _refuse_norm(_):
+    raise argparse.ArgumentTypeError(MSG_NORM)
+
+
+def make_parser():
+    p = argparse.ArgumentParser(description="BigGAN-deep real-image inversion (embedding_v2_BigGAN.py)")
+    p.add_argument("--iterations", type=int, default=DEFAULTS["iterations"])
+    p.add_argument("--lr", type=float, default=DEFAULTS["lr"])
+    p.add_argument("--beta_1", type=float, default=DEFAULTS["beta_1"])
+    p.add_argument("--batch_size", type=int, default=DEFAULTS["batch_size"])
+    p.add_argument("--experiment_dir", default=None)
+    add_model_args(p)
+    p.set_defaults(mtype=4, img_size=DEFAULTS["img_size"], z_dim=DEFAULTS["z_dim"], start_features=DEFAULTS["start_features"])
+    p.add_argument("--img_dir", default="./bigGAN_inversion/id30/", help="a directory of images or a .pt tensor in [0,1]")
+    p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise the latent directly")
+    p.add_argument("--attention", type=strict_bool, default=True, help="false: leave the Grad-CAM++ mask / cam terms out of loss_msiv")
+    p.add_argument("--label", type=int, default=DEFAULTS["label"], help="ImageNet class id of the condition (30: frog)")
+    p.add_argument("--truncation", type=float, default=DEFAULTS["truncation"])
+    p.add_argument("--beta", type=_refuse_norm, default=None, help="not offered: the norm term is commented out in the script")
+    p.add_argument("--norm_p", type=_refuse_norm, default=None, help="not offered: the norm term is commented out in the script")
+    p.add_argument("--vgg16_weights", default=None, help="torchvision vgg16 checkpoint for the attention terms (seeded stand-in without)")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--save_every", type=int, default=100)
+    p.add_argument("--vgg_weights", default=None)
+    p.add_argument("--lpips_weights", default=None)
+    p.add_argument("--allow_standin_lpips", action="store_true")
+    p.add_argument("--deterministic", action="store_true")
+    return p
+
+
+def parse_args(argv=None):
+    args = make_parser().parse_args(argv)
+    if args.mtype != 4:
+        raise SystemExit("embedding_v2_biggan: --mtype is 4 (BigGAN-deep + E_BIG); the StyleGAN loops are dge_amd.embedding_v2")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.deterministic:
+        ops.set_deterministic(True)
+    from .biggan_generator import BigGANConfig
+    from .infer import save_image_grid
+    dev = "cuda"
+    config = BigGANConfig.from_json_file(args.config_dir) if args.config_dir else None
+    G, E, LP, vgg = build_models_big_v2(config, args.img_size, args.start_features, args.compute_dtype, device=dev, seed=args.seed,
+                                        attention=args.attention)
+    # the mtype-4 containers of models.load_models: the generator a bare state_dict, the encoder a bare state_dict
+    if args.checkpoint_dir_GAN:
+        G.load_state_dict(torch.load(args.checkpoint_dir_GAN, map_location="cpu"))
+    if args.checkpoint_dir_E:
+        E.load_state_dict(torch.load(args.checkpoint_dir_E, map_location="cpu"))
+    if vgg is not None and args.vgg16_weights:
+        vgg.load_pretrained(args.vgg16_weights)
+    load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
+    out = args.experiment_dir or "./result_bigGAN_id30_GradCAM/mis_aligh_bigGAN_v1_opE"
+    for sub in ("", "imgs", "models", "summaries"):
+        os.makedirs(os.path.join(out, sub), exist_ok=True)
+    imgs = _load_imgs(args.img_dir, args.img_size, dev)
+    st = BigEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", vgg16=vgg, attention=args.attention, label=args.label, lr=args.lr,
+                      beta_1=args.beta_1, truncation=args.truncation, iterations=args.iterations)
+    bs = args.batch_size
+    ngroups = imgs.shape[0] // bs
+    w_all, img_all = [], []
+    for g in range(ngroups):
+        imgs1 = imgs[g * bs:(g + 1) * bs].contiguous()
+        r = invert_big(st, imgs1, args.iterations, save_every=args.save_every, out_dir=out, group=g)
+        print("group %d: loss_msiv %.5f  w_norm %.4f  events %d" % (g, float(r["loss_msiv"]), float(r["w_norm"]), len(r["tracker"]["events"])))
+        save_image_grid(r["imgs2"], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
+        w_all.append(r["w1"][0].clone().cpu())
+        img_all.append(r["imgs2"][0].clone().cpu())
+    if w_all:
+        torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (ngroups - 1)))
+        torch.save(torch.stack(img_all, dim=0), os.path.join(out, "models", "img_all_%d.pt" % (ngroups - 1)))
+    return st
+
+
+if __name__ == "__main__":
+    main()

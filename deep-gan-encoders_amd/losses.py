@@ -362,6 +362,13 @@ def space_loss(imgs1, imgs2, image_space=True, lpips_model=None, global_batch=No
             out8 = _space_loss_window(a.view(Bt, n_in, 1, 1), b.view(Bt, n_in, 1, 1), (0, 0, 1, 1), False, None,
                                       g.view(Bt, n_in, 1, 1) if need else None, gb=global_batch)
             loss = out8[0]
+            if imgs1.requires_grad and torch.is_grad_enabled():
+                # the first argument carries a gradient too (embedding_v2_biggan: w1 is the optimised leaf or the encoder's output):
+                # the exchanged call, as for 3-D latents below
+                ga = torch.empty_like(a)
+                _space_loss_window(b.view(Bt, n_in, 1, 1), a.view(Bt, n_in, 1, 1), (0, 0, 1, 1), False, None, ga.view(Bt, n_in, 1, 1),
+                                   gb=global_batch)
+                return _ScaledGrad2.apply(imgs1, imgs2, loss, ga, g if need else torch.zeros_like(b)), out8
             return (_ScaledGrad.apply(imgs2, loss, g) if need else loss), out8
         out8 = _space_loss_window(a.view(1, Bt, 1, n_in), b.view(1, Bt, 1, n_in), (0, 0, 1, n_in), False, None,
                                   g.view(1, Bt, 1, n_in) if need else None, gb=global_batch)

@@ -1027,6 +1027,30 @@ def in_bwd_fromrgb_img(gy, x0, coef, w, img=None, extra=None, extra_pool=False, 
     return gimg, _sum_planar(part, torch.empty((4, Cc), dtype=torch.float32, device=x0.device), defer)
 
 
+def affine_bwd_fromrgb_img_supported(Cc, dtype):
+    """Whether dge_affine_bwd_fromrgb_img takes the channel count: the rule of in_bwd_fromrgb_img_supported (the same kernel)."""
+    return in_bwd_fromrgb_img_supported(Cc, dtype)
+
+
+def affine_bwd_fromrgb_img(gy, x0, a, w, img=None, extra=None, extra_pool=False, extra_scale=1.0, defer=None):
+    """Last step of the E_BIG backward when the image carries a gradient: g = a * gy (+ extra_scale * extra) on the FromRGB output
+    x0 (a [B,C]: the conditional batch norm's scale), the FromRGB data gradient of the result -> g_img [B,3,H,W] f32 and, with `img`,
+    the FromRGB parameter gradients [4, C] (planar; None without).  The gradient w.r.t. x0 is never stored.  w: FromRGB's weight."""
+    B, H, W, Cc = x0.shape
+    if tuple(a.shape) != (B, Cc):
+        raise DgeError(f"affine_bwd_fromrgb_img: a {tuple(a.shape)} is not [B={B}, C={Cc}]")
+    gimg = torch.empty((B, 3, H, W), dtype=torch.float32, device=x0.device)
+    part = zeros((B, Cc, 4), x0.device) if img is not None else None
+    check(lib().dge_affine_bwd_fromrgb_img(_p(gy), _p(x0), _f32(a.float().contiguous()), _p(extra), _f32(w.reshape(Cc, 3).contiguous()),
+                                           _f32(img.contiguous()) if img is not None else None, _p(part), _p(gimg), B, H, W, Cc,
+                                           1 if extra_pool else 0, float(extra_scale), dtype_of(x0), _stream()),
+          "dge_affine_bwd_fromrgb_img")
+    log_kernel()
+    if part is None:
+        return gimg, None
+    return gimg, _sum_planar(part, torch.empty((4, Cc), dtype=torch.float32, device=x0.device), defer)
+
+
 def conv_pool_supported(B, H, W, cin, cout, ksize, dtype):
     return bool(lib().dge_conv_pool_supported(B, H, W, cin, cout, ksize, dtype))
 

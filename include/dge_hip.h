@@ -422,6 +422,11 @@ int dge_in_bwd_fromrgb(const void* gy, const void* x0, const float* dots, int ns
 int dge_in_bwd_fromrgb_img(const void* gy, const void* x0, const float* dots, int nslot, const float* gms, const float* musig,
                            const float* sc, const float* sh, int npix, const void* extra, const float* w, const float* img, float* out4,
                            float* gimg, int B, int H, int W, int C, int extra_pool, float extra_scale, int dtype, dge_stream_t stream);
+/* The same launch in coefficient form for E_BIG, whose conditional batch norm is a per-(b,c) affine: g = a[b,c]*gy + extra_scale*extra[q(p)]
+   (a [B,C] f32; extra optional, full-resolution or 2x2-pooled), gp = g*lrelu'(x0), gimg[b,k,p] = sum_c w[c][k]*gp; with img / out4 (a pair
+   or both NULL) out4[b,c,0..2] += sum_p gp*img[k], out4[b,c,3] += sum_p gp.  C <= 512, 16-byte channel chunks that tile a workgroup. */
+int dge_affine_bwd_fromrgb_img(const void* gy, const void* x0, const float* a, const void* extra, const float* w, const float* img, float* out4,
+                               float* gimg, int B, int H, int W, int C, int extra_pool, float extra_scale, int dtype, dge_stream_t stream);
 /* Forward of every inver_mod head of the encoder in one launch (E.py:51-53,64-66): w[b, gcol_l + o] = musig_l[b,:] . W_l[o,:] + bias_l[o]
  * over the same entry table as dge_heads_bwd (entries carry the bias pointer); w [B, ldw]. */
 int dge_heads_fwd(const void* dev_entries, int n, const float* musig_all, float* w, int ldw, int B, int O, dge_stream_t stream);
