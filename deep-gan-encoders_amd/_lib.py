@@ -157,10 +157,13 @@ SIGNATURES = {
     "dge_adaptive_pool7_bwd": [_P, _P, _I, _I, _I, _I, _I, _P],
     "dge_class_target": [_P, _P, _P, _P, _I, _I, _P],
     "dge_gather_row": [_P, _P, _P, _I, _I, _F, _P],
+    "dge_class_target_rows": [_P, _P, _P, _P, _I, _I, _P],
+    "dge_gather_rows": [_P, _P, _P, _I, _I, _P],
     "dge_campp_map": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "dge_cam_resize": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "dge_mask2cam_blocks": [_I],
     "dge_mask2cam": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "dge_mask2cam_rows": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
     "dge_randn": [_P, _I, _P, _P, _P, _P, C.c_ulonglong, _P, _P],
     "dge_version": [],
     "dge_env_reload": [],

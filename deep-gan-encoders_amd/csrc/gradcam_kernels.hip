@@ -100,6 +100,43 @@ __global__ void gather_row_kernel(const float* __restrict__ w, const int* __rest
     for (long i = blockIdx.x * 256L + threadIdx.x; i < (long)B * I; i += (long)gridDim.x * 256) y[i] = scale * row[i % I];
 }
 
+// The per-row forms (GradCamPlusPlus.call_per_image, grad_cam.py:122-155: row b's target is logits[b, index_b] itself).
+// index_out[b] = index_in[b] (clamped to [0, K)) or the first maximum of row b (np.argmax); glogits[b, k] = (k == index_out[b]).
+// One wave per row: every lane scans k = lane, lane + 64, ... (ascending, strict >: its first maximum), then a butterfly that keeps
+// the smaller index among equal maxima - every lane ends with the row's result.  Plain stores, the same bits in every mode.
+__global__ void class_target_rows_kernel(const float* __restrict__ logits, const int* __restrict__ index_in, int* __restrict__ index_out,
+                                         float* __restrict__ glogits, int B, int K) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                               // whole waves leave: the shuffles below stay inside one row
+    const float* row = logits + (size_t)b * K;
+    int am;
+    if (index_in) {
+        am = index_in[b];
+        am = am < 0 ? 0 : (am >= K ? K - 1 : am);
+    } else {
+        float mv = -INFINITY;
+        am = lane < K ? lane : 0x7fffffff;
+        for (int k = lane; k < K; k += 64) { const float v = row[k]; if (v > mv) { mv = v; am = k; } }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(mv, o, 64);
+            const int oa = __shfl_xor(am, o, 64);
+            if (ov > mv || (ov == mv && oa < am)) { mv = ov; am = oa; }
+        }
+    }
+    if (lane == 0) index_out[b] = am;
+    for (int k = lane; k < K; k += 64) glogits[(size_t)b * K + k] = (k == am) ? 1.f : 0.f;
+}
+
+// y[b, :] = w[index[b], :]  (d logits[b, index_b] / d hidden2[b]: the first backward step of the classifier, per row, scale 1)
+__global__ void gather_rows_kernel(const float* __restrict__ w, const int* __restrict__ index, float* __restrict__ y, int B, int I) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < (long)B * I; i += (long)gridDim.x * 256) {
+        const int b = (int)(i / I);
+        y[i] = w[(size_t)index[b] * I + (i - (long)b * I)];
+    }
+}
+
 // Channel weights.  Grad-CAM++ (mode 1, grad_cam.py:180-186): s = sum_hw relu(g); weight = s > 0 ? s * (1/s) : 0.
 // Grad-CAM (mode 0, :101-102): weight = mean_hw g.  grid (C/64, B); 16 waves split the pixels, lane = channel (the grid is
 // small - 64 workgroups for 8 x 512 channels - so each workgroup brings many waves to hide the load latency).
@@ -251,6 +288,25 @@ __global__ void cam_norm_apply_kernel(float* __restrict__ cam, const float* __re
     }
 }
 
+// mask2cam with every row normalised on its own (what the recurrence above gives for a batch of one): m = min(cam_b),
+// scl = max(cam_b) - m from row b's per-block extrema - a fixed-order tree over its nblk <= 256 partials -, applied in the same
+// launch: cam = (cam - m) / scl.  grid (x, B).
+__global__ void cam_norm_rows_kernel(float* __restrict__ cam, const float* __restrict__ part, int nblk, long per_sample) {
+    __shared__ float lo[256], hi[256];
+    const int b = blockIdx.y, t = threadIdx.x;
+    const float* o = part + ((size_t)b * nblk + t) * 3;
+    lo[t] = t < nblk ? o[1] : INFINITY;
+    hi[t] = t < nblk ? o[2] : -INFINITY;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) { lo[t] = fminf(lo[t], lo[t + s]); hi[t] = fmaxf(hi[t], hi[t + s]); }
+        __syncthreads();
+    }
+    const float m = lo[0], scl = hi[0] - m;
+    float* row = cam + (size_t)b * per_sample;
+    for (long i = blockIdx.x * 256L + t; i < per_sample; i += (long)gridDim.x * 256) row[i] = (row[i] - m) / scl;
+}
+
 static inline unsigned blocks_for(long n, long cap = 65535L * 16) {
     long g = (n + 255) / 256;
     return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
@@ -303,6 +359,21 @@ extern "C" int dge_gather_row(const float* w, const int* index, float* y, int B,
     return 0;
 }
 
+extern "C" int dge_class_target_rows(const float* logits, const int* index_in, int* index_out, float* glogits, int B, int K,
+                                     hipStream_t s) {
+    DGE_CHECK(B >= 1 && K >= 1 && (B + 3) / 4 <= 65535, "class_target_rows: B=%d K=%d", B, K);
+    hipLaunchKernelGGL(class_target_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, index_in, index_out, glogits, B, K);
+    DGE_LAUNCH_CHECK("class_target_rows");
+    return 0;
+}
+
+extern "C" int dge_gather_rows(const float* w, const int* index, float* y, int B, int I, hipStream_t s) {
+    DGE_CHECK(B >= 1 && I >= 1, "gather_rows: B=%d I=%d", B, I);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks_for((long)B * I, 1024)), dim3(256), 0, s, w, index, y, B, I);
+    DGE_LAUNCH_CHECK("gather_rows");
+    return 0;
+}
+
 extern "C" int dge_campp_map(const void* grad, const void* feat, float* wgt, float* cam, float* minmax, int B, int HW, int C,
                              int mode, int dtype, hipStream_t s) {
     const int ep = dtype == DGE_BF16 ? 8 : 4;
@@ -338,5 +409,16 @@ extern "C" int dge_mask2cam(const float* mask, const float* img, const int* lut,
     const long n = (long)B * 3 * HW;
     hipLaunchKernelGGL(cam_norm_apply_kernel, dim3(blocks_for(n, 4096)), dim3(256), 0, s, cam, coef, (long)3 * HW, n);
     DGE_LAUNCH_CHECK("mask2cam");
+    return 0;
+}
+
+extern "C" int dge_mask2cam_rows(const float* mask, const float* img, const int* lut, float* heat, float* cam, float* part, int B,
+                                 int HW, hipStream_t s) {
+    DGE_CHECK(B >= 1 && B <= 65535 && HW >= 1, "mask2cam_rows: B=%d (1..65535) HW=%d", B, HW);
+    const int nblk = dge_mask2cam_blocks(HW);
+    hipLaunchKernelGGL(jet_overlay_kernel, dim3(nblk, B), dim3(256), 0, s, mask, img, lut, heat, cam, part, HW);
+    const long per = (long)3 * HW;
+    hipLaunchKernelGGL(cam_norm_rows_kernel, dim3(blocks_for(per, 256), B), dim3(256), 0, s, cam, part, nblk, per);
+    DGE_LAUNCH_CHECK("mask2cam_rows");
     return 0;
 }

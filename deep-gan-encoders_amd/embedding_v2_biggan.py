@@ -34,20 +34,32 @@ Decisions:
   * Tracker.  The device-side dge_embed_track with embedding_v2.tracker_rules("sg1", iterations): armed at iterations // 2,
     hysteresis 1.05, no norm tracker, minima restart per group; files through embedding_v2.write_tracker_files (the script's names).
   * Not offered, each a ValueError / SystemExit with a clear message: capture() / hipGraph replay (the power iterations are
-    host-sequenced; --mtype 4 is excluded from capture elsewhere too), independent=True, more than one process, and --beta /
-    --norm_p (the norm term is commented out in the script, :163).
+    host-sequenced; --mtype 4 is excluded from capture elsewhere too), independent=True on BigEmbedStep (the rows form is a class of
+    its own, below), more than one process, and --beta / --norm_p (the norm term is commented out in the script, :163).
+  * Independent rows (BigEmbedRowsStep, --independent true; mode W only).  The B rows of a group are B inversions of their own,
+    each with its own class label (--labels): per-row losses (losses.space_loss_image_rows / space_loss_rows), per-row Grad-CAM++
+    targets and mask2cam normalisation (GradCAM.call_per_image, mask2cam(rows=True)), one tracker per row.  Phase 1 back-propagates
+    sum_b loss_msiv_b, phase 2 0.01 * sum_b space_loss_b(w1, w2); LREQAdam is element-wise, the batch norms use stored statistics.
+      - z0 of the condition vector is the batch-1 draw, repeated for every row: a batch-1 run of any image draws exactly that.
+      - Each forward of G and E runs ONE spectral-norm power iteration for the whole batch.  So row b equals the batch-1 run of
+        image b started from the same weight_u / weight_v buffers - not the b-th run of a sequential loop, whose buffers the earlier
+        images have advanced.
+      - The encoder is shared by a group, so mode E has no rows form (ValueError); capture() / replay() and more than one process
+        stay refused.
+      - A short last group is padded by repeating its last image and label; the padded rows' outputs are dropped.
   * --optimizeE parses true / false strictly (the reference's `type=bool` cannot be switched off).
   * Without --config_dir the generator is BigGAN-deep-256 (BIGGAN_DEEP256, the released configuration).
 """
 import argparse
 import collections
+import numbers
 import os
 
 import torch
 
 from . import losses, ops, weight_cache
 from .custom_adam import LREQAdam
-from .embedding_v2 import _load_imgs, strict_bool, tracker_rules, write_tracker_files
+from .embedding_v2 import _load_imgs, group_plan, padded_rows, strict_bool, tracker_rules, write_tracker_files
 from .generators import truncated_noise_sample
 from .models import add_model_args, load_lpips_weights
 
@@ -60,7 +72,9 @@ BIGGAN_DEEP256 = dict(output_dim=256, z_dim=128, class_embed_dim=128, channel_wi
 
 MSG_CAPTURE = ("BigEmbedStep: hipGraph capture / replay is not offered - every forward of G and E runs host-sequenced spectral-norm "
                "power iterations (train mode); run step()")
-MSG_INDEPENDENT = "BigEmbedStep: independent=True is not offered (the script couples the rows of a batch; run batch_size 1 per image)"
+MSG_INDEPENDENT = ("BigEmbedStep: independent=True is not offered (the script couples the rows of a batch; run batch_size 1 per image) "
+                   "- the rows form is BigEmbedRowsStep")
+MSG_ROWS_MODE = "BigEmbedRowsStep: mode 'W' only - in mode 'E' one encoder is shared by the rows of a group"
 MSG_DIST = "BigEmbedStep: more than one process is not offered (the inversion loop is a single-process loop)"
 MSG_NORM = "embedding_v2_biggan: --beta / --norm_p are not offered (the norm term is commented out in embedding_v2_BigGAN.py:163)"
 
@@ -225,21 +239,198 @@ class BigEmbedStep:
                     best_loss=t["best_loss"].clone(), best_norm=t["best_norm"].clone())
 
 
+class BigEmbedRowsStep(BigEmbedStep):
+    """BigEmbedStep with the B rows of a group as B inversions of their own (mode W), each with its own class label.
+
+    Row b equals the batch-1 BigEmbedStep run of image b with label b STARTED FROM THE SAME weight_u / weight_v BUFFERS: each forward
+    of G and E runs one spectral-norm power iteration for the whole batch.  It does not equal the b-th run of a sequential loop,
+    whose buffers the earlier images have advanced.  The logged values of step() (`loss_msiv`, `loss_imgs`, `loss_w`, `loss_c2`,
+    `loss_mslv`, `w_norm`, the attention losses) are [B] columns, the infos [B,8]; tracker() returns one read-out per row."""
+    independent = True
+
+    def __init__(self, G, E, lpips_model, mode="W", **kw):
+        if mode != "W":
+            raise ValueError(MSG_ROWS_MODE)
+        if kw.pop("independent", True) is not True:
+            raise ValueError("BigEmbedRowsStep is the independent form; the coupled loop is BigEmbedStep")
+        super().__init__(G, E, lpips_model, mode="W", **kw)
+        self.labels = None
+
+    def _row_labels(self, labels, B):
+        if labels is None:
+            labels = self.label
+        if isinstance(labels, numbers.Integral) or (torch.is_tensor(labels) and labels.dim() == 0):
+            labels = [int(labels)] * B
+        labels = [int(v) for v in labels]
+        K = self.G.config.num_classes
+        if len(labels) != B:
+            raise ValueError(f"BigEmbedRowsStep: {len(labels)} labels for {B} images")
+        if any(v < 0 or v >= K for v in labels):
+            raise ValueError(f"BigEmbedRowsStep: class ids must lie in [0, {K}), got {labels}")
+        return tuple(labels)
+
+    def _setup(self, B, dev, labels):
+        """The per-row class conditions and condition vectors; rebuilt when the group's labels change."""
+        if self.cond_vector is not None and self.labels == labels and self.cond_vector.device == dev:
+            return
+        cfg = self.G.config
+        self.labels = labels
+        self.conditions = torch.zeros(B, cfg.num_classes, device=dev)
+        self.conditions[torch.arange(B, device=dev), torch.tensor(labels, device=dev)] = 1.0
+        with torch.no_grad():
+            embed = ops.linear(self.conditions, self.G.embeddings.weight.detach())
+        # the batch-1 draw for every row (rows 1.. of a batch-B draw are other numbers: no batch-1 run would see them)
+        z0 = truncated_noise_sample(truncation=self.z_truncation, batch_size=1, dim_z=cfg.z_dim, seed=self.iterations % 30000)
+        z0 = torch.tensor(z0, dtype=torch.float).to(dev).expand(B, -1)
+        self.cond_vector = torch.cat((z0, embed), dim=1).contiguous()
+
+    def begin_image(self, imgs1, labels=None, w_init=None, noises=None):
+        """Start a group of B images: `labels` (an int or one class id per row; default: the constructor's `label`) set the rows'
+        conditions, w1 starts from E(imgs1, cond_vector) (or `w_init`) with a fresh Adam state, and every row's tracker restarts."""
+        dev = imgs1.device
+        B = imgs1.shape[0]
+        self._setup(B, dev, self._row_labels(labels, B))
+        self.group += 1
+        shape = (B, self.G.config.z_dim)
+        with torch.no_grad():
+            c0, w0 = self.E(imgs1, self.cond_vector, noises=noises)
+            self._const1 = c0.detach().clone()
+            if w_init is not None:
+                w0 = w_init.to(dev, torch.float32).reshape(shape)
+        self.w1 = w0.detach().clone().requires_grad_(True)
+        self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
+        t = self._track
+        if t is None or t["best_loss"].shape != shape or t["fstate"].device != dev:      # a tracker per row: a leading B everywhere
+            self._track = t = dict(istate=torch.zeros((B, 4), dtype=torch.int32, device=dev),
+                                   fstate=torch.zeros((B, 2), dtype=torch.float32, device=dev),
+                                   best_loss=torch.zeros(shape, dtype=torch.float32, device=dev),
+                                   best_norm=torch.zeros(shape, dtype=torch.float32, device=dev),
+                                   events=torch.zeros((B, self.events_cap, 4), dtype=torch.float32, device=dev),
+                                   l2=torch.zeros(B, dtype=torch.float32, device=dev))
+        t["istate"].zero_()
+        t["events"].zero_()
+        t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32).expand_as(t["fstate"]))      # minima restart per group
+
+    def _attention_terms(self, imgs1, imgs2):
+        """Per row: space_loss_b(mask_1, mask_2) and space_loss_b(cam_1, cam_2) as values, every row's mask towards its own arg-max
+        class and every cam normalised on its own."""
+        from .grad_cam import mask2cam
+        with torch.no_grad():
+            mask_1 = self.grad_cam_plus_plus.call_per_image(imgs1.detach(), None)
+            mask_2 = self.grad_cam_plus_plus.call_per_image(imgs2.detach(), None)
+            _, cam_1 = mask2cam(mask_1, imgs1, rows=True)
+            _, cam_2 = mask2cam(mask_2, imgs2, rows=True)
+            _, info_mask = losses.space_loss_image_rows(mask_1, mask_2, lpips_model=self.lpips)
+            _, info_cam = losses.space_loss_image_rows(cam_1, cam_2, lpips_model=self.lpips)
+        return dict(mask_1=mask_1, mask_2=mask_2, cam_1=cam_1, cam_2=cam_2, loss_mask=info_mask[:, 0].contiguous(),
+                    loss_Gcam=info_cam[:, 0].contiguous(), info_mask=info_mask, info_Gcam=info_cam)
+
+    def step(self, imgs1, noises=(None, None)):
+        """One iteration of every row; `noises` as BigEmbedStep.step.  The attention terms are values (the script detaches them): they
+        enter every row's loss_msiv, and phase 1 back-propagates sum_b space_loss_b(imgs1, imgs2)."""
+        E, t = self.E, self._track
+        if t is None:
+            raise RuntimeError("BigEmbedRowsStep.step: call begin_image() first")
+        ops.zero_arena_begin(imgs1.device)
+        w1, const1 = self.w1, self._const1
+        imgs2, _ = self.G(w1, self.conditions, self.truncation)
+        const2, w2 = E(imgs2, self.cond_vector, noises=noises[1])
+        loss_sum, info_imgs = losses.space_loss_image_rows(imgs1, imgs2, lpips_model=self.lpips)
+        loss_imgs = info_imgs[:, 0].contiguous()
+        loss_msiv, att = loss_imgs, {}
+        if self.attention:
+            att = self._attention_terms(imgs1, imgs2)
+            loss_msiv = loss_imgs + att["loss_mask"] + att["loss_Gcam"]
+        self.opt.zero_grad()
+        loss_sum.backward(retain_graph=True)
+        self.opt.step()
+        lat_sum, info_w = losses.space_loss_rows(w1, w2, image_space=False)
+        with torch.no_grad():
+            _, info_c2 = losses.space_loss_rows(const1, const2, image_space=False)          # logged only
+        self.opt.zero_grad()
+        (lat_sum * 0.01).backward()
+        self.opt.step()
+        loss_w = info_w[:, 0].contiguous()
+        w1d = w1.detach()
+        r = self.rules
+        ops.latent_l2_rows(w1d, out=t["l2"])
+        ops.embed_track_rows(loss_msiv, t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
+                             r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
+        ops.zero_arena_end()
+        self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const1=const1.detach(), const2=const2.detach(),
+                         loss_msiv=loss_msiv, loss_imgs=loss_imgs, info_imgs=info_imgs, loss_w=loss_w, info_w=info_w,
+                         loss_c2=info_c2[:, 0].contiguous(), info_c2=info_c2, loss_mslv=loss_w * 0.01, w_norm=t["l2"], **att)
+        return self.last
+
+    def tracker(self):
+        """A list with one read-out per row (one host read)."""
+        t = self._track
+        B, cap = t["istate"].shape[0], self.events_cap
+        host = torch.cat((t["istate"].float(), t["fstate"], t["events"].reshape(B, -1)), dim=1).cpu()      # counters < 2^24: exact in f32
+        out = []
+        for b in range(B):
+            ist = [int(v) for v in host[b, :4]]
+            ev = host[b, 6:].view(cap, 4)
+            idx = [k % cap for k in range(max(0, ist[1] - cap), ist[1])]
+            out.append(dict(iteration=ist[0], events=[(int(ev[i, 0]), int(ev[i, 1]), float(ev[i, 2]), float(ev[i, 3])) for i in idx],
+                            dropped=ist[2], min_loss=float(host[b, 4]), min_norm=float(host[b, 5]),
+                            best_loss=t["best_loss"][b:b + 1].clone(), best_norm=t["best_norm"][b:b + 1].clone()))
+        return out
+
+
 def _info_line(info):
     v = [float(x) for x in info.cpu()]
     return "[[%s, %s, %s], %s, %s, %s, %s]" % tuple(v[1:8])
 
 
-def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0):
+def _dump_rows(st, imgs1, r, i, out_dir, group, keep):
+    """The every-`save_every` dump of the rows form: per image (number group * B + b) the image pair, w1 and a Loss.txt block."""
+    from .infer import save_image_grid
+    B = imgs1.shape[0]
+    vals = torch.stack((r["w_norm"], r["loss_msiv"])).cpu()
+    infos = {k: r[k].cpu() for k in ("info_mask", "info_Gcam", "info_imgs", "info_w", "info_c2") if k in r}
+    for b in range(keep):
+        num, norm, loss = group * B + b, float(vals[0, b]), float(vals[1, b])
+        save_image_grid(torch.cat((imgs1[b:b + 1], r["imgs2"][b:b + 1])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f.jpg" % (num, i, norm)),
+                        nrow=2)
+        with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
+            print("id_" + str(num) + "_____i_" + str(i), file=f)
+            print("[loss_imgs_mse[img,img_mean,img_std], loss_imgs_kl, loss_imgs_cosine, loss_imgs_ssim, loss_imgs_lpips]", file=f)
+            print("---------ImageSpace--------", file=f)
+            if st.attention:
+                print("loss_small_info: %s" % _info_line(infos["info_mask"][b]), file=f)
+                print("loss_medium_info: %s" % _info_line(infos["info_Gcam"][b]), file=f)
+            print("loss_imgs_info: %s" % _info_line(infos["info_imgs"][b]), file=f)
+            print("---------LatentSpace--------", file=f)
+            print("loss_w_info: %s" % _info_line(infos["info_w"][b]), file=f)
+            print("loss_c2_info: %s" % _info_line(infos["info_c2"][b]), file=f)
+            print("Img_loss: %s" % loss, file=f)
+        torch.save(r["w1"][b:b + 1].clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f.pt" % (num, 0, i, norm)))
+
+
+def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0, labels=None, keep=None):
     """`iterations` iterations on one image group (eager: there is no captured form).  With `out_dir` the script's
     every-`save_every` dumps (image pair, per-row w1, Loss.txt: one host read per dump) and, at the end, the tracker's files.
-    Returns the last result dict with the tracker read-out under "tracker"."""
+    Returns the last result dict with the tracker read-out under "tracker".  Rows form (BigEmbedRowsStep; `labels`: one class id per
+    row): files carry the image number group * B + b, Loss.txt gets a block per image, only the first `keep` rows (default: all) are
+    written, and "tracker" is the list of per-row read-outs."""
     from .infer import save_image_grid
-    st.begin_image(imgs1)
+    rows = getattr(st, "independent", False)
     B = imgs1.shape[0]
+    if rows:
+        st.begin_image(imgs1, labels=labels)
+        keep = B if keep is None else keep
+    elif labels is not None or keep is not None:
+        raise ValueError("invert_big: labels / keep belong to the rows form (BigEmbedRowsStep)")
+    else:
+        st.begin_image(imgs1)
     r = st.last
     for i in range(iterations):
         r = st.step(imgs1)
+        if rows:
+            if out_dir is not None and save_every and i % save_every == 0:
+                _dump_rows(st, imgs1, r, i, out_dir, group, keep)
+            continue
         if out_dir is not None and save_every and i % save_every == 0:
             norm = float(r["w_norm"])
             save_image_grid(torch.cat((imgs1[:B], r["imgs2"][:B])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f.jpg" % (group, i, norm)),
@@ -259,7 +450,10 @@ def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0):
             for k, row in enumerate(r["w1"]):
                 torch.save(row.unsqueeze(0).clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f.pt" % (group, k, i, norm)))
     tr = st.tracker()
-    if out_dir is not None:
+    if out_dir is not None and rows:
+        for b in range(keep):
+            write_tracker_files(tr[b], group * B + b, os.path.join(out_dir, "models"), out_dir)
+    elif out_dir is not None:
         write_tracker_files(tr, group, os.path.join(out_dir, "models"), out_dir)
     r = dict(r)
     r["tracker"] = tr
@@ -298,6 +492,10 @@ def make_parser():
     p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise the latent directly")
     p.add_argument("--attention", type=strict_bool, default=True, help="false: leave the Grad-CAM++ mask / cam terms out of loss_msiv")
     p.add_argument("--label", type=int, default=DEFAULTS["label"], help="ImageNet class id of the condition (30: frog)")
+    p.add_argument("--independent", type=strict_bool, default=False,
+                   help="true (with --optimizeE false): every image of a batch is an inversion of its own, equal to its batch-1 run")
+    p.add_argument("--labels", default=None, help="with --independent true: one class id per image in the sorted order of --img_dir, "
+                                                  "as a comma list or a text file with one id per line (default: --label for all)")
     p.add_argument("--truncation", type=float, default=DEFAULTS["truncation"])
     p.add_argument("--beta", type=_refuse_norm, default=None, help="not offered: the norm term is commented out in the script")
     p.add_argument("--norm_p", type=_refuse_norm, default=None, help="not offered: the norm term is commented out in the script")
@@ -315,7 +513,42 @@ def parse_args(argv=None):
     args = make_parser().parse_args(argv)
     if args.mtype != 4:
         raise SystemExit("embedding_v2_biggan: --mtype is 4 (BigGAN-deep + E_BIG); the StyleGAN loops are dge_amd.embedding_v2")
+    if args.independent and args.optimizeE:
+        raise SystemExit("embedding_v2_biggan: --independent true needs --optimizeE false (the fine-tuned encoder is shared by a group)")
+    if args.labels is not None and not args.independent:
+        raise SystemExit("embedding_v2_biggan: --labels needs --independent true (the coupled loop has one --label for the batch)")
     return args
+
+
+def read_labels(spec, n_images, num_classes, default):
+    """The class id of every image: `spec` None -> `default` for all; a comma list, or the path of a text file with one id per line.
+    A wrong count or an id outside [0, num_classes) is a SystemExit."""
+    if spec is None:
+        return [int(default)] * n_images
+    try:
+        if os.path.isfile(spec):
+            with open(spec) as f:
+                ids = [int(tok) for tok in f.read().split()]
+        else:
+            ids = [int(tok) for tok in spec.split(",") if tok.strip()]
+    except ValueError:
+        raise SystemExit(f"embedding_v2_biggan: --labels holds integer class ids (a comma list or a text file), got {spec!r}")
+    if len(ids) != n_images:
+        raise SystemExit(f"embedding_v2_biggan: --labels names {len(ids)} class ids for {n_images} images")
+    bad = [v for v in ids if v < 0 or v >= num_classes]
+    if bad:
+        raise SystemExit(f"embedding_v2_biggan: --labels: class ids {bad} lie outside [0, {num_classes})")
+    return ids
+
+
+def rows_plan(n_images, batch_size, labels):
+    """The groups of the rows form: (first image number, rows kept, image number of every row, label of every row) - a short last
+    group repeats its last image and label."""
+    plan = []
+    for first, keep in group_plan(n_images, batch_size):
+        idx = padded_rows(first, batch_size, n_images)
+        plan.append((first, keep, idx, [labels[i] for i in idx]))
+    return plan
 
 
 def main(argv=None):
@@ -340,9 +573,28 @@ def main(argv=None):
     for sub in ("", "imgs", "models", "summaries"):
         os.makedirs(os.path.join(out, sub), exist_ok=True)
     imgs = _load_imgs(args.img_dir, args.img_size, dev)
+    bs = args.batch_size
+    if args.independent:
+        n = imgs.shape[0]
+        labels = read_labels(args.labels, n, G.config.num_classes, args.label)
+        st = BigEmbedRowsStep(G, E, LP, vgg16=vgg, attention=args.attention, label=args.label, lr=args.lr, beta_1=args.beta_1,
+                              truncation=args.truncation, iterations=args.iterations)
+        w_all, img_all = [], []
+        for g, (first, keep, idx, lab) in enumerate(rows_plan(n, bs, labels)):
+            r = invert_big(st, imgs[idx].contiguous(), args.iterations, save_every=args.save_every, out_dir=out, group=g, labels=lab, keep=keep)
+            vals = torch.stack((r["loss_msiv"], r["w_norm"])).cpu()
+            for b in range(keep):
+                print("image %d (label %d): loss_msiv %.5f  w_norm %.4f  events %d" % (first + b, lab[b], float(vals[0, b]), float(vals[1, b]),
+                                                                                     len(r["tracker"][b]["events"])))
+                w_all.append(r["w1"][b].clone().cpu())
+                img_all.append(r["imgs2"][b].clone().cpu())
+            save_image_grid(r["imgs2"][:keep], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
+        if w_all:
+            torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (n - 1)))
+            torch.save(torch.stack(img_all, dim=0), os.path.join(out, "models", "img_all_%d.pt" % (n - 1)))
+        return st
     st = BigEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", vgg16=vgg, attention=args.attention, label=args.label, lr=args.lr,
                       beta_1=args.beta_1, truncation=args.truncation, iterations=args.iterations)
-    bs = args.batch_size
     ngroups = imgs.shape[0] // bs
     w_all, img_all = [], []
     for g in range(ngroups):

@@ -3,6 +3,9 @@
 
 Surface follows the reference: `GradCAM(net, layer_name)`, `GradCamPlusPlus(net, layer_name)`,
 `GuidedBackPropagation(net)` are callables `(inputs, index) -> tensor`, `mask2cam(mask, imgs) -> (heatmap, cam)`.
+Per-row forms (embedding_v2_biggan.BigEmbedRowsStep): `call_per_image(inputs, index)` (the reference's name, grad_cam.py:122-155 -
+every image towards its own class) and `mask2cam(mask, imgs, rows=True)` (every row normalised on its own): row n is what the
+coupled call returns on the one-row slice.
 `net` is `VGG16` below - torchvision.models.vgg16's layout and state_dict keys (`features.{0..28}.weight/bias`,
 `classifier.{0,3,6}.weight/bias`), so the torchvision checkpoint the script downloads loads with load_state_dict;
 without it (this image has neither torchvision nor the weights) the module carries seeded stand-in weights and says
@@ -148,6 +151,25 @@ class VGG16(nn.Module):
         out = torch.empty(1 + N, dtype=torch.int32, device=logits.device)
         g = torch.empty_like(logits)
         check(lib().dge_class_target(_f32(logits), _p(idx_in), _p(out), _f32(g), N, K, _stream()), "dge_class_target")
+        ops._log_dense("class_target")
+        return out, g
+
+    def select_target_rows(self, logits, index=None):
+        """The per-row target of call_per_image (grad_cam.py:129-136) on the device: row n's target is logits[n, index_n] itself.
+        Returns (index tensor int32 [N]: `index` where given, else the first maximum of every row; glogits [N,K], exactly one-hot)."""
+        N, K = logits.shape
+        idx_in = None
+        if index is not None:
+            idx_in = torch.as_tensor(index).reshape(-1)
+            if idx_in.numel() != N:
+                raise ValueError("index must hold one class id per input")
+            if not idx_in.is_cuda and (int(idx_in.min()) < 0 or int(idx_in.max()) >= K):
+                raise ValueError(f"index must lie in [0, {K})")
+            idx_in = idx_in.to(logits.device, torch.int32).contiguous()
+        out = torch.empty(N, dtype=torch.int32, device=logits.device)
+        g = torch.empty_like(logits)
+        check(lib().dge_class_target_rows(_f32(logits), _p(idx_in), _p(out), _f32(g), N, K, _stream()), "dge_class_target_rows")
+        ops._log_dense("class_target_rows")
         return out, g
 
     def _relu_bwd(self, g, a):
@@ -164,15 +186,20 @@ class VGG16(nn.Module):
               "dge_maxpool2_relu_bwd")
         return out
 
-    def backward_to_last_conv(self, st, index_dev):
+    def backward_to_last_conv(self, st, index_dev, rows=False):
         """Gradient of the target w.r.t. the OUTPUT of the last conv (pre-ReLU), NHWC [N,h,w,C] - what the backward hook
-        on `features.28` receives (grad_cam.py:30-40)."""
+        on `features.28` receives (grad_cam.py:30-40).  rows=True: `index_dev` is select_target_rows' [N] tensor and row n is the
+        gradient of its own target logits[n, index_n] (scale 1, a gather of rows: dge_gather_rows, a launch of its own)."""
         L = lib()
         N, dt = st["N"], st["dt"]
         c0, c3, c6 = (getattr(self.classifier, k) for k in ("0", "3", "6"))
         dev = st["h2"].device
         g2 = torch.empty_like(st["h2"])
-        check(L.dge_gather_row(_f32(c6.weight.detach()), _p(index_dev), _f32(g2), N, g2.shape[1], 1.0 / N, _stream()), "dge_gather_row")
+        if rows:
+            check(L.dge_gather_rows(_f32(c6.weight.detach()), _p(index_dev), _f32(g2), N, g2.shape[1], _stream()), "dge_gather_rows")
+            ops._log_dense("gather_rows")
+        else:
+            check(L.dge_gather_row(_f32(c6.weight.detach()), _p(index_dev), _f32(g2), N, g2.shape[1], 1.0 / N, _stream()), "dge_gather_row")
         g2 = self._relu_bwd(g2, st["h2"])
         g1 = ops.linear_t(g2, c3.weight.detach(), torch.empty_like(st["h1"]))
         g1 = self._relu_bwd(g1, st["h1"])
@@ -249,6 +276,17 @@ class GradCAM(object):
         self.feature = st["acts"][-1]
         return self._mask(st)
 
+    def call_per_image(self, inputs, index=None):
+        """grad_cam.py:122-155 (defined on GradCamPlusPlus there): every image against its own target logits[n, index_n], so row n
+        of the mask is what `__call__` returns on inputs[n:n+1].  One forward and one backward for the batch - the network is
+        per sample throughout (eval mode) and row n's backward starts from its own one-hot.  Returns a device tensor [N,1,H,W]
+        like `__call__` (the reference: numpy [N,H,W]); `self.index` is the int32 [N] tensor of the class ids."""
+        logits, st = self.net.run(inputs)
+        self.index, _ = self.net.select_target_rows(logits, index)
+        self.gradient = self.net.backward_to_last_conv(st, self.index, rows=True)
+        self.feature = st["acts"][-1]
+        return self._mask(st)
+
     def with_input_gradient(self, inputs, index=None):
         """(mask, d target / d inputs) from ONE forward and ONE backward.  The script calls `grad_cam_plus_plus(imgs, None)`
         and `gbp(imgs_)` on the same images (E_mis_align_cropping_s1.py:159-168): two forward and two backward passes of
@@ -299,8 +337,9 @@ def _jet_table():
 _JET = {}
 
 
-def mask2cam(mask, imgs):
-    """grad_cam.py:234-251: mask [N,1,H,W], imgs [N,3,H,W] -> (heatmap, cam), both [N,3,H,W] f32 on the device."""
+def mask2cam(mask, imgs, rows=False):
+    """grad_cam.py:234-251: mask [N,1,H,W], imgs [N,3,H,W] -> (heatmap, cam), both [N,3,H,W] f32 on the device.  rows=True: every
+    row is normalised on its own - row n is what mask2cam returns on the one-row slices (dge_mask2cam_rows)."""
     N, _, H, W = imgs.shape
     dev = imgs.device
     if dev not in _JET:
@@ -310,7 +349,13 @@ def mask2cam(mask, imgs):
     heat, cam = torch.empty_like(imgs), torch.empty_like(imgs)
     nblk = lib().dge_mask2cam_blocks(H * W)
     part = torch.empty((N, nblk, 3), dtype=torch.float32, device=dev)
+    if rows:
+        check(lib().dge_mask2cam_rows(_f32(mask), _f32(imgs), _p(_JET[dev]), _f32(heat), _f32(cam), _f32(part), N, H * W, _stream()),
+              "dge_mask2cam_rows")
+        ops._log_dense("mask2cam_rows")
+        return heat, cam
     coef = torch.empty((N, 2), dtype=torch.float32, device=dev)
     check(lib().dge_mask2cam(_f32(mask), _f32(imgs), _p(_JET[dev]), _f32(heat), _f32(cam), _f32(part), _f32(coef), N, H * W,
                              _stream()), "dge_mask2cam")
+    ops._log_dense("mask2cam")
     return heat, cam

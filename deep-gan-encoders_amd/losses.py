@@ -7,8 +7,8 @@ window SSIM, LPIPS value and gradient and the pooled-image gradient, forked to s
 two ends.  _coupled_losses: the sums run over the (global) batch - dge_loss_reduce3 or dge_loss_reduce per window, one exchange of
 the packed sums, dge_space_loss_finalize; the gradient is one of _bwd3 (image_loss_tsa), _bwd_each (space_loss, and
 image_loss_tsa in deterministic mode) and _bwd_split (image_losses_split).  _rows_losses: the per-sample forms image_loss_tsa_rows
-/ space_loss_rows (embedding_v2 `independent`): sample b's loss is what image_loss_tsa / space_loss return on the one-row slices,
-the result is their sum over b (so the gradient of row b is the gradient of its own loss) and the info tensors keep a row per
+/ space_loss_image_rows / space_loss_rows (embedding_v2 `independent`, embedding_v2_biggan.BigEmbedRowsStep): sample b's loss is
+what image_loss_tsa / space_loss return on the one-row slices, the result is their sum over b (so the gradient of row b is the gradient of its own loss) and the info tensors keep a row per
 sample."""
 import contextlib
 import ctypes as C
@@ -452,13 +452,33 @@ def image_loss_tsa_rows(imgs1, imgs2, lpips_model=None, weights=(1.0, 5.0, 9.0),
     return loss, info
 
 
+def space_loss_image_rows(imgs1, imgs2, lpips_model=None, global_batch=None):
+    """space_loss on images [B,3,H,W] or maps [B,1,H,W] with every sample a loss of its own: loss_b is space_loss(imgs1[b:b+1],
+    imgs2[b:b+1], lpips_model=...) - the full window alone, with LPIPS (embedding_v2_biggan.BigEmbedRowsStep).  Returns (sum_b loss_b
+    on device, carrying the analytic gradient - row b of it is d loss_b / d imgs2[b] -, info [B,8] on device).  The same kernels and
+    bits in both reduction modes.  No host synchronisation."""
+    _no_global_batch(global_batch, "space_loss_image_rows")
+    if imgs1.dim() != 4:
+        raise ValueError(f"space_loss_image_rows: images [B,C,H,W], got {tuple(imgs1.shape)} (latents go through space_loss_rows)")
+    a = imgs1.detach().float().contiguous()
+    b = imgs2.detach().float().contiguous()
+    need = imgs2.requires_grad and torch.is_grad_enabled()
+    g = torch.empty_like(b) if need else None
+    info = _rows_losses(a, b, [(0, 0, a.shape[2], a.shape[3])], True, lpips_model, [1.0], [need], gb=g)[:, 0]
+    loss = info[:, 0].sum()
+    if need:
+        loss = _ScaledGrad.apply(imgs2, loss, g)
+    return loss, info
+
+
 def space_loss_rows(imgs1, imgs2, image_space=False, global_batch=None):
     """space_loss on latents with every sample a loss of its own: loss_b is space_loss(imgs1[b:b+1], imgs2[b:b+1],
-    image_space=False) - one row is its own cosine vector and its own softmax group, whatever its rank.  Returns (sum_b loss_b on
-    device with the analytic gradient of both arguments attached where they carry one, info [B,8]).  No host synchronisation."""
+    image_space=False) - one row is its own cosine vector and its own softmax group (2-D latents: a softmax over the row's
+    features).  Returns (sum_b loss_b on device with the analytic gradient of both arguments attached where they carry one, info
+    [B,8]).  No host synchronisation."""
     _no_global_batch(global_batch, "space_loss_rows")
     if image_space:
-        raise ValueError("space_loss_rows: latents only (images go through image_loss_tsa_rows)")
+        raise ValueError("space_loss_rows: latents only (images go through image_loss_tsa_rows / space_loss_image_rows)")
     a = imgs1.detach().float().contiguous()
     b = imgs2.detach().float().contiguous()
     Bt = a.shape[0]
@@ -467,8 +487,11 @@ def space_loss_rows(imgs1, imgs2, image_space=False, global_batch=None):
     need_a, need_b = imgs1.requires_grad and grad, imgs2.requires_grad and grad
     ga = torch.empty_like(a) if need_a else None
     gb = torch.empty_like(b) if need_b else None
-    view = lambda t: t.view(Bt, 1, 1, n_in) if t is not None else None
-    info = _rows_losses(view(a), view(b), [(0, 0, 1, n_in)], False, None, [1.0], [True], ga=view(ga), gb=view(gb))[:, 0]
+    # 2-D latents (BigGAN's w [B,128]): the implicit softmax dim of a one-row slice is 1, the features - they are the planes of a
+    # one-pixel sample, as in space_loss; every other rank: the slice's softmax runs over its batch of one (one plane)
+    shape, win = ((Bt, n_in, 1, 1), (0, 0, 1, 1)) if a.dim() == 2 else ((Bt, 1, 1, n_in), (0, 0, 1, n_in))
+    view = lambda t: t.view(shape) if t is not None else None
+    info = _rows_losses(view(a), view(b), [win], False, None, [1.0], [True], ga=view(ga), gb=view(gb))[:, 0]
     loss = info[:, 0].sum()
     if need_a:
         loss = _ScaledGrad2.apply(imgs1, imgs2, loss, ga, gb if need_b else torch.zeros_like(b))

@@ -640,6 +640,12 @@ int dge_adaptive_pool7_bwd(const float* gy, void* gx, int B, int H, int W, int C
 int dge_class_target(const float* logits, const int* index_in, int* index_out, float* glogits, int B, int K, dge_stream_t stream);
 /* y[b,:] = scale * w[index[0], :]  (w [O,I] f32, index on the device) */
 int dge_gather_row(const float* w, const int* index, float* y, int B, int I, float scale, dge_stream_t stream);
+/* the per-row target (GradCamPlusPlus.call_per_image, grad_cam.py:122-155): index_out[b] = index_in[b] (NULL: the first maximum of
+ * row b; a given id is clamped to [0, K)), glogits[b,k] = (k == index_out[b]) - row b's target is logits[b, index_b] itself.  One
+ * wave per row; plain stores, no atomics, no pre-zeroed buffer: the same bits in both reduction modes. */
+int dge_class_target_rows(const float* logits, const int* index_in, int* index_out, float* glogits, int B, int K, dge_stream_t stream);
+/* y[b,:] = w[index[b], :]  (w [O,I] f32, index [B] on the device, every id in [0, O)); a launch of its own */
+int dge_gather_rows(const float* w, const int* index, float* y, int B, int I, dge_stream_t stream);
 /* per sample, mode 1 = Grad-CAM++ (grad_cam.py:180-191): weight[c] = sum relu(grad) * 1/sum relu(grad) (0 when the sum is 0),
  * cam[p] = sum_c feat[p,c]*weight[c]; mode 0 = Grad-CAM (:101-105): weight[c] = mean grad, cam = relu(sum).  wgt [B,C],
  * cam [B,HW], minmax [B,2] = (min, max) of cam.  grad / feat NHWC [B,HW,C] */
@@ -653,6 +659,12 @@ int dge_cam_resize(const float* cam, const float* minmax, float* mask, int B, in
 int dge_mask2cam_blocks(int HW);
 int dge_mask2cam(const float* mask, const float* img, const int* lut, float* heat, float* cam, float* part, float* coef, int B,
                  int HW, dge_stream_t stream);
+
+/* dge_mask2cam with every row normalised on its own: m = min(cam_b), scl = max(cam_b) - m (the reference's recurrence for a batch
+ * of one).  Two launches (the overlay with its per-block extrema; a fixed-order tree over row b's partials + the apply).
+ * part: scratch [B, dge_mask2cam_blocks(HW), 3] f32 */
+int dge_mask2cam_rows(const float* mask, const float* img, const int* lut, float* heat, float* cam, float* part, int B, int HW,
+                      dge_stream_t stream);
 
 /* ---- inversion loop (embedding_v2.py; reference embedding_v2_styleGAN1.py / embedding_v2_styleGAN2.py) ----------------- */
 /* out[0] = ||w||_p = (sum |w|^p)^(1/p) over all n values (Tensor.norm(p), integer p >= 1), out_l2[0] = ||w||_2; either may be

@@ -7,20 +7,25 @@ round, medians over --rounds rounds.
 --last-stage: the last stage of the E_BIG backward alone when the image carries a gradient, at [B,256,256,64] for B in --batches:
 the one launch (ops.affine_bwd_fromrgb_img) against the launches it replaces (in_bwd with (a, 0, 0) -> fromrgb_dgrad
 [-> fromrgb_bwd]), frozen and trained encoder, alternating, medians over --rounds rounds.
-    python tools/bench_embed_v2_biggan.py --last-stage --batches 1,8"""
+    python tools/bench_embed_v2_biggan.py --last-stage --batches 1,8
+--independent: mode W, batch 1 on the coupled BigEmbedStep against the independent rows (BigEmbedRowsStep, labels 30, 207, 5, ...) at
+every B of --batches - one process, the configurations alternating round by round, medians over --rounds rounds, with the
+round-to-round spread (max - min over the median) of every configuration.
+    python tools/bench_embed_v2_biggan.py --independent --batches 1,2,4,8"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import dge_amd  # noqa: F401
 from dge_amd import autograd_encbig, ops
 from dge_amd.embedding_v2 import strict_bool
-from dge_amd.embedding_v2_biggan import BigEmbedStep, build_models_big_v2
+from dge_amd.embedding_v2_biggan import BigEmbedRowsStep, BigEmbedStep, build_models_big_v2
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--img-size", type=int, default=256); ap.add_argument("--start-features", type=int, default=64)
 ap.add_argument("--batch", type=int, default=1); ap.add_argument("--iters", type=int, default=10); ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--dtype", default="bf16"); ap.add_argument("--attention", type=strict_bool, default=True)
 ap.add_argument("--last-stage", action="store_true"); ap.add_argument("--batches", default="1,8")
+ap.add_argument("--independent", action="store_true")
 a = ap.parse_args()
 res = {}
 
@@ -99,4 +104,37 @@ def bench_loop():
     print(json.dumps(res))
 
 
-bench_last_stage() if a.last_stage else bench_loop()
+def bench_independent():
+    G, E, LP, vgg = build_models_big_v2(None, a.img_size, a.start_features, a.dtype, seed=0, attention=a.attention)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    labels = [30, 207, 5, 1, 9, 100, 417, 980]
+    runs = {}
+
+    def add(name, st, B, **kw):
+        st._setup(B, dev, *([tuple(labels[b % 8] for b in range(B))] if kw else []))
+        with torch.no_grad():
+            imgs1 = G(st.cond_vector[:, :G.config.z_dim].contiguous(), st.conditions, st.truncation)[0].detach().clamp(-1, 1).contiguous()
+        runs[name] = (st, imgs1, B, kw)
+
+    add("coupled_B1", BigEmbedStep(G, E, LP, mode="W", vgg16=vgg, attention=a.attention, iterations=1501), 1)
+    for B in [int(v) for v in a.batches.split(",")]:
+        add(f"rows_B{B}", BigEmbedRowsStep(G, E, LP, vgg16=vgg, attention=a.attention, iterations=1501), B, labels=[labels[b % 8] for b in range(B)])
+    for st, imgs1, B, kw in runs.values():          # (the steps share G and E: mode W leaves both unchanged but for the u / v buffers)
+        st.begin_image(imgs1, **kw)
+        for _ in range(2):
+            st.step(imgs1)
+    ms = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for k, (st, imgs1, B, kw) in runs.items():
+            ms[k].append(timed(lambda: st.step(imgs1), a.iters))
+    for k, v in ms.items():
+        B = runs[k][2]
+        m = median(v)
+        res[k] = dict(ms_per_iteration=round(m, 3), ms_per_image_iteration=round(m / B, 3), spread=round((max(v) - min(v)) / m, 4),
+                      rounds=[round(q, 3) for q in v])
+        print(f"embedding_v2_biggan eager mode W, BigGAN-deep-{a.img_size} + E_BIG, {a.dtype}, attention {a.attention}, {k}: "
+              f"{m:.2f} ms/iteration, {m / B:.2f} ms/image-iteration, round-to-round spread {100 * (max(v) - min(v)) / m:.1f} %", flush=True)
+    print(json.dumps(res))
+
+
+bench_last_stage() if a.last_stage else (bench_independent() if a.independent else bench_loop())
