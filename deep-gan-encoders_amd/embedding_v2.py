@@ -25,9 +25,9 @@ Decisions where the reference cannot run as written:
   * StyleGAN2 generator: the script's wrapper (truncation=0.7, use_w=True) is not in the reference tree.  It is read as a
     rosinality-style wrapper: truncation avg + psi*(w1 - avg) on every row of the W+ code, noise fixed (randomize_noise=False),
     output in [-1, 1].  psi is `truncation` (1: the plain synthesis(w1)).
-  * Trackers are device-side (dge_embed_track): the device keeps the latest best latent of each kind and a bounded event log
-    (iteration, kind, loss, norm); the host writes the final best .pt per kind with the reference's file names and
-    loss_min.txt from the log at the end of each group.
+  * Trackers are device-side (embed_track.EmbedTracker, dge_embed_track): the device keeps the latest best latent of each kind and
+    a bounded event log (iteration, kind, loss, norm); the host writes the final best .pt per kind with the reference's file
+    names and loss_min.txt from the log at the end of each group (finish_group).
   * W mode takes a batch B >= 1 (the reference hard-codes 1); the norm and space_loss terms couple the rows as in the reference.
     StyleGAN2's W-mode start is randn(B, L, 512) from a seeded generator (unseeded in the reference).
   * --optimizeE parses true / false strictly (the reference's `type=bool` cannot be switched off).
@@ -44,6 +44,10 @@ Decisions where the reference cannot run as written:
       - files are numbered by image (g*B + b), not by group; main() pads a short last group by repeating its last image (the
         captured iteration keeps its shape) and discards the padded rows' outputs;
       - the encoder is shared by a group, so mode "E" has no independent form (ValueError).
+
+The file side of a group (dump_group, loss_txt_block, finish_group) and the group walk of main() (invert_folder, rows_plan) serve
+embedding_v2_biggan too: its dumps differ in the two file-name patterns and in the Loss.txt block, its walk in labels and
+img_all_*.pt.
 """
 import argparse
 import math
@@ -53,6 +57,7 @@ import torch
 
 from . import losses, ops, weight_cache
 from .custom_adam import LREQAdam
+from .embed_track import EVENT_LOSS, EVENT_NORM, EmbedTracker, tracker_rules, write_tracker_files  # noqa: F401 (re-exported)
 from .embedding import select_launch
 from .graph_step import GraphReplay
 from .models import add_model_args, blur_encoder, load_lpips_weights
@@ -63,17 +68,6 @@ DEFAULTS = {
     2: dict(iterations=2001, lr=0.005, beta_1=0.0, beta=3e-4, norm_p=2, truncation=0.7),
 }
 IMG_WEIGHTS = (1.0, 0.125 * 3, 0.125 * 5)
-EVENT_LOSS, EVENT_NORM = 0, 1
-
-
-def tracker_rules(generator, iterations):
-    """The reference's best-loss / best-norm `if` chains as parameters of dge_embed_track."""
-    if generator == "sg1":        # armed at iterations//2 (min := that loss), hysteresis 1.05, no norm tracker, reset per group
-        return dict(arm_rule=ops.TRACK_ARM_AT, arm_iter=iterations // 2, loss_hyst=1.05, norm_hyst=0.0, init=(0.0, 0.0),
-                    reset_per_group=True)
-    # iteration > 1000, hysteresis 1.03 / 1.05, minima start at 100 / 1000 and carry over between groups
-    return dict(arm_rule=ops.TRACK_ARM_AFTER, arm_iter=1000, loss_hyst=1.03, norm_hyst=1.05, init=(100.0, 1000.0),
-                reset_per_group=False)
 
 
 class _PNorm(torch.autograd.Function):
@@ -148,7 +142,7 @@ class LatentEmbedStep(GraphReplay):
         self.group = -1
         self.last = {}
         self.w1 = self._const2 = None
-        self._track = None
+        self._tracker = EmbedTracker(self.rules, self.events_cap, rows=self.independent)
         if mode == "E":
             self.opt = LREQAdam([{"params": E.parameters()}], lr=lr, betas=(beta_1, 0.99), weight_decay=0)
             self._ckpt = {k: v.detach().clone() for k, v in E.state_dict().items()}
@@ -161,28 +155,6 @@ class LatentEmbedStep(GraphReplay):
     # ------------------------------------------------------------------ per image group
     def _num_rows(self):
         return self.E.layer_count * 2
-
-    def _track_alloc(self, shape, dev):
-        n = int(math.prod(shape))
-        t = self._track
-        if self.independent:      # a tracker per row: every state array gets a leading batch dimension
-            B = shape[0]
-            if t is None or t["n"] != n or t["fstate"].device != torch.device(dev):
-                self._track = t = dict(n=n, istate=torch.zeros((B, 4), dtype=torch.int32, device=dev),
-                                       fstate=torch.tensor([self.rules["init"]] * B, dtype=torch.float32, device=dev),
-                                       best_loss=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                       best_norm=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                       events=torch.zeros((B, self.events_cap, 4), dtype=torch.float32, device=dev),
-                                       l2=torch.zeros(B, dtype=torch.float32, device=dev))
-            return t
-        if t is None or t["n"] != n or t["fstate"].device != torch.device(dev):
-            self._track = t = dict(n=n, istate=torch.zeros(4, dtype=torch.int32, device=dev),
-                                   fstate=torch.tensor(self.rules["init"], dtype=torch.float32, device=dev),
-                                   best_loss=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                   best_norm=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                   events=torch.zeros((self.events_cap, 4), dtype=torch.float32, device=dev),
-                                   l2=torch.zeros((), dtype=torch.float32, device=dev))
-        return t
 
     def begin_image(self, imgs1, w_init=None, noises=None):
         """Start an image group: E mode re-loads the encoder checkpoint and clears the Adam state (embedding_v2_*.py: the
@@ -221,13 +193,7 @@ class LatentEmbedStep(GraphReplay):
                     self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
                 self.w1.copy_(w0)
             self._reset_opt()
-        t = self._track_alloc(shape, dev)
-        first = getattr(self, "_track_started", False) is False
-        t["istate"].zero_()
-        t["events"].zero_()
-        if first or self.rules["reset_per_group"] or self.independent:
-            t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32).expand_as(t["fstate"]))
-        self._track_started = True
+        self._tracker.reset(shape, dev)
 
     # ------------------------------------------------------------------ one iteration
     def _generate(self, w1, noises):
@@ -244,8 +210,7 @@ class LatentEmbedStep(GraphReplay):
         (`loss_msiv`, `loss_w`, `loss_c1`, `norm`, `loss_mslv`, `w_norm`) are [B], `info_img` is [B,3,8]."""
         E = self.E
         rows = self.independent
-        t = self._track
-        if t is None:
+        if self.group < 0:
             raise RuntimeError("LatentEmbedStep.step: call begin_image() first")
         ops.zero_arena_begin(imgs1.device)
         if self.mode == "E":
@@ -274,7 +239,6 @@ class LatentEmbedStep(GraphReplay):
         loss_mslv.backward()
         self.opt.step()
         w1d = w1.detach()
-        r = self.rules
         if rows:      # the values of every row: the [B] columns of the info tensors (the scalars above are their sums over the rows)
             loss_msiv = info_img[:, 0, 0] * IMG_WEIGHTS[0] + info_img[:, 1, 0] * IMG_WEIGHTS[1] + info_img[:, 2, 0] * IMG_WEIGHTS[2]
             loss_w = info_w[:, 0].contiguous()
@@ -282,18 +246,12 @@ class LatentEmbedStep(GraphReplay):
             if loss_c1 is not None:
                 loss_c1 = info_c[:, 0].contiguous()
                 loss_mslv = loss_mslv + loss_c1 * 0.01
-            ops.latent_l2_rows(w1d, out=t["l2"])
-            ops.embed_track_rows(loss_msiv, t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
-                                 r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
-        else:
-            ops.latent_l2(w1d, out=t["l2"])
-            ops.embed_track(loss_msiv.detach(), t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
-                            r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
+        self._tracker.update(loss_msiv.detach(), w1d)
         ops.zero_arena_end()
         self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const2=const2.detach() if const2 is not None else None,
                          const3=const3.detach(), loss_msiv=loss_msiv.detach(), info_img=info_img, loss_w=loss_w.detach(),
                          loss_c1=loss_c1.detach() if loss_c1 is not None else None, norm=nrm.detach(), loss_mslv=loss_mslv.detach(),
-                         w_norm=t["l2"])
+                         w_norm=self._tracker.l2)
         return self.last
 
     # ------------------------------------------------------------------ hipGraph replay of the iteration
@@ -329,48 +287,7 @@ class LatentEmbedStep(GraphReplay):
     # ------------------------------------------------------------------ tracker read-out (one host read)
     def tracker(self):
         """The tracker's state on the host; independent mode: a list with one such read-out per row."""
-        t = self._track
-        if self.independent:
-            B, cap = t["istate"].shape[0], self.events_cap
-            # one host read: the three small state arrays travel as one float tensor (counters < 2^24 are exact in f32)
-            host = torch.cat((t["istate"].float(), t["fstate"], t["events"].reshape(B, -1)), dim=1).cpu()
-            bl, bn = t["best_loss"], t["best_norm"]
-            out = []
-            for b in range(B):
-                ist = [int(v) for v in host[b, :4]]
-                ev = host[b, 6:].view(cap, 4)
-                idx = [k % cap for k in range(max(0, ist[1] - cap), ist[1])]
-                out.append(dict(iteration=ist[0], events=[(int(ev[i, 0]), int(ev[i, 1]), float(ev[i, 2]), float(ev[i, 3])) for i in idx],
-                                dropped=ist[2], min_loss=float(host[b, 4]), min_norm=float(host[b, 5]), best_loss=bl[b:b + 1].clone(), best_norm=bn[b:b + 1].clone()))
-            return out
-        ist = t["istate"].cpu().tolist()
-        cnt, cap = ist[1], self.events_cap
-        ev = t["events"].cpu()
-        idx = [k % cap for k in range(max(0, cnt - cap), cnt)]
-        events = [(int(ev[i, 0]), int(ev[i, 1]), float(ev[i, 2]), float(ev[i, 3])) for i in idx]
-        return dict(iteration=ist[0], events=events, dropped=ist[2], min_loss=float(t["fstate"][0]), min_norm=float(t["fstate"][1]),
-                    best_loss=t["best_loss"].clone(), best_norm=t["best_norm"].clone())
-
-
-def write_tracker_files(tr, g, models_dir, result_dir):
-    """The reference's outputs of the trackers for group g: the final best latent per kind (file names of
-    embedding_v2_styleGAN2.py:156,163) and loss_min.txt lines (:159,166) from the event log."""
-    last = {}
-    loss_min = None
-    with open(os.path.join(result_dir, "loss_min.txt"), "a+") as f:
-        for it, kind, loss, norm in tr["events"]:
-            if kind == EVENT_LOSS:
-                loss_min = loss
-                print("ep%d_iter%d_minImg%.5f_wNorm%f" % (g, it, loss, norm), file=f)
-            else:
-                print("ep%d_iter%d_Img%.5f_wNorm-min%f" % (g, it, loss, norm), file=f)
-            last[kind] = (it, loss, norm, loss_min)
-    if EVENT_LOSS in last:
-        it, loss, norm, _ = last[EVENT_LOSS]
-        torch.save(tr["best_loss"], os.path.join(models_dir, "id%d-iter%d-norm%f-imgLoss-min%f.pt" % (g, it, norm, loss)))
-    if EVENT_NORM in last:
-        it, loss, norm, lm = last[EVENT_NORM]
-        torch.save(tr["best_norm"], os.path.join(models_dir, "id%d-iter%d-norm-min%f-imgLoss%f.pt" % (g, it, norm, lm if lm is not None else 0.0)))
+        return self._tracker.read()
 
 
 def group_plan(n_images, batch_size):
@@ -385,54 +302,121 @@ def padded_rows(first, batch_size, n_images):
     return [min(first + r, n_images - 1) for r in range(batch_size)]
 
 
+def rows_plan(n_images, batch_size, labels=None):
+    """The groups of the rows form: (first image number, rows kept, image number of every row, label of every row - None without
+    `labels`) - a short last group repeats its last image and label."""
+    plan = []
+    for first, keep in group_plan(n_images, batch_size):
+        idx = padded_rows(first, batch_size, n_images)
+        plan.append((first, keep, idx, None if labels is None else [labels[i] for i in idx]))
+    return plan
+
+
+# ------------------------------------------------------------------ files of a group (shared with embedding_v2_biggan)
+IMG_NAME, W_NAME = "id{n}_ep{i}-norm{norm:.2f}-imgLoss{loss:f}.jpg", "id{n}-i{k}-w{i}-norm{norm:f}-imgLoss{loss:f}.pt"
+LOSS_TXT_IMAGE = (("info_mask", "loss_small_info"), ("info_Gcam", "loss_medium_info"), ("info_imgs", "loss_imgs_info"))
+LOSS_TXT_LATENT = (("info_w", "loss_w_info"), ("info_c2", "loss_c2_info"))
+
+
+def loss_txt_block(f, num, i, infos, loss):
+    """One Loss.txt block of embedding_v2_BigGAN.py:204-215 for image (group) `num` at iteration i; `infos`: the [8] info vectors
+    (losses.space_loss) by result key - without the attention terms the small / medium lines are absent."""
+    print("id_" + str(num) + "_____i_" + str(i), file=f)
+    print("[loss_imgs_mse[img,img_mean,img_std], loss_imgs_kl, loss_imgs_cosine, loss_imgs_ssim, loss_imgs_lpips]", file=f)
+    def lines(keys):
+        for key, name in keys:
+            if key in infos:
+                print("%s: [[%s, %s, %s], %s, %s, %s, %s]" % ((name,) + tuple(float(x) for x in infos[key][1:8])), file=f)
+    print("---------ImageSpace--------", file=f)
+    lines(LOSS_TXT_IMAGE)
+    print("---------LatentSpace--------", file=f)
+    lines(LOSS_TXT_LATENT)
+    print("Img_loss: %s" % loss, file=f)
+
+
+def dump_group(st, imgs1, r, i, out_dir, group, keep=None, img_name=IMG_NAME, w_name=W_NAME, loss_txt=False):
+    """The every-`save_every` dump of iteration i (norm and loss of all rows in one host read): the image pair and one w1 file per
+    row; `loss_txt`: a Loss.txt block too.  Coupled form: one pair and one block for the group, named by `group`.  Independent
+    form: a pair, a block and a w1 file for each of the first `keep` rows (default: all), named by the image number group * B + b,
+    with that row's norm and loss.  `img_name` / `w_name`: format patterns of n (number), i, k (row of the file set), norm, loss."""
+    from .infer import save_image_grid
+    B = imgs1.shape[0]
+    vals = torch.stack((r["w_norm"], r["loss_msiv"])).reshape(2, -1).cpu()
+    infos = {k: r[k].cpu() for k, _ in LOSS_TXT_IMAGE + LOSS_TXT_LATENT if k in r} if loss_txt else {}
+    w1 = r["w1"].cpu()
+    units = [(group, 0, slice(0, B))]          # (number, column of vals, rows of the batch)
+    if st.independent:
+        units = [(group * B + b, b, slice(b, b + 1)) for b in range(B if keep is None else keep)]
+    for num, b, sl in units:
+        names = dict(n=num, i=i, norm=float(vals[0, b]), loss=float(vals[1, b]))
+        save_image_grid(torch.cat((imgs1[sl], r["imgs2"][sl])), os.path.join(out_dir, "imgs", img_name.format(**names)), nrow=2)
+        if loss_txt:
+            with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
+                loss_txt_block(f, num, i, {k: (v[b] if st.independent else v) for k, v in infos.items()}, names["loss"])
+        for k, row in enumerate(w1[sl]):
+            torch.save(row.unsqueeze(0).clone(), os.path.join(out_dir, "models", w_name.format(k=k, **names)))
+
+
+def finish_group(st, r, B, out_dir, group, keep=None):
+    """The end of a group: the tracker read-out, its files with `out_dir` (independent form: per kept row, numbered group * B + b),
+    and the result dict with the read-out under "tracker"."""
+    tr = st.tracker()
+    if out_dir is not None:
+        models = os.path.join(out_dir, "models")
+        if st.independent:
+            for b in range(B if keep is None else keep):
+                write_tracker_files(tr[b], group * B + b, models, out_dir)
+        else:
+            write_tracker_files(tr, group, models, out_dir)
+    return dict(r, tracker=tr)
+
+
+def invert_folder(invert, imgs, bs, independent, out, labels=None, save_imgs=False):
+    """The group walk of the CLIs: `invert(imgs1, group=g, **kw)` runs one group.  Coupled: the n // bs full groups, one line, one
+    `summaries/<g>_rec.png` and w1[0] per group, models/w_all_<groups-1>.pt.  Independent: every image (rows_plan), a line and a w1
+    per kept row, models/w_all_<n-1>.pt; `labels` (one class id per image) go to `invert` row by row.  `save_imgs`: the kept
+    reconstructions too, as models/img_all_*.pt."""
+    from .infer import save_image_grid
+    n = imgs.shape[0]
+    plan = rows_plan(n, bs, labels) if independent else [(g * bs, bs, list(range(g * bs, (g + 1) * bs)), None) for g in range(n // bs)]
+    w_all, img_all = [], []
+    for g, (first, keep, idx, lab) in enumerate(plan):
+        kw = dict(keep=keep, **({} if lab is None else {"labels": lab})) if independent else {}
+        r = invert(imgs[idx].contiguous(), group=g, **kw)
+        vals = torch.stack((r["loss_msiv"], r["w_norm"])).reshape(2, -1).cpu()
+        trs = r["tracker"] if independent else [r["tracker"]]
+        for b in range(keep if independent else 1):
+            who = ("image %d" % (first + b) + ("" if lab is None else " (label %d)" % lab[b])) if independent else "group %d" % g
+            print("%s: loss_msiv %.5f  w_norm %.4f  events %d" % (who, float(vals[0, b]), float(vals[1, b]), len(trs[b]["events"])))
+            w_all.append(r["w1"][b].clone().cpu())
+            if save_imgs:
+                img_all.append(r["imgs2"][b].clone().cpu())
+        save_image_grid(r["imgs2"][:keep], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
+    if w_all:
+        torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (len(w_all) - 1)))
+        if save_imgs:
+            torch.save(torch.stack(img_all, dim=0), os.path.join(out, "models", "img_all_%d.pt" % (len(w_all) - 1)))
+
+
 def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=None, group=0, w_init=None, keep=None):
     """`iterations` iterations on one image group.  launch="graph" captures the iteration once (its warm-up iteration is a real one)
-    and replays it; later groups go through set_image.  With `out_dir` the reference's every-`save_every` dumps (image pair,
-    per-row w1) are written - one host read per chunk - and, at the end, the trackers' files.  Returns the last result dict with
-    the tracker read-out under "tracker".  Independent mode: files carry the image number group*B + b and that row's norm and loss;
-    only the first `keep` rows (default: all) are written, and "tracker" is the list of per-row read-outs."""
+    and replays it; later groups go through set_image.  With `out_dir` the reference's every-`save_every` dumps (dump_group: image
+    pair, per-row w1) are written and, at the end, the trackers' files (finish_group).  Returns the last result dict with the tracker
+    read-out under "tracker".  Independent mode: files carry the image number group*B + b and that row's norm and loss; only the
+    first `keep` rows (default: all) are written, and "tracker" is the list of per-row read-outs."""
     st.begin_image(imgs1, w_init=w_init)
     if launch not in ("graph", "eager"):
         raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
     run, done = select_launch(st, imgs1, launch)
     r = st.last
-
-    def dump(i, r):
-        if out_dir is None:
-            return
-        from .infer import save_image_grid
-        B = imgs1.shape[0]
-        if st.independent:
-            vals = torch.stack((r["w_norm"], r["loss_msiv"])).cpu()
-            for b in range(B if keep is None else keep):
-                num, norm, loss = group * B + b, float(vals[0, b]), float(vals[1, b])
-                save_image_grid(torch.cat((imgs1[b:b + 1], r["imgs2"][b:b + 1])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f-imgLoss%f.jpg"
-                                                                                              % (num, i, norm, loss)), nrow=2)
-                torch.save(r["w1"][b:b + 1].clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f-imgLoss%f.pt"
-                                                                        % (num, 0, i, norm, loss)))
-            return
-        norm, loss = float(r["w_norm"]), float(r["loss_msiv"])
-        save_image_grid(torch.cat((imgs1[:B], r["imgs2"][:B])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f-imgLoss%f.jpg"
-                                                                            % (group, i, norm, loss)), nrow=2)
-        for k, row in enumerate(r["w1"]):
-            torch.save(row.unsqueeze(0).clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f-imgLoss%f.pt"
-                                                                     % (group, k, i, norm, loss)))
-
-    if done and save_every:
-        dump(0, r)                              # iteration 0 ran as capture()'s warm-up
+    dumps = out_dir is not None and save_every
+    if done and dumps:
+        dump_group(st, imgs1, r, 0, out_dir, group, keep)          # iteration 0 ran as capture()'s warm-up
     for i in range(done, iterations):
         r = run()
-        if save_every and i % save_every == 0:
-            dump(i, r)
-    tr = st.tracker()
-    if out_dir is not None and st.independent:
-        for b in range(imgs1.shape[0] if keep is None else keep):
-            write_tracker_files(tr[b], group * imgs1.shape[0] + b, os.path.join(out_dir, "models"), out_dir)
-    elif out_dir is not None:
-        write_tracker_files(tr, group, os.path.join(out_dir, "models"), out_dir)
-    r = dict(r)
-    r["tracker"] = tr
-    return r
+        if dumps and i % save_every == 0:
+            dump_group(st, imgs1, r, i, out_dir, group, keep)
+    return finish_group(st, r, imgs1.shape[0], out_dir, group, keep)
 
 
 ENCODERS = ("blur", "be")
@@ -551,7 +535,6 @@ def main(argv=None):
     args = parse_args(argv)
     if args.deterministic:
         ops.set_deterministic(True)
-    from .infer import save_image_grid
     dev = "cuda"
     G, E, LP = build_models_v2(args.mtype, args.img_size, args.start_features, args.compute_dtype, device=dev, seed=args.seed,
                                fmaps_base=args.fmaps_base, fmaps_max=args.fmaps_max, enc_maxf=args.enc_maxf, encoder=args.encoder)
@@ -564,31 +547,8 @@ def main(argv=None):
     st = LatentEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", generator="sg1" if args.mtype == 1 else "sg2", lr=args.lr,
                          beta_1=args.beta_1, beta=args.beta, norm_p=args.norm_p, truncation=args.truncation,
                          iterations=args.iterations, seed=args.seed, independent=args.independent)
-    bs = args.batch_size
-    w_all = []
-    if args.independent:
-        n = imgs.shape[0]
-        for g, (first, keep) in enumerate(group_plan(n, bs)):
-            imgs1 = imgs[padded_rows(first, bs, n)].contiguous()
-            r = invert_v2(st, imgs1, args.iterations, launch=args.launch, save_every=args.save_every, out_dir=out, group=g, keep=keep)
-            vals = torch.stack((r["loss_msiv"], r["w_norm"])).cpu()
-            for b in range(keep):
-                print("image %d: loss_msiv %.5f  w_norm %.4f  events %d" % (first + b, float(vals[0, b]), float(vals[1, b]),
-                                                                          len(r["tracker"][b]["events"])))
-                w_all.append(r["w1"][b].clone().cpu())
-            save_image_grid(r["imgs2"][:keep], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
-        if w_all:
-            torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (n - 1)))
-        return st
-    ngroups = imgs.shape[0] // bs
-    for g in range(ngroups):
-        imgs1 = imgs[g * bs:(g + 1) * bs].contiguous()
-        r = invert_v2(st, imgs1, args.iterations, launch=args.launch, save_every=args.save_every, out_dir=out, group=g)
-        print("group %d: loss_msiv %.5f  w_norm %.4f  events %d" % (g, float(r["loss_msiv"]), float(r["w_norm"]), len(r["tracker"]["events"])))
-        save_image_grid(r["imgs2"], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
-        w_all.append(r["w1"][0].clone().cpu())
-    if w_all:
-        torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (ngroups - 1)))
+    invert_folder(lambda imgs1, **kw: invert_v2(st, imgs1, args.iterations, launch=args.launch, save_every=args.save_every, out_dir=out, **kw),
+                  imgs, args.batch_size, args.independent, out)
     return st
 
 

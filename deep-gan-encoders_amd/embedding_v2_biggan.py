@@ -31,8 +31,9 @@ Decisions:
     network as in the script (:56-57: from then on every backward of that network is the guided one, the masks' too) but never
     called: the guided-backprop gradients and the heat maps the script also computes are unused and are not produced.
     attention=True is the default (it needs the vgg16 network); --attention false leaves the two terms out.
-  * Tracker.  The device-side dge_embed_track with embedding_v2.tracker_rules("sg1", iterations): armed at iterations // 2,
-    hysteresis 1.05, no norm tracker, minima restart per group; files through embedding_v2.write_tracker_files (the script's names).
+  * Tracker.  embed_track.EmbedTracker (the device-side dge_embed_track) with tracker_rules("sg1", iterations): armed at
+    iterations // 2, hysteresis 1.05, no norm tracker, minima restart per group; files through embedding_v2.finish_group (the
+    script's names), the dumps through embedding_v2.dump_group, the folder walk of main() through embedding_v2.invert_folder.
   * Not offered, each a ValueError / SystemExit with a clear message: capture() / hipGraph replay (the power iterations are
     host-sequenced; --mtype 4 is excluded from capture elsewhere too), independent=True on BigEmbedStep (the rows form is a class of
     its own, below), more than one process, and --beta / --norm_p (the norm term is commented out in the script, :163).
@@ -59,7 +60,8 @@ import torch
 
 from . import losses, ops, weight_cache
 from .custom_adam import LREQAdam
-from .embedding_v2 import _load_imgs, group_plan, padded_rows, strict_bool, tracker_rules, write_tracker_files
+from .embed_track import EmbedTracker, tracker_rules
+from .embedding_v2 import _load_imgs, dump_group, finish_group, invert_folder, rows_plan, strict_bool  # noqa: F401 (rows_plan: re-exported)
 from .generators import truncated_noise_sample
 from .models import add_model_args, load_lpips_weights
 
@@ -77,6 +79,8 @@ MSG_INDEPENDENT = ("BigEmbedStep: independent=True is not offered (the script co
 MSG_ROWS_MODE = "BigEmbedRowsStep: mode 'W' only - in mode 'E' one encoder is shared by the rows of a group"
 MSG_DIST = "BigEmbedStep: more than one process is not offered (the inversion loop is a single-process loop)"
 MSG_NORM = "embedding_v2_biggan: --beta / --norm_p are not offered (the norm term is commented out in embedding_v2_BigGAN.py:163)"
+# dump names (embedding_v2.dump_group): the script names neither file by the loss (:203,218)
+IMG_NAME, W_NAME = "id{n}_ep{i}-norm{norm:.2f}.jpg", "id{n}-i{k}-w{i}-norm{norm:f}.pt"
 
 
 class BigEmbedStep:
@@ -102,9 +106,10 @@ class BigEmbedStep:
         if arm_iter is not None:
             self.rules["arm_iter"] = int(arm_iter)
         self.events_cap = int(events_cap)
+        self._tracker = EmbedTracker(self.rules, self.events_cap, rows=self.independent)
         self.group = -1
         self.last = {}
-        self.w1 = self._const1 = self._track = None
+        self.w1 = self._const1 = None
         self.conditions = self.cond_vector = None
         for p in G.parameters():
             p.requires_grad_(False)
@@ -121,7 +126,7 @@ class BigEmbedStep:
                 p.requires_grad_(False)
             self.opt = None
 
-    captured = False
+    captured = independent = False
 
     def capture(self, *a, **kw):
         raise ValueError(MSG_CAPTURE)
@@ -156,24 +161,19 @@ class BigEmbedStep:
             weight_cache.written(self.E.parameters())
             self.opt.state = collections.defaultdict(dict)
         else:
-            with torch.no_grad():
-                c0, w0 = self.E(imgs1, self.cond_vector, noises=noises)
-                self._const1 = c0.detach().clone()
-                if w_init is not None:
-                    w0 = w_init.to(dev, torch.float32).reshape(shape)
-            self.w1 = w0.detach().clone().requires_grad_(True)
-            self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
-        t = self._track
-        if t is None or t["best_loss"].shape != shape or t["fstate"].device != dev:
-            self._track = t = dict(istate=torch.zeros(4, dtype=torch.int32, device=dev),
-                                   fstate=torch.zeros(2, dtype=torch.float32, device=dev),
-                                   best_loss=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                   best_norm=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                   events=torch.zeros((self.events_cap, 4), dtype=torch.float32, device=dev),
-                                   l2=torch.zeros((), dtype=torch.float32, device=dev))
-        t["istate"].zero_()
-        t["events"].zero_()
-        t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32))          # minima restart per group (:88)
+            self._start_w(imgs1, shape, w_init, noises)
+        self._tracker.reset(shape, dev)          # (sg1 rules: the minima restart per group, :88)
+
+    def _start_w(self, imgs1, shape, w_init, noises):
+        """Mode W: const1, w1 = E(imgs1, cond_vector) under no_grad - const1 stays as the logged constant, w1 (or `w_init`) becomes
+        the leaf, with a fresh LREQAdam on it."""
+        with torch.no_grad():
+            c0, w0 = self.E(imgs1, self.cond_vector, noises=noises)
+            self._const1 = c0.detach().clone()
+            if w_init is not None:
+                w0 = w_init.to(imgs1.device, torch.float32).reshape(shape)
+        self.w1 = w0.detach().clone().requires_grad_(True)
+        self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
 
     # ------------------------------------------------------------------ one iteration
     def _attention_terms(self, imgs1, imgs2):
@@ -191,8 +191,8 @@ class BigEmbedStep:
 
     def step(self, imgs1, noises=(None, None)):
         """One iteration; `noises` = optional (E(imgs1), E(imgs2)) noise lists for parity runs (mode W: E(imgs1)'s is unused)."""
-        E, t = self.E, self._track
-        if t is None:
+        E = self.E
+        if self.group < 0:
             raise RuntimeError("BigEmbedStep.step: call begin_image() first")
         ops.zero_arena_begin(imgs1.device)
         if self.mode == "E":
@@ -217,26 +217,18 @@ class BigEmbedStep:
         loss_mslv.backward()
         self.opt.step()
         w1d = w1.detach()
-        r = self.rules
-        ops.latent_l2(w1d, out=t["l2"])
-        ops.embed_track(loss_msiv.detach(), t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
-                        r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
+        self._tracker.update(loss_msiv.detach(), w1d)
         ops.zero_arena_end()
         self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const1=const1.detach(), const2=const2.detach(),
                          loss_msiv=loss_msiv.detach(), loss_imgs=loss_imgs.detach(), info_imgs=info_imgs, loss_w=loss_w.detach(),
-                         info_w=info_w, loss_c2=loss_c2.detach(), info_c2=info_c2, loss_mslv=loss_mslv.detach(), w_norm=t["l2"], **att)
+                         info_w=info_w, loss_c2=loss_c2.detach(), info_c2=info_c2, loss_mslv=loss_mslv.detach(),
+                         w_norm=self._tracker.l2, **att)
         return self.last
 
     # ------------------------------------------------------------------ tracker read-out (one host read)
     def tracker(self):
-        t = self._track
-        ist = t["istate"].cpu().tolist()
-        cnt, cap = ist[1], self.events_cap
-        ev = t["events"].cpu()
-        idx = [k % cap for k in range(max(0, cnt - cap), cnt)]
-        events = [(int(ev[i, 0]), int(ev[i, 1]), float(ev[i, 2]), float(ev[i, 3])) for i in idx]
-        return dict(iteration=ist[0], events=events, dropped=ist[2], min_loss=float(t["fstate"][0]), min_norm=float(t["fstate"][1]),
-                    best_loss=t["best_loss"].clone(), best_norm=t["best_norm"].clone())
+        """The tracker's state on the host; rows form: a list with one such read-out per row."""
+        return self._tracker.read()
 
 
 class BigEmbedRowsStep(BigEmbedStep):
@@ -292,24 +284,8 @@ class BigEmbedRowsStep(BigEmbedStep):
         self._setup(B, dev, self._row_labels(labels, B))
         self.group += 1
         shape = (B, self.G.config.z_dim)
-        with torch.no_grad():
-            c0, w0 = self.E(imgs1, self.cond_vector, noises=noises)
-            self._const1 = c0.detach().clone()
-            if w_init is not None:
-                w0 = w_init.to(dev, torch.float32).reshape(shape)
-        self.w1 = w0.detach().clone().requires_grad_(True)
-        self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
-        t = self._track
-        if t is None or t["best_loss"].shape != shape or t["fstate"].device != dev:      # a tracker per row: a leading B everywhere
-            self._track = t = dict(istate=torch.zeros((B, 4), dtype=torch.int32, device=dev),
-                                   fstate=torch.zeros((B, 2), dtype=torch.float32, device=dev),
-                                   best_loss=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                   best_norm=torch.zeros(shape, dtype=torch.float32, device=dev),
-                                   events=torch.zeros((B, self.events_cap, 4), dtype=torch.float32, device=dev),
-                                   l2=torch.zeros(B, dtype=torch.float32, device=dev))
-        t["istate"].zero_()
-        t["events"].zero_()
-        t["fstate"].copy_(torch.tensor(self.rules["init"], dtype=torch.float32).expand_as(t["fstate"]))      # minima restart per group
+        self._start_w(imgs1, shape, w_init, noises)
+        self._tracker.reset(shape, dev)
 
     def _attention_terms(self, imgs1, imgs2):
         """Per row: space_loss_b(mask_1, mask_2) and space_loss_b(cam_1, cam_2) as values, every row's mask towards its own arg-max
@@ -328,8 +304,8 @@ class BigEmbedRowsStep(BigEmbedStep):
     def step(self, imgs1, noises=(None, None)):
         """One iteration of every row; `noises` as BigEmbedStep.step.  The attention terms are values (the script detaches them): they
         enter every row's loss_msiv, and phase 1 back-propagates sum_b space_loss_b(imgs1, imgs2)."""
-        E, t = self.E, self._track
-        if t is None:
+        E = self.E
+        if self.group < 0:
             raise RuntimeError("BigEmbedRowsStep.step: call begin_image() first")
         ops.zero_arena_begin(imgs1.device)
         w1, const1 = self.w1, self._const1
@@ -352,60 +328,12 @@ class BigEmbedRowsStep(BigEmbedStep):
         self.opt.step()
         loss_w = info_w[:, 0].contiguous()
         w1d = w1.detach()
-        r = self.rules
-        ops.latent_l2_rows(w1d, out=t["l2"])
-        ops.embed_track_rows(loss_msiv, t["l2"], w1d, t["istate"], t["fstate"], t["best_loss"], t["best_norm"], t["events"],
-                             r["arm_rule"], r["arm_iter"], r["loss_hyst"], r["norm_hyst"])
+        self._tracker.update(loss_msiv, w1d)
         ops.zero_arena_end()
         self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const1=const1.detach(), const2=const2.detach(),
                          loss_msiv=loss_msiv, loss_imgs=loss_imgs, info_imgs=info_imgs, loss_w=loss_w, info_w=info_w,
-                         loss_c2=info_c2[:, 0].contiguous(), info_c2=info_c2, loss_mslv=loss_w * 0.01, w_norm=t["l2"], **att)
+                         loss_c2=info_c2[:, 0].contiguous(), info_c2=info_c2, loss_mslv=loss_w * 0.01, w_norm=self._tracker.l2, **att)
         return self.last
-
-    def tracker(self):
-        """A list with one read-out per row (one host read)."""
-        t = self._track
-        B, cap = t["istate"].shape[0], self.events_cap
-        host = torch.cat((t["istate"].float(), t["fstate"], t["events"].reshape(B, -1)), dim=1).cpu()      # counters < 2^24: exact in f32
-        out = []
-        for b in range(B):
-            ist = [int(v) for v in host[b, :4]]
-            ev = host[b, 6:].view(cap, 4)
-            idx = [k % cap for k in range(max(0, ist[1] - cap), ist[1])]
-            out.append(dict(iteration=ist[0], events=[(int(ev[i, 0]), int(ev[i, 1]), float(ev[i, 2]), float(ev[i, 3])) for i in idx],
-                            dropped=ist[2], min_loss=float(host[b, 4]), min_norm=float(host[b, 5]),
-                            best_loss=t["best_loss"][b:b + 1].clone(), best_norm=t["best_norm"][b:b + 1].clone()))
-        return out
-
-
-def _info_line(info):
-    v = [float(x) for x in info.cpu()]
-    return "[[%s, %s, %s], %s, %s, %s, %s]" % tuple(v[1:8])
-
-
-def _dump_rows(st, imgs1, r, i, out_dir, group, keep):
-    """The every-`save_every` dump of the rows form: per image (number group * B + b) the image pair, w1 and a Loss.txt block."""
-    from .infer import save_image_grid
-    B = imgs1.shape[0]
-    vals = torch.stack((r["w_norm"], r["loss_msiv"])).cpu()
-    infos = {k: r[k].cpu() for k in ("info_mask", "info_Gcam", "info_imgs", "info_w", "info_c2") if k in r}
-    for b in range(keep):
-        num, norm, loss = group * B + b, float(vals[0, b]), float(vals[1, b])
-        save_image_grid(torch.cat((imgs1[b:b + 1], r["imgs2"][b:b + 1])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f.jpg" % (num, i, norm)),
-                        nrow=2)
-        with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
-            print("id_" + str(num) + "_____i_" + str(i), file=f)
-            print("[loss_imgs_mse[img,img_mean,img_std], loss_imgs_kl, loss_imgs_cosine, loss_imgs_ssim, loss_imgs_lpips]", file=f)
-            print("---------ImageSpace--------", file=f)
-            if st.attention:
-                print("loss_small_info: %s" % _info_line(infos["info_mask"][b]), file=f)
-                print("loss_medium_info: %s" % _info_line(infos["info_Gcam"][b]), file=f)
-            print("loss_imgs_info: %s" % _info_line(infos["info_imgs"][b]), file=f)
-            print("---------LatentSpace--------", file=f)
-            print("loss_w_info: %s" % _info_line(infos["info_w"][b]), file=f)
-            print("loss_c2_info: %s" % _info_line(infos["info_c2"][b]), file=f)
-            print("Img_loss: %s" % loss, file=f)
-        torch.save(r["w1"][b:b + 1].clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f.pt" % (num, 0, i, norm)))
 
 
 def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0, labels=None, keep=None):
@@ -414,12 +342,8 @@ def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0, lab
     Returns the last result dict with the tracker read-out under "tracker".  Rows form (BigEmbedRowsStep; `labels`: one class id per
     row): files carry the image number group * B + b, Loss.txt gets a block per image, only the first `keep` rows (default: all) are
     written, and "tracker" is the list of per-row read-outs."""
-    from .infer import save_image_grid
-    rows = getattr(st, "independent", False)
-    B = imgs1.shape[0]
-    if rows:
+    if st.independent:
         st.begin_image(imgs1, labels=labels)
-        keep = B if keep is None else keep
     elif labels is not None or keep is not None:
         raise ValueError("invert_big: labels / keep belong to the rows form (BigEmbedRowsStep)")
     else:
@@ -427,37 +351,9 @@ def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0, lab
     r = st.last
     for i in range(iterations):
         r = st.step(imgs1)
-        if rows:
-            if out_dir is not None and save_every and i % save_every == 0:
-                _dump_rows(st, imgs1, r, i, out_dir, group, keep)
-            continue
         if out_dir is not None and save_every and i % save_every == 0:
-            norm = float(r["w_norm"])
-            save_image_grid(torch.cat((imgs1[:B], r["imgs2"][:B])), os.path.join(out_dir, "imgs", "id%d_ep%d-norm%.2f.jpg" % (group, i, norm)),
-                            nrow=2)
-            with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
-                print("id_" + str(group) + "_____i_" + str(i), file=f)
-                print("[loss_imgs_mse[img,img_mean,img_std], loss_imgs_kl, loss_imgs_cosine, loss_imgs_ssim, loss_imgs_lpips]", file=f)
-                print("---------ImageSpace--------", file=f)
-                if st.attention:
-                    print("loss_small_info: %s" % _info_line(r["info_mask"]), file=f)
-                    print("loss_medium_info: %s" % _info_line(r["info_Gcam"]), file=f)
-                print("loss_imgs_info: %s" % _info_line(r["info_imgs"]), file=f)
-                print("---------LatentSpace--------", file=f)
-                print("loss_w_info: %s" % _info_line(r["info_w"]), file=f)
-                print("loss_c2_info: %s" % _info_line(r["info_c2"]), file=f)
-                print("Img_loss: %s" % float(r["loss_msiv"]), file=f)
-            for k, row in enumerate(r["w1"]):
-                torch.save(row.unsqueeze(0).clone().cpu(), os.path.join(out_dir, "models", "id%d-i%d-w%d-norm%f.pt" % (group, k, i, norm)))
-    tr = st.tracker()
-    if out_dir is not None and rows:
-        for b in range(keep):
-            write_tracker_files(tr[b], group * B + b, os.path.join(out_dir, "models"), out_dir)
-    elif out_dir is not None:
-        write_tracker_files(tr, group, os.path.join(out_dir, "models"), out_dir)
-    r = dict(r)
-    r["tracker"] = tr
-    return r
+            dump_group(st, imgs1, r, i, out_dir, group, keep, IMG_NAME, W_NAME, loss_txt=True)
+    return finish_group(st, r, imgs1.shape[0], out_dir, group, keep)
 
 
 def build_models_big_v2(config=None, img_size=256, start_features=64, compute_dtype="bf16", device="cuda", seed=0, attention=True):
@@ -541,22 +437,11 @@ def read_labels(spec, n_images, num_classes, default):
     return ids
 
 
-def rows_plan(n_images, batch_size, labels):
-    """The groups of the rows form: (first image number, rows kept, image number of every row, label of every row) - a short last
-    group repeats its last image and label."""
-    plan = []
-    for first, keep in group_plan(n_images, batch_size):
-        idx = padded_rows(first, batch_size, n_images)
-        plan.append((first, keep, idx, [labels[i] for i in idx]))
-    return plan
-
-
 def main(argv=None):
     args = parse_args(argv)
     if args.deterministic:
         ops.set_deterministic(True)
     from .biggan_generator import BigGANConfig
-    from .infer import save_image_grid
     dev = "cuda"
     config = BigGANConfig.from_json_file(args.config_dir) if args.config_dir else None
     G, E, LP, vgg = build_models_big_v2(config, args.img_size, args.start_features, args.compute_dtype, device=dev, seed=args.seed,
@@ -573,40 +458,16 @@ def main(argv=None):
     for sub in ("", "imgs", "models", "summaries"):
         os.makedirs(os.path.join(out, sub), exist_ok=True)
     imgs = _load_imgs(args.img_dir, args.img_size, dev)
-    bs = args.batch_size
+    kw = dict(vgg16=vgg, attention=args.attention, label=args.label, lr=args.lr, beta_1=args.beta_1, truncation=args.truncation,
+              iterations=args.iterations)
+    labels = None
     if args.independent:
-        n = imgs.shape[0]
-        labels = read_labels(args.labels, n, G.config.num_classes, args.label)
-        st = BigEmbedRowsStep(G, E, LP, vgg16=vgg, attention=args.attention, label=args.label, lr=args.lr, beta_1=args.beta_1,
-                              truncation=args.truncation, iterations=args.iterations)
-        w_all, img_all = [], []
-        for g, (first, keep, idx, lab) in enumerate(rows_plan(n, bs, labels)):
-            r = invert_big(st, imgs[idx].contiguous(), args.iterations, save_every=args.save_every, out_dir=out, group=g, labels=lab, keep=keep)
-            vals = torch.stack((r["loss_msiv"], r["w_norm"])).cpu()
-            for b in range(keep):
-                print("image %d (label %d): loss_msiv %.5f  w_norm %.4f  events %d" % (first + b, lab[b], float(vals[0, b]), float(vals[1, b]),
-                                                                                     len(r["tracker"][b]["events"])))
-                w_all.append(r["w1"][b].clone().cpu())
-                img_all.append(r["imgs2"][b].clone().cpu())
-            save_image_grid(r["imgs2"][:keep], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
-        if w_all:
-            torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (n - 1)))
-            torch.save(torch.stack(img_all, dim=0), os.path.join(out, "models", "img_all_%d.pt" % (n - 1)))
-        return st
-    st = BigEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", vgg16=vgg, attention=args.attention, label=args.label, lr=args.lr,
-                      beta_1=args.beta_1, truncation=args.truncation, iterations=args.iterations)
-    ngroups = imgs.shape[0] // bs
-    w_all, img_all = [], []
-    for g in range(ngroups):
-        imgs1 = imgs[g * bs:(g + 1) * bs].contiguous()
-        r = invert_big(st, imgs1, args.iterations, save_every=args.save_every, out_dir=out, group=g)
-        print("group %d: loss_msiv %.5f  w_norm %.4f  events %d" % (g, float(r["loss_msiv"]), float(r["w_norm"]), len(r["tracker"]["events"])))
-        save_image_grid(r["imgs2"], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
-        w_all.append(r["w1"][0].clone().cpu())
-        img_all.append(r["imgs2"][0].clone().cpu())
-    if w_all:
-        torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (ngroups - 1)))
-        torch.save(torch.stack(img_all, dim=0), os.path.join(out, "models", "img_all_%d.pt" % (ngroups - 1)))
+        labels = read_labels(args.labels, imgs.shape[0], G.config.num_classes, args.label)
+        st = BigEmbedRowsStep(G, E, LP, **kw)
+    else:
+        st = BigEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", **kw)
+    invert_folder(lambda imgs1, **gk: invert_big(st, imgs1, args.iterations, save_every=args.save_every, out_dir=out, **gk),
+                  imgs, args.batch_size, args.independent, out, labels=labels, save_imgs=True)
     return st
 
 
