@@ -146,6 +146,8 @@ SIGNATURES = {
     "dge_upconv_supported": [_I, _I, _I],
     "dge_pack_upconv_weight": [_P, _P, _I, _I, _F, _I, _P],
     "dge_upconv_fir": [_P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P],
+    "dge_up_dgrad_stream_supported": [_I, _I, _I, _I, _I, _I],
+    "dge_up_dgrad_stream": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "dge_cbn_affine": [_P, _P, _I, _P, _P, _F, _P, _P, _I, _I, _P],
     "dge_slice_up": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "dge_attention": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

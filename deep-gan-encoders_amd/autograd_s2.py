@@ -172,7 +172,7 @@ def synthesis_backward(mod, wp, saved, g_image):
                 g_img = ops.up2_bwd(g_img)
         st = ops.SlotStats(B, L.in_c, dev) if fused else ops.zeros((B, L.in_c, 2), dev)
         prep, P_next = None, None
-        if fused and i >= 1 and s2_conv.dgrad_takes_prep(L):
+        if fused and i >= 1 and s2_conv.dgrad_takes_prep(L, B, dt):
             Lp = getattr(mod, f"layer{i - 1}")
             P_next = ops.SlotStats(B, L.in_c, dev)
             prep = dict(gain=Lp.gain, noise=layers[i - 1]["noise"], ns=Lp.noise_strength.detach().reshape(1), stats=P_next)

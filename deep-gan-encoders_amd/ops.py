@@ -1363,6 +1363,55 @@ def upconv_fir(x, w_packed, cout, in_scale=None, out_scale=None, bias=None, bias
     return y
 
 
+# ------------------------------------------------------------------ data gradient of the narrow up layer as one stream
+def up_dgrad_stream_supported(B, Hin, Win, cin, cout, dtype):
+    """True when the data gradient of an up layer cin -> cout on the Hin x Win input grid runs on csrc/upconv_stream_bwd.hip:
+    bf16, 64 -> 32, not in deterministic mode (its sums leave by atomics)."""
+    return (not is_deterministic()) and bool(lib().dge_up_dgrad_stream_supported(int(B), int(Hin), int(Win), int(cin), int(cout), int(dtype)))
+
+
+def pack_up_dgrad_stream(w, dtype=BF16, scale=1.0):
+    """w: [Cout,Cin,3,3] f32 (the forward layer's parameter) -> [9 (ky,kx), Cin, Cout] bf16, element [3ky+kx][i][o] = scale *
+    w[o][i][2-ky][2-kx]: tap (ky, kx) of the transposed conv's adjoint on the t grid, g_x[m,n] = sum W[ky,kx] g_t[2m+ky, 2n+kx]."""
+    if dtype != BF16:
+        raise DgeError("pack_up_dgrad_stream: bf16 only")
+    cout, cin = w.shape[0], w.shape[1]
+    return (w.detach().float() * float(scale)).flip(2, 3).permute(2, 3, 1, 0).reshape(9, cin, cout).to(torch.bfloat16).contiguous()
+
+
+def up_dgrad_stream(g_z, w_packed, d_in, out_scale, addend, stats, dot_src, prep=None):
+    """g_z [B,2H,2W,Cout] (gradient w.r.t. the up layer's pre-activation; d_in [B,Cout] or None still to be applied) -> [B,H,W,Cin]:
+    FIR^T, transposed-conv adjoint and the data-gradient epilogue of conv2d(in_s2d=True, out_scale=, addend=, stats=, dot_src=,
+    prep=) in one streaming launch (dge_up_dgrad_stream).  stats: SlotStats(B, Cin) or a zeroed [B,Cin,2] tensor."""
+    B, FH, FW, cout = g_z.shape
+    H, W = FH // 2, FW // 2
+    _, cin, _ = w_packed.shape
+    dt = dtype_of(g_z)
+    if dot_src is None or stats is None:
+        raise DgeError("up_dgrad_stream: needs stats and dot_src")
+    if not up_dgrad_stream_supported(B, H, W, cin, cout, dt):
+        raise DgeError(f"up_dgrad_stream: unsupported launch {cin} <- {cout} channels, dtype {dt}")
+    out = torch.empty((B, H, W, cin), dtype=g_z.dtype, device=g_z.device)
+    nslot = _stats_slots(B, H, W, 32)
+    lazy = isinstance(stats, SlotStats)
+    partial = stats.alloc(nslot) if lazy else (zeros((nslot,) + tuple(stats.shape), g_z.device) if nslot > 1 else stats)
+    pn = pns = pst = None
+    pgain, pbs = 1.0, 0
+    if prep is not None:
+        pn = prep.get("noise")
+        pns = prep.get("ns") if pn is not None else None
+        pbs = 0 if (pn is None or pn.shape[0] == 1) else H * W
+        pgain, pst = float(prep["gain"]), prep["stats"].alloc(nslot)
+    _launch(lib().dge_up_dgrad_stream,
+            (_p(g_z), _p(w_packed), _p(out), _f32(d_in), _f32(out_scale), _p(addend), _p(dot_src), _f32(partial), nslot,
+             0 if prep is None else 1, pgain, _f32(pn), pbs, _f32(pns), _f32(pst), B, H, W, cin, cout, dt, _stream()),
+            "dge_up_dgrad_stream", 9.0 * cin * cout * H * W * B, (B, H, W, 4 * cout, cin, 3, False, True),
+            (g_z, out, addend, dot_src, w_packed))
+    if not lazy and partial is not stats:
+        check(lib().dge_sum_slots(_p(partial), _p(stats), nslot, stats.numel(), 1, _stream()), "dge_sum_slots")
+    return out
+
+
 # ------------------------------------------------------------------ inversion loop (embedding_v2.py)
 TRACK_ARM_AT, TRACK_ARM_AFTER = 0, 1        # include/dge_hip.h DGE_TRACK_ARM_*
 

@@ -10,6 +10,7 @@ UP_PP = os.environ.get("DGE_UP_PP", "1") != "0"      # round 6: the default for 
 UP_FOLDED = os.environ.get("DGE_UP_FOLDED") == "1"
 T2D = not os.environ.get("DGE_NO_T2D")
 PP_DG = not os.environ.get("DGE_NO_PP_DG")
+UP_DG_STREAM = not os.environ.get("DGE_NO_UP_DG_STREAM")      # the 64 <- 32 up layer's data gradient as one streaming launch (csrc/upconv_stream_bwd.hip)
 
 
 # ------------------------------------------------------------------ forward
@@ -100,10 +101,24 @@ def _dgrad_weight_pp(L, d, t2d=False):
     return c if t2d else ops.pack_conv_pp_rows(c, L.in_c, in_scale=d, in_period=L.out_c)
 
 
-def dgrad_takes_prep(L):
+def _up_stream_dgrad(L, B, dtype, fused):
+    """the data gradient of this up layer runs on the streaming adjoint kernel (ops.up_dgrad_stream: 64 <- 32 channels, bf16; fused
+    mode only - its sums leave by atomics)"""
+    return UP_DG_STREAM and fused and L.up and L.ksize == 3 and ops.up_dgrad_stream_supported(B, L.res // 2, L.res // 2, L.in_c, L.out_c, dtype)
+
+
+def _dgrad_weight_stream(L, dtype):
+    c = lookup(L._cache, ("dgs", dtype), L.weight)
+    return c if c is not None else store(L._cache, ("dgs", dtype), L.weight, ops.pack_up_dgrad_stream(L.weight, dtype, L.wscale))
+
+
+def dgrad_takes_prep(L, B=None, dtype=None):
     """True when the data-gradient launch of L may carry the tail backward of the layer below in its epilogue (`prep`)
-    (the space-to-depth data gradient of a narrow up layer - layer 15: 64 -> 32 channels - loses more in its 64-wide tile
-     than the separate pass costs: measured 890 vs 747 us; tools/perf_prep.py)"""
+    (the space-to-depth data gradient of a narrow up layer - layer 15: 64 -> 32 channels - loses more in its 64-wide conv_igemm tile
+     than the separate pass costs: measured 890 vs 747 us; tools/perf_prep.py.  The streaming adjoint carries it: the stored
+     activation of the layer below is in its registers for the dot products anyway.)"""
+    if B is not None and L.up and _up_stream_dgrad(L, B, dtype, not ops.is_deterministic()):
+        return True
     return _up_phase_form(L) or not (L.up and L.in_c < 128)
 
 
@@ -111,6 +126,11 @@ def dgrad(L, g_y, d_in, dt, fused, prep=None, **epilogue):
     """g_xprev [B,Hin,Win,in_c] of layer L from g_y; d_in: the demodulation factor still to be applied to g_y, or None.
     `prep` and `epilogue` (out_scale, addend, stats, dot_src) go to the launch as they are (ops.conv2d / ops.conv_pp)."""
     B, hg = g_y.shape[0], (L.res // 2 if L.up else L.res)
+    if L.up and _up_stream_dgrad(L, B, dt, fused) and epilogue.get("dot_src") is not None and epilogue.get("stats") is not None \
+            and set(epilogue) <= {"out_scale", "addend", "stats", "dot_src"}:
+        # narrow up layer (64 <- 32): FIR^T, the 9-tap adjoint on the t grid and the epilogue in one streaming pass
+        return ops.up_dgrad_stream(g_y, _dgrad_weight_stream(L, dt), d_in, epilogue.get("out_scale"), epilogue.get("addend"),
+                                   epilogue.get("stats"), epilogue["dot_src"], prep=prep)
     t2d = _up_phase_form(L)
     if fused and d_in is not None and not t2d and _pp_dgrad(L, B, hg, dt):
         # MFMA-bound launches on the ping-pong kernel (csrc/conv_pp.hip): the demodulation factor is folded into a per-sample

@@ -523,6 +523,18 @@ int dge_upconv_fir(const void* x, const void* w_packed, void* y, const float* in
                    const float* noise, int noise_bstride, const float* noise_w, int noise_w_stride, const float* bias,
                    float bias_scale, float gain, int act, int B, int H, int W, int Cin, int Cout, int dtype, dge_stream_t stream);
 
+/* ---- Streaming data gradient of the narrow up layer (csrc/upconv_stream_bwd.hip; 64 <- 32 channels, bf16): the adjoint of
+ * dge_upconv_fir in phase form, one pass.  g_z [B,2H,2W,Cout] -> FIR^T (times d_in [B,Cout] or NULL, then ONE bf16 rounding) ->
+ * 9-tap transposed conv on the t grid -> acc [B,H,W,Cin].  Epilogue as dge_conv2d's data-gradient mode: y = acc*out_scale + addend,
+ * stats [slots][B][Cin][2] += (sum acc*dot_src, sum acc); with prep: y = g_z of the layer that produced dot_src, stats += (sum
+ * acc*dot_src, -), prep_stats += (sum g_z*(z - ns*noise), sum g_z)  (dge_conv_desc.prep).  w_packed: [9 (ky,kx)][Cin][Cout] bf16,
+ * w_packed[3ky+kx][i][o] = w[o][i][2-ky][2-kx] * wscale.  Not offered in deterministic mode (the caller keeps dge_conv2d there). */
+int dge_up_dgrad_stream_supported(int B, int H, int W, int Cin, int Cout, int dtype);
+int dge_up_dgrad_stream(const void* g_z, const void* w_packed, void* y, const float* d_in, const float* out_scale,
+                        const void* addend, const void* dot_src, float* stats, int stats_slots, int prep, float prep_gain,
+                        const float* prep_noise, int prep_noise_bstride, const float* prep_ns, float* prep_stats,
+                        int B, int H, int W, int Cin, int Cout, int dtype, dge_stream_t stream);
+
 /* ---- The same up layer as a ping-pong implicit GEMM for the MFMA-bound layers (csrc/up_pp.hip; Cin >= 128: layers 7 / 9 / 11 / 13
  * of the 1024^2 generator).  stylegan2_generator.py:879-896 conv_transpose2d + FIR in the reference's FUSED-modulation form
  * (:858-875): dge_pack_up_pp folds style, demodulation and gain into one weight image per sample,
