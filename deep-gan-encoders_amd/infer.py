@@ -8,12 +8,17 @@
                     from the training loss's pytorch_ssim, which `losses.space_loss` reports);
 * `load_images` / `reconstruct_images` - rec_real_img.py:84-120: image files -> `[N,3,S,S]` batch in [-1,1] (PIL, the script's
                     Resize + ToTensor; `training_utils.imgPath2loader` with `bicubic=True`) -> E -> G, the "invert this image" path;
-* `save_image`    - torchvision.utils.save_image(img*0.5+0.5, path) for a single image batch laid out in one row.
+* `save_image`    - torchvision.utils.save_image(img*0.5+0.5, path) for a single image batch laid out in one row;
+* `quantize_u8` / `image_metrics_rows` - the numbers of comparing-baseline.py:46-87: every image pair on its own, on the 8-bit
+                    images a saved file holds (exact integer sums, f64 metrics; ops.image_metrics_u8);
+* `MetricsTable`  - the per-pair table behind `<out>/metrics.csv` / `metrics.json` of `infer eval`, `rec --metrics` and
+                    `python -m dge_amd.compare`.
 """
 import math
 
 import torch
 
+from . import ops
 from ._lib import lib, check
 from .generators import set_seed
 from .losses import batch_sums
@@ -105,6 +110,129 @@ def ssim_skimage(img1, img2):
     return sums.view(B, Cc).sum(1) / float(Cc * (H - 6) * (W - 6))
 
 
+@torch.no_grad()
+def quantize_u8(img):
+    """img [B,C,H,W] f32 or bf16 in [-1,1] on the GPU -> device uint8 [B,H,W,C]: the bytes `save_image_grid` /
+    torchvision.utils.save_image write for it (PIL's layout), rounded on the device with the host formula's f32 arithmetic."""
+    return ops.quantize_u8(img.detach().contiguous())
+
+
+@torch.no_grad()
+def image_metrics_rows(img1, img2, lpips_model=None, quantize=True):
+    """comparing-baseline.py:67-87 for a batch: every pair (img1[i], img2[i]) measured on its own, on 8-bit images as the script
+    reads them from files (ToTensor()*255).  Inputs: uint8 [B,H,W,3] (decoded files, `quantize_u8` output), or float [B,3,H,W] in
+    [-1,1], which is quantised first - the numbers of the saved files.  Returns a dict of [B] float64 device tensors psnr, ssim,
+    mse (on [0,255]), cosine (on [-1,1]), `isums` [B,5] int64 (sum a, sum b, sum a^2, sum b^2, sum ab) and, with a model, `lpips`
+    [B] f32 on q/255*2-1.  PSNR is +inf for identical images (skimage).  One launch, no host sync.  The batch-coupled float
+    statistics stay `image_metrics`; quantize=False on floats is refused."""
+    q = []
+    for t in (img1, img2):
+        t = t.detach()
+        if t.dtype == torch.uint8:
+            q.append(t)
+        elif t.is_floating_point():
+            if not quantize:
+                raise ValueError("image_metrics_rows measures 8-bit images: float inputs are quantised (quantize=True); the float, "
+                                 "batch-coupled form is image_metrics")
+            if t.dim() != 4 or t.shape[1] != 3:
+                raise ValueError(f"image_metrics_rows: float images are [B,3,H,W] in [-1,1], got {tuple(t.shape)}")
+            q.append(quantize_u8(t))
+        else:
+            raise ValueError(f"image_metrics_rows: uint8 [B,H,W,3] or float [B,3,H,W] images, got {t.dtype}")
+    a, b = q
+    if a.dim() != 4 or a.shape[3] != 3 or a.shape != b.shape:
+        raise ValueError(f"image_metrics_rows: two image batches of one shape [B,H,W,3], got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape[1] < 7 or a.shape[2] < 7:
+        raise ValueError("win_size exceeds image extent (skimage raises the same for images smaller than 7x7)")
+    isums, _, m = ops.image_metrics_u8(a, b)
+    out = dict(psnr=m[:, 0], ssim=m[:, 1], mse=m[:, 2], cosine=m[:, 3], isums=isums)
+    if lpips_model is not None:
+        fa, fb = (t.permute(0, 3, 1, 2).float().div(255.0).mul(2.0).sub(1.0).contiguous() for t in (a, b))
+        out["lpips"], _ = lpips_model.value_and_grad(fa, fb, need_grad=False, per_sample=True)
+    return out
+
+
+METRIC_COLUMNS = ("psnr", "ssim", "mse", "lpips", "cosine")           # the order of comparing-baseline.py's progress line
+
+
+class MetricsTable:
+    """Per-pair metrics of a run, kept on the device until `write`: `add` takes the dict of `image_metrics_rows` and the two file
+    names of every pair and makes no host read; `write` reads once and writes <out>/metrics.csv (one row per pair: index, file1,
+    file2 and the five metrics, floats in repr form, the lpips column empty without a model) and <out>/metrics.json (the means
+    the script prints at its end, `count`, `identical_pairs`; `lpips: null` without a model).  A pair with mse == 0 puts inf into
+    the PSNR mean, as in the script, and is counted in `identical_pairs`."""
+
+    def __init__(self):
+        self.names, self.rows, self.lpips = [], [], []
+
+    def add(self, m, names1, names2):
+        self.names += list(zip(names1, names2))
+        self.rows.append(torch.stack((m["psnr"], m["ssim"], m["mse"], m["cosine"]), dim=1))
+        if "lpips" in m:
+            self.lpips.append(m["lpips"].double())
+
+    def values(self):
+        """[(psnr, ssim, mse, lpips | None, cosine)] as Python floats: the one host read"""
+        if not self.rows:
+            return []
+        rows = torch.cat(self.rows)
+        if self.lpips:
+            rows = torch.cat((rows, torch.cat(self.lpips).unsqueeze(1)), dim=1)
+        rows = rows.cpu().tolist()
+        return [(r[0], r[1], r[2], r[4] if len(r) > 4 else None, r[3]) for r in rows]
+
+    def write(self, out_dir, progress=None):
+        """`progress`: a callable taking the script's running-mean line of every pair (comparing-baseline.py:84-85)."""
+        import json
+        import os
+        vals = self.values()
+        os.makedirs(out_dir, exist_ok=True)
+        sums = [0.0] * 5
+        lines = ["index,file1,file2," + ",".join(METRIC_COLUMNS)]
+        for i, ((n1, n2), v) in enumerate(zip(self.names, vals)):
+            lines.append("%d,%s,%s,%s" % (i, n1, n2, ",".join("" if x is None else repr(x) for x in v)))
+            sums = [s + (0.0 if x is None else x) for s, x in zip(sums, v)]
+            if progress is not None:
+                progress("img_num:%d--psnr:%f--ssim:%f--mse_value:%f--lpips_value:%f--cosine_value:%f" % ((i + 1,) + tuple(s / (i + 1) for s in sums)))
+        n = len(vals)
+        summary = dict(count=n, identical_pairs=sum(1 for v in vals if v[2] == 0.0))
+        for k, name in enumerate(METRIC_COLUMNS):
+            summary[name] = None if (n == 0 or vals[0][k] is None) else sums[k] / n
+        paths = os.path.join(out_dir, "metrics.csv"), os.path.join(out_dir, "metrics.json")
+        with open(paths[0], "w") as f:
+            f.write("\n".join(lines) + "\n")
+        with open(paths[1], "w") as f:
+            json.dump(summary, f, indent=1)                       # an infinite PSNR mean is written as Infinity (Python's json)
+            f.write("\n")
+        return list(paths)
+
+
+def add_lpips_args(parser):
+    parser.add_argument("--vgg_weights", default=None, help="torchvision vgg16 checkpoint (features.*) or an lpips.LPIPS state_dict")
+    parser.add_argument("--lpips_weights", default=None, help="the lpips package's weights/v0.1/vgg.pth (lin{k}.model.1.weight)")
+    parser.add_argument("--allow_standin_lpips", action="store_true", help="report LPIPS on seeded stand-in weights (NOT the published metric)")
+    return parser
+
+
+def lpips_from_args(args, device="cuda", compute_dtype="bf16"):
+    """The LPIPS model of a metrics run, or None when none of --vgg_weights / --lpips_weights / --allow_standin_lpips is given
+    (the lpips column then stays empty)."""
+    from .lpips import LPIPS
+    from .models import load_lpips_weights
+    if not (args.vgg_weights or args.lpips_weights or args.allow_standin_lpips):
+        return None
+    torch.manual_seed(0)
+    LP = LPIPS(compute_dtype=compute_dtype).to(device)
+    LP.eval()
+    return load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
+
+
+def save_u8(q, path):
+    """q [H,W,3] uint8 (one image of `quantize_u8`) -> PNG, the bytes as they are."""
+    from PIL import Image
+    Image.fromarray(q.cpu().numpy()).save(path)
+
+
 def save_image(img, path):
     """img [B,3,H,W] in [-1,1] -> PNG (samples side by side)."""
     from PIL import Image
@@ -143,21 +271,33 @@ def main(argv=None):
     * `rec`   - rec_real_img.py:84-127: every image of --img_dir -> E -> G, writes <out>/real/%05d_realimg.png and
                 <out>/rec/%05d_mtv_rec.png;
     * `synth` - synthesized_IMG.py:97-145: for iteration in 30000 .. 30000 + --iterations: set_seed(iteration), z -> G -> E -> G,
-                writes <out>/id<flag>_%05d.png (nrow 10: originals then reconstructions)."""
+                writes <out>/id<flag>_%05d.png (nrow 10: originals then reconstructions);
+    * `eval`  - the `synth` loop measured instead of drawn: imgs1 and imgs2 of every iteration are quantised to the 8-bit
+                images a file would hold and every pair's PSNR / SSIM / MSE / cosine (LPIPS with the weight flags) is kept on
+                the device (`image_metrics_rows`); one host read at the end writes <out>/metrics.csv and metrics.json
+                (`MetricsTable`).  --dump_dir D also writes the quantised bytes as D/real/%05d.png and D/rec/%05d.png, on
+                which `python -m dge_amd.compare` reproduces the table.
+    `rec --metrics` adds the same two files for the real images against their reconstructions (the images without the
+    2-pixel frame of the PNGs it writes)."""
     import argparse
     import os
     parser = argparse.ArgumentParser(prog="dge_amd.infer", description=main.__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    parser.add_argument("command", choices=("infer", "rec", "synth"))
+    parser.add_argument("command", choices=("infer", "rec", "synth", "eval"))
     add_model_args(parser)
     parser.add_argument("--batch_size", type=int, default=5)
     parser.add_argument("--seed", type=int, default=4)
     parser.add_argument("--iterations", type=int, default=1)
     parser.add_argument("--img_dir", default=None, help="rec: directory of images (sorted by name)")
     parser.add_argument("--out", default="./result")
+    parser.add_argument("--metrics", action="store_true", help="rec: also write <out>/metrics.csv and metrics.json")
+    parser.add_argument("--dump_dir", default=None, help="eval: also write every pair as <dump_dir>/real/%%05d.png and rec/%%05d.png")
+    add_lpips_args(parser)
     args = parser.parse_args(argv)
     os.makedirs(args.out, exist_ok=True)
     step = _step_from_args(args)
     written = []
+    table = MetricsTable() if args.command == "eval" or (args.command == "rec" and args.metrics) else None
+    LP = lpips_from_args(args, step.dev, args.compute_dtype) if table is not None else None
     if args.command == "infer":
         r = reconstruct(step, iteration=args.seed)
         path = os.path.join(args.out, "v2ep%d.png" % args.seed)
@@ -180,6 +320,23 @@ def main(argv=None):
             save_image_grid(imgs[i:i + 1], a, nrow=1)
             save_image_grid(rec[i:i + 1], b, nrow=1)
             written += [a, b]
+        if table is not None:
+            table.add(image_metrics_rows(imgs, rec, LP), [os.path.basename(w) for w in written[0::2]], [os.path.basename(w) for w in written[1::2]])
+    elif args.command == "eval":
+        B = args.batch_size
+        if args.dump_dir:
+            os.makedirs(os.path.join(args.dump_dir, "real"), exist_ok=True)
+            os.makedirs(os.path.join(args.dump_dir, "rec"), exist_ok=True)
+        for iteration in range(30000, 30000 + args.iterations):
+            r = reconstruct(step, iteration=iteration % 30000 if step.gen.conditional else iteration)
+            q1, q2 = quantize_u8(r["imgs1"]), quantize_u8(r["imgs2"])
+            names = ["%s.png" % str((iteration - 30000) * B + j).rjust(5, "0") for j in range(q1.shape[0])]
+            table.add(image_metrics_rows(q1, q2, LP), names, names)
+            if args.dump_dir:
+                for j, n in enumerate(names):
+                    for sub, q in (("real", q1), ("rec", q2)):
+                        save_u8(q[j], os.path.join(args.dump_dir, sub, n))
+                        written.append(os.path.join(args.dump_dir, sub, n))
     else:
         for iteration in range(30000, 30000 + args.iterations):
             r = reconstruct(step, iteration=iteration % 30000 if step.gen.conditional else iteration)
@@ -187,6 +344,8 @@ def main(argv=None):
             path = os.path.join(args.out, "id%s_%s.png" % (flag, str(iteration - 30000).rjust(5, "0")))
             save_image_grid(torch.cat((r["imgs1"], r["imgs2"])), path, nrow=10)
             written.append(path)
+    if table is not None:
+        written += table.write(args.out)
     for w in written:
         print(w)
     return written

@@ -1518,3 +1518,52 @@ def embed_track_rows(loss, norm, w, istate, fstate, best_loss_w, best_norm_w, ev
                                      int(arm_iter), float(loss_hyst), float(norm_hyst), _stream()), "dge_embed_track_rows")
     log_kernel()
 
+
+
+# ---- evaluation metrics on 8-bit images (include/dge_hip.h dge_quantize_u8 / dge_image_metrics_u8)
+def quantize_u8(x, out=None):
+    """x [B,C,H,W] f32 or bf16 in [-1,1] -> [B,H,W,C] uint8: the bytes save_image writes (x*0.5+0.5, clamp, *255+0.5, truncate)."""
+    if x.dim() != 4:
+        raise DgeError("quantize_u8: expected [B,C,H,W]")
+    B, Cc, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, H, W, Cc), dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, H, W, Cc):
+        raise DgeError("quantize_u8: out must be uint8 [B,H,W,C]")
+    check(lib().dge_quantize_u8(_p(x), dtype_of(x), _p(out), B, Cc, H, W, _stream()), "dge_quantize_u8")
+    log_kernel()
+    return out
+
+
+def image_metrics_u8_work_bytes(B, H, W):
+    """Bytes of the `work` buffer of image_metrics_u8 (raises for the sizes the launch refuses)."""
+    n = lib().dge_image_metrics_u8_work_bytes(int(B), int(H), int(W))
+    if n < 0:
+        check(n, "dge_image_metrics_u8_work_bytes")
+    return n
+
+
+def image_metrics_u8(a, b, work=None, isums=None, ssim=None, out=None):
+    """a, b [B,H,W,3] uint8 contiguous -> (isums [B,5] int64, ssim [B] f64, out [B,4] f64 = psnr, ssim, mse, cosine), every image
+    pair on its own.  No host sync; the buffers may be passed in (a captured graph reuses them), none has to be zeroed."""
+    for t in (a, b):
+        if t.dtype != torch.uint8:
+            raise DgeError(f"image_metrics_u8: expected uint8 images, got {t.dtype}")
+    if a.dim() != 4 or a.shape[3] != 3 or a.shape != b.shape:
+        raise DgeError(f"image_metrics_u8: expected two [B,H,W,3] images of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, H, W, _ = a.shape
+    nbytes = image_metrics_u8_work_bytes(B, H, W)
+    dev = a.device
+    if work is None:
+        work = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    elif work.numel() * work.element_size() < nbytes:
+        raise DgeError(f"image_metrics_u8: work holds {work.numel() * work.element_size()} bytes, {nbytes} needed")
+    isums = torch.empty((B, 5), dtype=torch.int64, device=dev) if isums is None else isums
+    ssim = torch.empty(B, dtype=torch.float64, device=dev) if ssim is None else ssim
+    out = torch.empty((B, 4), dtype=torch.float64, device=dev) if out is None else out
+    if isums.dtype != torch.int64 or ssim.dtype != torch.float64 or out.dtype != torch.float64 \
+            or isums.numel() != 5 * B or ssim.numel() != B or out.numel() != 4 * B:
+        raise DgeError("image_metrics_u8: isums int64 [B,5], ssim float64 [B], out float64 [B,4]")
+    check(lib().dge_image_metrics_u8(_p(a), _p(b), B, H, W, _p(work), _p(isums), _p(ssim), _p(out), _stream()), "dge_image_metrics_u8")
+    log_kernel()
+    return isums, ssim, out

@@ -718,6 +718,27 @@ int dge_embed_track_rows(const float* loss, const float* norm, const float* w, i
 int dge_mapping_bwd(const float* z, int ldz, const dge_dense_layer* layers, int n, const float* const* acts, const float* g, int L,
                     const float* coefs, float* dz, int lddz, int B, int pixelnorm, float eps, dge_stream_t stream);
 
+/* ---- evaluation metrics on 8-bit images (comparing-baseline.py:21-45, one image pair at a time) ------------------------------ */
+/* x [B,C,H,W] f32 or bf16 (dtype) in [-1,1] -> out [B,H,W,C] uint8 (4-byte aligned), the bytes torchvision.utils.save_image
+ * writes: t = x*0.5 + 0.5, clamp to [0,1], t*255 + 0.5, truncated, as separate round-to-nearest f32 operations (no FMA), so the
+ * bytes equal the host formula on every finite input.  dge_last_kernel: "quantize_u8<f32>" / "quantize_u8<bf16>". */
+int dge_quantize_u8(const void* x, int dtype, unsigned char* out, int B, int C, int H, int W, dge_stream_t stream);
+/* a, b [B,H,W,3] uint8, contiguous.  For every image pair of the batch, computed as if it were alone:
+ *   isums [B][5] int64 = sum a, sum b, sum a^2, sum b^2, sum ab (exact);
+ *   ssim  [B]    f64   = mean of the skimage SSIM map (defaults of compare_ssim as dge_ssim_box7 lists them: 7x7 uniform window,
+ *                        K1 0.01, K2 0.03, cov_norm 49/48, data_range 255, 3-pixel border cropped, channels averaged);
+ *   out   [B][4] f64   = psnr, ssim, mse, cosine: mse = (sum a^2 - 2 sum ab + sum b^2)/N on the [0,255] scale, N = 3HW;
+ *                        psnr = 10 log10(255^2/mse), +inf at mse == 0; cosine of x/255*2 - 1 from the integer sums.
+ * One pass over the images: a workgroup loads a tile and its 6-pixel halo once, forms the five 7x7 window sums as int32
+ * (horizontal 7-sums through LDS, then vertical) and the map value in f64 from the integer variance numerators; its partials go
+ * to a slot of its own in `work` (dge_image_metrics_u8_work_bytes(B,H,W) bytes, 8-byte aligned, every slot WRITTEN) and a
+ * finaliser adds a row's slots in a fixed order.  No atomics, no pre-zeroed buffer, no host sync: the same bits in both
+ * reduction modes and from run to run.  Refused: H or W below 7 (skimage refuses them too) or above 65536 (keeps every integer
+ * formed below 2^52), B above 65535, a workspace of 2 GiB or more (work_bytes returns -1).  dge_last_kernel: "image_metrics_u8". */
+int dge_image_metrics_u8_work_bytes(int B, int H, int W);
+int dge_image_metrics_u8(const unsigned char* a, const unsigned char* b, int B, int H, int W, void* work, long long* isums,
+                         double* ssim, double* out, dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
