@@ -134,6 +134,7 @@ SIGNATURES = {
     "dge_nearest_up2_bwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "dge_pixelnorm_nhwc": [_P, _P, C.c_long, _I, _F, _I, _P],
     "dge_pixelnorm_nhwc_bwd": [_P, _P, _P, C.c_long, _I, _F, _I, _P],
+    "dge_pixelnorm_act_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P],
     "dge_affine_relu_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "dge_slice_up_bwd": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "dge_softmax_rows": [_P, C.c_long, _I, _I, _P],

@@ -71,8 +71,19 @@ def pg_encoder_forward(E, img, noises=None, save=False):
     return xo, z, saved
 
 
-def pg_encoder_backward(E, saved, g_z):
-    """Gradients for E.parameters() in registration order."""
+FUSE_IMG_GRAD = True          # block 0's last stage with an image gradient: one launch (False: the composed passes, for timing)
+
+
+def pg_encoder_backward(E, saved, g_z, need_img=False, params=True):
+    """-> the gradients for E.parameters() in registration order; with need_img the pair (those, g_img [B,3,R,R] f32).
+    need_img: the input image carries a gradient (embedding_v2_pggan: E(imgs2) of a generated image).  Block 0's last stage - the
+    instance-norm backward on the FromRGB output plus the residual branch's gradient `extra` at full resolution, FromRGB's leaky-relu
+    and data gradient and (trained encoder) its parameter reductions - is then one ops.in_bwd_fromrgb_img launch, which computes
+    the instance-norm coefficients itself; where it refuses the channel count: in_bwd -> fromrgb_dgrad (-> fromrgb_bwd).
+    params=False (frozen encoder: the z inversion mode): the data gradient alone.  No weight gradient, bias / noise-weight
+    reduction, instance_norm_3 gamma / beta sum, conv_3 bias sum, FromRGB reduction or head weight gradient is launched, and every
+    parameter gradient is None.
+    The default call issues the launches of e_align --mtype 3's backward, in their order."""
     if saved is None:
         raise RuntimeError("E_PG forward ran without saved activations")
     cache = pack_cache(E)
@@ -81,54 +92,77 @@ def pg_encoder_backward(E, saved, g_z):
     R = saved["img"].shape[2]
     dt = ops.dtype_of(saved["x0"])
     grads = {}
-    g_flat = linear_backward(E.new_final, g_z.float().contiguous(), saved["flat"], grads, "new_final")     # head: z = flat @ W^T + b
+    g_flat = linear_backward(E.new_final, g_z.float().contiguous(), saved["flat"], grads, "new_final", params)     # head: z = flat @ W^T + b
     L = len(saved["blocks"])
     C_last = E.decode_block[L - 1].inputs
     g_out = ops.nchw_to_nhwc(g_flat.view(B, C_last, R >> (L - 1), R >> (L - 1)), B, dt)
+    g_img = fr = None
     for j, blk, rec, pre, Cc, C2, H, N in blocks(E, R, saved):
         x, x1 = rec["x"], rec["x1"]
-        red1 = ops.zeros((Cc, 2), dev)
+        red1 = ops.zeros((Cc, 2), dev) if params else None
         if blk.has_second_conv:
             has3 = Cc != C2
             # s = pre2 + res ; a = lrelu(s) ; out = avg_pool(a)
-            red2 = ops.zeros((C2, 2), dev)
+            red2 = ops.zeros((C2, 2), dev) if params else None
             g_s = ops.act_bwd(g_out, rec["a"], rec["n2"], pool=True, scale=0.25, red=red2)
-            red_param_grads(grads, pre, 2, red2)
-            g_y2, dots2 = conv_bwd(cache, grads, pre + "conv_2", blk.conv_2, g_s, x1, dt, H, rec["sc2"], rec["sh2"])
+            if params:
+                red_param_grads(grads, pre, 2, red2)
+            g_y2, dots2 = conv_bwd(cache, grads, pre + "conv_2", blk.conv_2, g_s, x1, dt, H, rec["sc2"], rec["sh2"], params)
             coef2 = ops.in_bwd_coef(dots2, None, rec["musig2"], rec["sc2"], rec["sh2"], N)
             g_pre1 = ops.in_bwd(g_y2, x1, coef2, noise=rec["n1"], act=True, red=red1)
             if has3:
                 gam, bta = blk.instance_norm_3.weight.detach(), blk.instance_norm_3.bias.detach()
                 style = torch.cat([gam - 1.0, bta]).unsqueeze(0).expand(B, -1).contiguous()
                 coef3, gstyle = ops.sg1_in_bwd_coef(ops.dot_stats(g_s, rec["r3"]), rec["sc3"], rec["sh3"], style, N)
-                gsum = ops._sum_over_batch(gstyle)
-                grads[pre + "instance_norm_3.weight"], grads[pre + "instance_norm_3.bias"] = gsum[:C2], gsum[C2:]
+                if params:
+                    gsum = ops._sum_over_batch(gstyle)
+                    grads[pre + "instance_norm_3.weight"], grads[pre + "instance_norm_3.bias"] = gsum[:C2], gsum[C2:]
                 g_r3 = ops.in_bwd(g_s, rec["r3"], coef3)
-                grads[pre + "conv_3.bias"] = ops.chan_sum(g_r3)
-                extra, _ = conv_bwd(cache, grads, pre + "conv_3", blk.conv_3, g_r3, x, dt, None, dots=False)
+                if params:
+                    grads[pre + "conv_3.bias"] = ops.chan_sum(g_r3)
+                extra, _ = conv_bwd(cache, grads, pre + "conv_3", blk.conv_3, g_r3, x, dt, None, params=params, dots=False)
             else:
                 extra = g_s
         else:
             g_pre1 = ops.act_bwd(g_out, x1, rec["n1"], pool=False, scale=1.0, red=red1)
             extra = None
-        red_param_grads(grads, pre, 1, red1)
-        g_y1, dots1 = conv_bwd(cache, grads, pre + "conv_1", blk.conv_1, g_pre1, x, dt, H, rec["sc1"], rec["sh1"])
-        coef1 = ops.in_bwd_coef(dots1, None, rec["musig1"], rec["sc1"], rec["sh1"], N)
-        g_out = ops.in_bwd(g_y1, x, coef1, extra=extra, extra_pool=False, extra_scale=1.0)
-    fromrgb_param_grads(E, saved, g_out, grads)
-    return grads_in_order(E, grads)
+        if params:
+            red_param_grads(grads, pre, 1, red1)
+        g_y1, dots1 = conv_bwd(cache, grads, pre + "conv_1", blk.conv_1, g_pre1, x, dt, H, rec["sc1"], rec["sh1"], params)
+        if j == 0 and need_img and FUSE_IMG_GRAD and ops.in_bwd_fromrgb_img_supported(Cc, dt):
+            # x is the FromRGB output and the image carries a gradient: the gradient w.r.t. x is neither stored nor rounded
+            g_img, fr = ops.in_bwd_fromrgb_img(g_y1, x, (dots1, None, rec["musig1"], rec["sc1"], rec["sh1"], N),
+                                               E.FromRGB.from_rgb.weight.detach(), saved["img"].float() if params else None,
+                                               extra=extra, extra_pool=False, extra_scale=1.0)
+            g_out = None
+        else:
+            coef1 = ops.in_bwd_coef(dots1, None, rec["musig1"], rec["sc1"], rec["sh1"], N)
+            g_out = ops.in_bwd(g_y1, x, coef1, extra=extra, extra_pool=False, extra_scale=1.0)
+    if need_img and g_img is None:         # the composed passes: g_out is the stored gradient w.r.t. the FromRGB output
+        g_img = ops.fromrgb_dgrad(g_out, saved["x0"], E.FromRGB.from_rgb.weight.detach())
+    if params:
+        if fr is None:
+            fromrgb_param_grads(E, saved, g_out, grads)
+        else:
+            grads["FromRGB.from_rgb.weight"] = fr[:3].t().reshape(E.startf, 3, 1, 1)
+            grads["FromRGB.from_rgb.bias"] = fr[3]
+    out = grads_in_order(E, grads)
+    return (out, g_img) if need_img else out
 
 
 class PGEncoderFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, E, img, noises, *params):
-        if ctx.needs_input_grad[1]:
-            raise ops.DgeError("E_PG: the gradient w.r.t. the input image is not implemented on the HIP path; detach the image")
-        need = any(ctx.needs_input_grad[3:])
-        _, z, saved = pg_encoder_forward(E, img.detach(), noises, save=need)
-        ctx.E, ctx.saved_acts = E, saved
+        need_params = any(ctx.needs_input_grad[3:])
+        need_img = bool(ctx.needs_input_grad[1])
+        _, z, saved = pg_encoder_forward(E, img.detach(), noises, save=need_params or need_img)
+        ctx.E, ctx.saved_acts, ctx.need_img, ctx.need_params = E, saved, need_img, need_params
         return z
 
     @staticmethod
     def backward(ctx, g_z):
-        return (None, None, None) + tuple(pg_encoder_backward(ctx.E, ctx.saved_acts, g_z))
+        out = pg_encoder_backward(ctx.E, ctx.saved_acts, g_z, need_img=ctx.need_img, params=ctx.need_params)
+        grads, g_img = out if ctx.need_img else (out, None)
+        if g_img is not None:
+            g_img = g_img.to(ctx.saved_acts["img"].dtype)
+        return (None, g_img, None) + tuple(grads)

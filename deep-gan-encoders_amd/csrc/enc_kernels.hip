@@ -264,6 +264,65 @@ __global__ __launch_bounds__(256) void pixelnorm_nhwc_bwd_kernel(const T* __rest
     }
 }
 
+// pixel-norm backward fused with its neighbours in the PGGAN generator backward: x is both what the pixel norm read and the output
+// of the previous leaky-relu, so  out = (r*gl - x*(sum_c gl*x)*r^3/C) * lrelu'(x)  is one pass over g and x.
+// UP: g is [B,2H,2W,C] and gl its 2x2 block sum (the adjoint of the nearest x2 upsample), kept in f32 - the composed launches
+// round gl and the pixel-norm gradient to T in between.  act = 0: no activation factor.  p runs over the B*H*W pixels of x.
+// No LDS, no atomics: the lanes of a pixel combine by an xor butterfly, a fixed order.
+template <typename T, int NJ, bool UP>
+__global__ __launch_bounds__(256) void pixelnorm_act_bwd_kernel(const T* __restrict__ g, const T* __restrict__ x, T* __restrict__ out,
+                                                                 long npix, int H, int W, int C, int lpp, float eps, int act) {
+    constexpr int EP = Elem<T>::PER16;
+    const int lane = threadIdx.x & 63;
+    const int ppw = 64 / lpp, sub = lane / lpp, li = lane % lpp;
+    const long p = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * ppw + sub;
+    const bool ok = p < npix;
+    size_t gbase = (size_t)p * C;
+    const size_t row = (size_t)2 * W * C;              // UP: one row of g
+    if constexpr (UP) {
+        const long hw = (long)H * W, b = p / hw, rem = p % hw;
+        const long y = rem / W, xx = rem % W;
+        gbase = (((size_t)b * 2 * H + 2 * y) * 2 * W + 2 * xx) * C;
+    }
+    float f[NJ][EP], gl[NJ][EP];
+    float s = 0.f, d = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+        const int co = (j * lpp + li) * EP;
+        if (ok) {
+            unpack16(*(const uint4*)(x + (size_t)p * C + co), f[j], (T*)nullptr);
+            unpack16(*(const uint4*)(g + gbase + co), gl[j], (T*)nullptr);
+            if constexpr (UP) {
+                float g1[EP], g2[EP], g3[EP];
+                unpack16(*(const uint4*)(g + gbase + C + co), g1, (T*)nullptr);
+                unpack16(*(const uint4*)(g + gbase + row + co), g2, (T*)nullptr);
+                unpack16(*(const uint4*)(g + gbase + row + C + co), g3, (T*)nullptr);
+#pragma unroll
+                for (int e = 0; e < EP; e++) gl[j][e] = ((gl[j][e] + g1[e]) + g2[e]) + g3[e];          // nearest_up2_bwd_kernel's order
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < EP; e++) { f[j][e] = 0.f; gl[j][e] = 0.f; }
+        }
+#pragma unroll
+        for (int e = 0; e < EP; e++) { s += f[j][e] * f[j][e]; d += f[j][e] * gl[j][e]; }
+    }
+    for (int m = lpp >> 1; m > 0; m >>= 1) { s += __shfl_xor(s, m, 64); d += __shfl_xor(d, m, 64); }
+    const float r = rsqrtf(s / (float)C + eps);
+    const float k = d * r * r * r / (float)C;
+    if (ok) {
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+#pragma unroll
+            for (int e = 0; e < EP; e++) {
+                const float gx = gl[j][e] * r - f[j][e] * k;
+                gl[j][e] = act ? gx * (f[j][e] > 0.f ? 1.f : 0.2f) : gx;          // dge_act_bwd's rule: slope 0.2 at x <= 0
+            }
+            *(uint4*)(out + (size_t)p * C + (j * lpp + li) * EP) = pack16(gl[j], (T*)nullptr);
+        }
+    }
+}
+
 // =================================================================== C ABI
 
 extern "C" int dge_fromrgb2(const float* img, const float* w, const float* bias, void* y, float* stats, float* img4, int B, int HW,
@@ -385,5 +444,36 @@ extern "C" int dge_pixelnorm_nhwc_bwd(const void* gy, const void* x, void* gx, l
                                       : pixelnorm_nhwc_bwd_launch<float>(gy, x, gx, npix, C, eps, s);
     if (rc) return rc;
     DGE_LAUNCH_CHECK("pixelnorm_nhwc_bwd");
+    return 0;
+}
+
+template <typename T>
+static int pixelnorm_act_bwd_launch(const void* g, const void* x, void* out, int B, int H, int W, int C, int up, int act, float eps,
+                                    hipStream_t s) {
+    constexpr int EP = Elem<T>::PER16;
+    const int chunks = C / EP;
+    const int lpp = chunks >= 64 ? 64 : chunks;
+    const int nj = chunks / lpp;
+    const long npix = (long)B * H * W;
+    const long ppb = 4 * (64 / lpp);
+    if ((npix + ppb - 1) / ppb > 0x7fffffffL) { dge_set_error("pixelnorm_act_bwd: %ld pixels exceed one grid", npix); return -1; }
+    dim3 grid((unsigned)((npix + ppb - 1) / ppb));
+#define PAB(NJ, UP) hipLaunchKernelGGL((pixelnorm_act_bwd_kernel<T, NJ, UP>), grid, dim3(256), 0, s, (const T*)g, (const T*)x, (T*)out, npix, H, W, C, lpp, eps, act)
+    if (nj == 1) { if (up) PAB(1, true); else PAB(1, false); }
+    else if (nj == 2) { if (up) PAB(2, true); else PAB(2, false); }
+    else { dge_set_error("pixelnorm_act_bwd: unsupported C=%d", C); return -1; }
+#undef PAB
+    return 0;
+}
+extern "C" int dge_pixelnorm_act_bwd(const void* g, const void* x, void* out, int B, int H, int W, int C, int up, int act, float eps,
+                                     int dtype, hipStream_t s) {
+    const int ep = dtype == DGE_BF16 ? 8 : 4;
+    DGE_CHECK(g && x && out && B >= 1 && H >= 1 && W >= 1, "pixelnorm_act_bwd: bad operands (%d x %d x %d)", B, H, W);
+    DGE_CHECK(C >= ep && C % ep == 0 && ((C / ep) & (C / ep - 1)) == 0, "pixelnorm_act_bwd: C=%d must be a power-of-two multiple of %d", C, ep);
+    const int rc = dtype == DGE_BF16 ? pixelnorm_act_bwd_launch<bf16_t>(g, x, out, B, H, W, C, up, act, eps, s)
+                                      : pixelnorm_act_bwd_launch<float>(g, x, out, B, H, W, C, up, act, eps, s);
+    if (rc) return rc;
+    dge_note_kernel("pixelnorm_act_bwd<%s,%s,%s>", dtype == DGE_BF16 ? "bf16" : "f32", up ? "up" : "same", act ? "act" : "lin");
+    DGE_LAUNCH_CHECK("pixelnorm_act_bwd");
     return 0;
 }

@@ -45,6 +45,10 @@ Decisions where the reference cannot run as written:
         captured iteration keeps its shape) and discards the padded rows' outputs;
       - the encoder is shared by a group, so mode "E" has no independent form (ValueError).
 
+Generator kind "pg" (embedding_v2_pggan.PGEmbedStep: PGGAN + E_PG) runs the same iteration on z [B, z_space_dim] through three
+hooks - _latent_shape, _encode (E_PG has no const output: const2 / const3 / loss_c1 are None) and _generate - in StyleGAN1's
+order and with its defaults and tracker rules; "sg1" and "sg2" issue the launches they issued before.
+
 The file side of a group (dump_group, loss_txt_block, finish_group) and the group walk of main() (invert_folder, rows_plan) serve
 embedding_v2_biggan too: its dumps differ in the two file-name patterns and in the Loss.txt block, its walk in labels and
 img_all_*.pt.
@@ -116,6 +120,8 @@ class _WplusLerp(torch.autograd.Function):
 
 
 class LatentEmbedStep(GraphReplay):
+    fused_backward = True          # "pg": the generator backward with ops.pixelnorm_act_bwd (False: the composed launches, for timing)
+
     def __init__(self, G, E, lpips_model, mode="E", generator="sg2", lr=0.005, beta_1=0.0, beta=None, norm_p=2, truncation=None,
                  iterations=None, arm_iter=None, events_cap=256, seed=0, independent=False):
         if mode not in ("E", "W"):
@@ -123,10 +129,9 @@ class LatentEmbedStep(GraphReplay):
         if independent and mode != "W":
             raise ValueError("independent=True needs mode 'W': in mode 'E' one encoder is shared by the rows of a group")
         self.independent = bool(independent)
-        if generator not in ("sg1", "sg2"):
-            raise ValueError(f"generator must be 'sg1' or 'sg2', got {generator!r}")
-        mt = 1 if generator == "sg1" else 2
-        d = DEFAULTS[mt]
+        if generator not in ("sg1", "sg2", "pg"):
+            raise ValueError(f"generator must be 'sg1', 'sg2' or 'pg', got {generator!r}")
+        d = DEFAULTS[2 if generator == "sg2" else 1]          # "pg" (embedding_v2_pggan): StyleGAN1's defaults, rules and order
         self.G, self.E, self.lpips = G, E, lpips_model
         self.mode, self.generator = mode, generator
         self.lr, self.beta_1 = lr, beta_1
@@ -134,7 +139,7 @@ class LatentEmbedStep(GraphReplay):
         self.norm_p = int(norm_p)
         self.psi = (d["truncation"] if truncation is None else float(truncation)) if generator == "sg2" else None
         self.iterations = d["iterations"] if iterations is None else int(iterations)
-        self.rules = tracker_rules(generator, self.iterations)
+        self.rules = tracker_rules("sg2" if generator == "sg2" else "sg1", self.iterations)
         if arm_iter is not None:
             self.rules["arm_iter"] = int(arm_iter)
         self.events_cap, self.seed = int(events_cap), seed
@@ -156,6 +161,15 @@ class LatentEmbedStep(GraphReplay):
     def _num_rows(self):
         return self.E.layer_count * 2
 
+    def _latent_shape(self, B):
+        """Shape of the latent w1: the W+ code [B, rows, 512]; "pg": z [B, z_space_dim]."""
+        return (B, self.G.z_space_dim) if self.generator == "pg" else (B, self._num_rows(), 512)
+
+    def _encode(self, imgs, noises):
+        """(const, w) = E(imgs); "pg": E_PG has no const output -> (None, z)."""
+        const, w = self.E(imgs, noises=noises)
+        return (None if self.generator == "pg" else const), w
+
     def begin_image(self, imgs1, w_init=None, noises=None):
         """Start an image group: E mode re-loads the encoder checkpoint and clears the Adam state (embedding_v2_*.py: the
         per-group `E.load_state_dict`); W mode starts a fresh w1 (StyleGAN1: E(imgs1) detached, StyleGAN2: seeded randn or
@@ -166,7 +180,7 @@ class LatentEmbedStep(GraphReplay):
         dev = imgs1.device
         B = imgs1.shape[0]
         self.group += 1
-        shape = (B, self._num_rows(), 512)
+        shape = self._latent_shape(B)
         if self.mode == "E":
             self.E.load_state_dict(self._ckpt)
             weight_cache.written(self.E.parameters())
@@ -175,6 +189,8 @@ class LatentEmbedStep(GraphReplay):
             with torch.no_grad():
                 if w_init is not None:
                     w0 = w_init.to(dev, torch.float32).reshape(shape)
+                elif self.generator == "pg":
+                    w0 = self._encode(imgs1, noises)[1]
                 elif self.generator == "sg1":
                     c0, w0 = self.E(imgs1, noises=noises)
                     if self._const2 is None or self._const2.shape != c0.shape:
@@ -188,7 +204,7 @@ class LatentEmbedStep(GraphReplay):
                     w0 = torch.randn(shape, generator=gen)
                 if self.w1 is None or tuple(self.w1.shape) != shape or self.w1.device != dev:
                     if self.captured:
-                        raise ValueError("LatentEmbedStep.begin_image: the captured iteration works on a different W+ shape")
+                        raise ValueError("LatentEmbedStep.begin_image: the captured iteration works on a different latent shape")
                     self.w1 = torch.zeros(shape, dtype=torch.float32, device=dev, requires_grad=True)
                     self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
                 self.w1.copy_(w0)
@@ -199,6 +215,8 @@ class LatentEmbedStep(GraphReplay):
     def _generate(self, w1, noises):
         if self.generator == "sg1":
             return self.G.forward(w1, self.lod, noises=noises)
+        if self.generator == "pg":          # (lod given: the generator does not read its `lod` buffer back, a captured iteration cannot)
+            return self.G(w1, lod=0, fused_backward=self.fused_backward)["image"]
         syn = self.G.synthesis
         # (the synthesis backward reads its saved activations only, never wp: w1 itself may be the input when psi == 1)
         wt = w1 if self.psi == 1.0 else _WplusLerp.apply(w1, self.G.truncation.w_avg, self.psi)
@@ -208,25 +226,24 @@ class LatentEmbedStep(GraphReplay):
         """One iteration; `noises` = optional (E(imgs1), G, E(imgs2)) noise lists for parity runs (StyleGAN2: G's is unused, the
         synthesis noise is its fixed buffers; W mode: E(imgs1)'s is unused).  Independent mode: the loss entries of the result
         (`loss_msiv`, `loss_w`, `loss_c1`, `norm`, `loss_mslv`, `w_norm`) are [B], `info_img` is [B,3,8]."""
-        E = self.E
         rows = self.independent
         if self.group < 0:
             raise RuntimeError("LatentEmbedStep.step: call begin_image() first")
         ops.zero_arena_begin(imgs1.device)
         if self.mode == "E":
-            const2, w1 = E(imgs1, noises=noises[0])
+            const2, w1 = self._encode(imgs1, noises[0])
         else:
             w1, const2 = self.w1, self._const2
         imgs2 = self._generate(w1, noises[1])
-        if self.generator == "sg1":
-            const3, w2 = E(imgs2, noises=noises[2])
+        if self.generator != "sg2":
+            const3, w2 = self._encode(imgs2, noises[2])
         image_loss, latent_loss = (losses.image_loss_tsa_rows, losses.space_loss_rows) if rows else (losses.image_loss_tsa, losses.space_loss)
         loss_msiv, info_img = image_loss(imgs1, imgs2, self.lpips, weights=IMG_WEIGHTS, grad_windows=(True, True, True))
         self.opt.zero_grad()
         loss_msiv.backward(retain_graph=True)
         self.opt.step()
         if self.generator == "sg2":
-            const3, w2 = E(imgs2, noises=noises[2])
+            const3, w2 = self._encode(imgs2, noises[2])
         loss_w, info_w = latent_loss(w1, w2, image_space=False)
         lat = loss_w
         loss_c1 = None
@@ -249,8 +266,8 @@ class LatentEmbedStep(GraphReplay):
         self._tracker.update(loss_msiv.detach(), w1d)
         ops.zero_arena_end()
         self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const2=const2.detach() if const2 is not None else None,
-                         const3=const3.detach(), loss_msiv=loss_msiv.detach(), info_img=info_img, loss_w=loss_w.detach(),
-                         loss_c1=loss_c1.detach() if loss_c1 is not None else None, norm=nrm.detach(), loss_mslv=loss_mslv.detach(),
+                         const3=const3.detach() if const3 is not None else None, loss_msiv=loss_msiv.detach(), info_img=info_img,
+                         loss_w=loss_w.detach(), info_w=info_w, loss_c1=loss_c1.detach() if loss_c1 is not None else None, norm=nrm.detach(), loss_mslv=loss_mslv.detach(),
                          w_norm=self._tracker.l2)
         return self.last
 

@@ -1289,6 +1289,26 @@ def pixelnorm_nhwc_bwd(gy, x, eps=1e-8):
     return gx
 
 
+def pixelnorm_act_bwd_supported(Cc, dtype):
+    """Whether dge_pixelnorm_act_bwd takes the channel count: dge_pixelnorm_nhwc_bwd's rule (a power-of-two number of 16-byte
+    chunks, at most two per lane of a wave)."""
+    chunks, rem = divmod(int(Cc), 8 if dtype == BF16 else 4)
+    return rem == 0 and chunks >= 1 and chunks & (chunks - 1) == 0 and chunks <= 128
+
+
+def pixelnorm_act_bwd(g, x, up=False, act=True, eps=1e-8):
+    """pixelnorm_nhwc_bwd(g, x) times lrelu'(x) (`act`) in one launch; `up`: g is [B,2H,2W,C] and is first summed over its 2x2
+    blocks in f32 (nearest_up2_bwd).  x [B,H,W,C]: the activation the pixel norm read, itself the output of a leaky-relu(0.2)."""
+    B, H, W, Cc = x.shape
+    if tuple(g.shape) != ((B, 2 * H, 2 * W, Cc) if up else (B, H, W, Cc)) or g.dtype != x.dtype:
+        raise DgeError(f"pixelnorm_act_bwd: g {tuple(g.shape)} {g.dtype} does not go with x {tuple(x.shape)} {x.dtype} (up={bool(up)})")
+    out = torch.empty_like(x)
+    check(lib().dge_pixelnorm_act_bwd(_p(g), _p(x), _p(out), B, H, W, Cc, 1 if up else 0, 1 if act else 0, float(eps), dtype_of(x),
+                                      _stream()), "dge_pixelnorm_act_bwd")
+    log_kernel()
+    return out
+
+
 # ------------------------------------------------------------------ BigGAN-deep backward ops
 def affine_relu_bwd(gu, x, a, b):
     """Backward of u = relu(a*x + b): -> (gx, stats [B,C,2] = (d/da, d/db))."""

@@ -79,14 +79,16 @@ class PGGANGenerator(nn.Module):
             hit = store(L._cache, "dense0", L.weight, (w, L.bias.detach().repeat(16).contiguous()))
         return hit
 
-    def forward(self, z, label=None, lod=None, **_unused_kwargs):
+    def forward(self, z, label=None, lod=None, fused_backward=False, **_unused_kwargs):
+        """fused_backward: the backward runs every pixel-norm backward -> activation backward pair (with the nearest-upsample adjoint
+        of an up layer in between) as one ops.pixelnorm_act_bwd launch; the forward and the default backward are unchanged."""
         if z.ndim != 2 or z.shape[1] != self.z_space_dim:
             raise ValueError(f"Input latent code should be with shape [batch_size, latent_dim], where `latent_dim` equals "
                              f"to {self.z_space_dim}!\nBut `{z.shape}` is received!")
         lod = float(self.lod) if lod is None else lod
         if lod != 0:
             raise ValueError("only lod == 0 is implemented (the released generators are fully grown)")
-        image, zn = _PGGANFunction.apply(self, z)
+        image, zn = _PGGANFunction.apply(self, z, bool(fused_backward))
         return {"z": zn, "label": label, "image": image}
 
     # ------------------------------------------------------------------ pipelines
@@ -121,20 +123,38 @@ class PGGANGenerator(nn.Module):
             saved.update(x_last=x, xn_last=xn, out=O_)
         return image, zn, saved
 
-    def _backward(self, saved, g_image):
-        """d(image)/d(z) contracted with g_image (hand-written data gradient; the generator's parameters are frozen in E_align)."""
+    def _backward(self, saved, g_image, fused=False):
+        """d(image)/d(z) contracted with g_image (hand-written data gradient; the generator's parameters are frozen in E_align).
+        `fused`: between two data-gradient convs (and behind torgb_bwd) one ops.pixelnorm_act_bwd launch stands for
+        [nearest_up2_bwd ->] pixelnorm_nhwc_bwd -> act_bwd: the activation the pixel norm read is the previous conv's leaky-relu
+        output, so both factors come from one read of it and the gradient is not rounded in between.  A channel count the launch
+        refuses takes the composed launches; the dense layer-0 tail is the same in both forms."""
         dt = ops.dtype_of(saved["x_last"])
         B = g_image.shape[0]
         O_ = saved["out"]
         ones = torch.ones((B, saved["x_last"].shape[3]), dtype=torch.float32, device=g_image.device)
         g_xn, _ = ops.torgb_bwd(g_image.float().contiguous(), saved["xn_last"], O_.weight.detach().reshape(3, -1), ones, O_.wscale)
-        g = ops.pixelnorm_nhwc_bwd(g_xn, saved["x_last"])
-        for L, x_in, y, up in reversed(saved["convs"]):
-            g_pre = ops.act_bwd(g, y, None, pool=False, scale=1.0) if L.act == ops.ACT_LRELU else g
+        convs = saved["convs"]
+
+        def fuse(i):
+            """whether the pixel norm in front of convs[i + 1] (i == len - 1: in front of the output layer) is fused with the
+            activation backward of convs[i], whose output it read"""
+            return fused and convs[i][0].act == ops.ACT_LRELU and ops.pixelnorm_act_bwd_supported(convs[i][2].shape[3], dt)
+        last = len(convs) - 1
+        if fuse(last):
+            g, pre_done = ops.pixelnorm_act_bwd(g_xn, saved["x_last"]), True
+        else:
+            g, pre_done = ops.pixelnorm_nhwc_bwd(g_xn, saved["x_last"]), False
+        for i in range(last, -1, -1):
+            L, x_in, y, up = convs[i]
+            g_pre = g if pre_done or L.act != ops.ACT_LRELU else ops.act_bwd(g, y, None, pool=False, scale=1.0)
             g_xn = ops.conv2d(g_pre, L.packed(dt, ops.PACK_DGRAD), L.in_c, 3)
+            if i > 0 and fuse(i - 1):                       # x_in is convs[i - 1]'s output
+                g, pre_done = ops.pixelnorm_act_bwd(g_xn, x_in, up=up), True
+                continue
             if up:
                 g_xn, _ = ops.nearest_up2_bwd(g_xn)
-            g = ops.pixelnorm_nhwc_bwd(g_xn, x_in)
+            g, pre_done = ops.pixelnorm_nhwc_bwd(g_xn, x_in), False
         # layer0: h = lrelu(wscale * zn @ wd^T + bd) viewed as NHWC [B,4,4,C0]
         C0 = self.layer0.out_c
         g_h = ops.nhwc_to_nchw(g.view(B, 1, 1, 16 * C0)).view(B, 4, 4, C0)          # f32, same (y, x, c) order as h
@@ -147,10 +167,10 @@ class PGGANGenerator(nn.Module):
 
 class _PGGANFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, G, z):
+    def forward(ctx, G, z, fused_backward=False):
         need = ctx.needs_input_grad[1]
         image, zn, saved = G._run(z.detach(), save=need)
-        ctx.G, ctx.saved_acts = G, saved
+        ctx.G, ctx.saved_acts, ctx.fused = G, saved, fused_backward
         ctx.mark_non_differentiable(zn)
         return image, zn
 
@@ -158,4 +178,4 @@ class _PGGANFunction(torch.autograd.Function):
     def backward(ctx, g_image, _g_zn):
         if ctx.saved_acts is None:
             raise RuntimeError("PGGAN forward ran without saved activations")
-        return None, ctx.G._backward(ctx.saved_acts, g_image)
+        return None, ctx.G._backward(ctx.saved_acts, g_image, ctx.fused), None

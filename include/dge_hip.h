@@ -607,6 +607,12 @@ int dge_conv_pp(const dge_conv_pp_desc* d, dge_stream_t stream);
 int dge_pixelnorm_nhwc(const void* x, void* y, long npix, int C, float eps, int dtype, dge_stream_t stream);
 /* backward of dge_pixelnorm_nhwc: gx = r*(gy - yhat*mean_c(gy*yhat)), r = rsqrt(mean_c x^2 + eps), yhat = x*r */
 int dge_pixelnorm_nhwc_bwd(const void* gy, const void* x, void* gx, long npix, int C, float eps, int dtype, dge_stream_t stream);
+/* dge_pixelnorm_nhwc_bwd fused with what surrounds it in the generator backward: x [B,H,W,C] is what the pixel norm read and the
+ * output of the previous leaky-relu(0.2).  up = 1: g is [B,2H,2W,C] and gl its 2x2 block sum (adjoint of the nearest x2 upsample, kept
+ * in f32), else gl = g [B,H,W,C].  out = (r*gl - x*(sum_c gl*x)*r^3/C) * (act ? lrelu'(x) : 1), lrelu'(x) = x > 0 ? 1 : 0.2 as in
+ * dge_act_bwd.  One read of g and x, one store; no workspace.  Channel rule of dge_pixelnorm_nhwc_bwd. */
+int dge_pixelnorm_act_bwd(const void* g, const void* x, void* out, int B, int H, int W, int C, int up, int act, float eps, int dtype,
+                          dge_stream_t stream);
 
 /* ---- BigGAN-deep (model/biggan_generator.py) ----------------------------------------------- */
 /* BigGANBatchNorm :127-150 as a per-(b,c) affine: a = (1 + scale[b,c]) / sqrt(var[c]+eps), b = offset[b,c] - mean[c]*a
