@@ -167,6 +167,9 @@ SIGNATURES = {
     "dge_mask2cam_blocks": [_I],
     "dge_mask2cam": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     "dge_mask2cam_rows": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "dge_class_target_groups": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "dge_gather_row_groups": [_P, _P, _P, _I, _I, _I, _F, _P],
+    "dge_mask2cam_groups": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "dge_randn": [_P, _I, _P, _P, _P, _P, C.c_ulonglong, _P, _P],
     "dge_version": [],
     "dge_env_reload": [],
@@ -207,6 +210,8 @@ SIGNATURES = {
     "dge_quantize_u8": [_P, _I, _P, _I, _I, _I, _I, _P],
     "dge_image_metrics_u8_work_bytes": [_I, _I, _I],
     "dge_image_metrics_u8": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "dge_minmax_unit_slots": [C.c_long],
+    "dge_minmax_unit": [_P, _P, C.c_long, _P, _P],
 }
 
 _lib = None

@@ -137,6 +137,54 @@ __global__ void gather_rows_kernel(const float* __restrict__ w, const int* __res
     }
 }
 
+// The group forms (GradCAM.with_input_gradient_pair: imgs1 and imgs2 of a mis-align iteration in ONE VGG16 pass).  Rows
+// g*N .. g*N+N-1 are group g; workgroup g does for its rows what class_target_kernel does for a whole batch - the same scan, the
+// same vote, the same 1/N - so group g's slice of index_out ([G][1+N]) and glogits has the bits of dge_class_target on that slice.
+__global__ void class_target_groups_kernel(const float* __restrict__ logits, const int* __restrict__ index_in, int* __restrict__ index_out,
+                                           float* __restrict__ glogits, int N, int K) {
+    __shared__ int row_idx[1024];
+    __shared__ int best;
+    const int tid = threadIdx.x;
+    const size_t r0 = (size_t)blockIdx.x * N;
+    logits += r0 * K; glogits += r0 * K;
+    if (index_in) index_in += r0;
+    index_out += (size_t)blockIdx.x * (1 + N);
+    for (int b = tid; b < N; b += 256) {
+        if (index_in) { row_idx[b] = index_in[b]; continue; }
+        int am = 0; float mv = logits[(size_t)b * K];
+        for (int k = 1; k < K; k++) { const float v = logits[(size_t)b * K + k]; if (v > mv) { mv = v; am = k; } }
+        row_idx[b] = am;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int bi = 0, bc = -1;
+        for (int b = 0; b < N; b++) {
+            int cnt = 0;
+            for (int q = 0; q < N; q++) cnt += (row_idx[q] == row_idx[b]);
+            if (cnt > bc || (cnt == bc && row_idx[b] < bi)) { bc = cnt; bi = row_idx[b]; }
+        }
+        best = bi;
+        index_out[0] = bi;
+        for (int b = 0; b < N; b++) index_out[1 + b] = row_idx[b];
+    }
+    __syncthreads();
+    const float inv = 1.f / (float)N;
+    for (long i = tid; i < (long)N * K; i += 256) glogits[i] = ((int)(i % K) == best) ? inv : 0.f;
+}
+
+// y[row, :] = scale * w[index[g * (1 + N)], :], g = row / N: gather_row_kernel's expression with the group's index_max read
+// from class_target_groups' [G][1+N] layout.  A kernel of its own rather than gather_rows_kernel with a scale and a group
+// stride: the rows form keeps the launch it has (no multiply in it), and this one needs no expanded per-row index tensor.
+__global__ void gather_row_groups_kernel(const float* __restrict__ w, const int* __restrict__ index, float* __restrict__ y, int G, int N,
+                                         int I, float scale) {
+    const long per = (long)N * I, n = (long)G * per;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int g = (int)(i / per);
+        const float* row = w + (size_t)index[(size_t)g * (1 + N)] * I;
+        y[i] = scale * row[(i - (long)g * per) % I];
+    }
+}
+
 // Channel weights.  Grad-CAM++ (mode 1, grad_cam.py:180-186): s = sum_hw relu(g); weight = s > 0 ? s * (1/s) : 0.
 // Grad-CAM (mode 0, :101-102): weight = mean_hw g.  grid (C/64, B); 16 waves split the pixels, lane = channel (the grid is
 // small - 64 workgroups for 8 x 512 channels - so each workgroup brings many waves to hide the load latency).
@@ -275,6 +323,32 @@ __global__ void cam_norm_coef_kernel(const float* __restrict__ part, float* __re
         for (int i = 0; i < B; i++) {
             float m = fminf(done_min, ext[i * 3 + 1]);
             for (int j = i + 1; j < B; j++) m = fminf(m, ext[j * 3]);
+            const float scl = ext[i * 3 + 2] - m;
+            coef[2 * i] = m; coef[2 * i + 1] = scl;
+            done_min = fminf(done_min, (ext[i * 3 + 1] - m) / scl);
+        }
+    }
+}
+// cam_norm_coef_kernel with the recurrence restarted at every group of N rows (workgroup g: rows g*N .. g*N+N-1): what the
+// reference's loop gives when mask2cam is called on each group's slice.  coef [G*N][2].
+__global__ void cam_norm_coef_groups_kernel(const float* __restrict__ part, float* __restrict__ coef, int N, int nblk) {
+    __shared__ float ext[1024 * 3];
+    part += (size_t)blockIdx.x * N * nblk * 3;
+    coef += (size_t)blockIdx.x * N * 2;
+    for (int b = threadIdx.x; b < N; b += 256) {
+        float mi = INFINITY, mc = INFINITY, xc = -INFINITY;
+        for (int k = 0; k < nblk; k++) {
+            const float* o = part + ((size_t)b * nblk + k) * 3;
+            mi = fminf(mi, o[0]); mc = fminf(mc, o[1]); xc = fmaxf(xc, o[2]);
+        }
+        ext[b * 3] = mi; ext[b * 3 + 1] = mc; ext[b * 3 + 2] = xc;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float done_min = INFINITY;
+        for (int i = 0; i < N; i++) {
+            float m = fminf(done_min, ext[i * 3 + 1]);
+            for (int j = i + 1; j < N; j++) m = fminf(m, ext[j * 3]);
             const float scl = ext[i * 3 + 2] - m;
             coef[2 * i] = m; coef[2 * i + 1] = scl;
             done_min = fminf(done_min, (ext[i * 3 + 1] - m) / scl);
@@ -420,5 +494,33 @@ extern "C" int dge_mask2cam_rows(const float* mask, const float* img, const int*
     const long per = (long)3 * HW;
     hipLaunchKernelGGL(cam_norm_rows_kernel, dim3(blocks_for(per, 256), B), dim3(256), 0, s, cam, part, nblk, per);
     DGE_LAUNCH_CHECK("mask2cam_rows");
+    return 0;
+}
+
+extern "C" int dge_class_target_groups(const float* logits, const int* index_in, int* index_out, float* glogits, int G, int N, int K,
+                                       hipStream_t s) {
+    DGE_CHECK(G >= 1 && G <= 65535 && N >= 1 && N <= 1024 && K >= 1, "class_target_groups: G=%d (1..65535), N=%d (1..1024), K=%d", G, N, K);
+    hipLaunchKernelGGL(class_target_groups_kernel, dim3(G), dim3(256), 0, s, logits, index_in, index_out, glogits, N, K);
+    DGE_LAUNCH_CHECK("class_target_groups");
+    return 0;
+}
+
+extern "C" int dge_gather_row_groups(const float* w, const int* index, float* y, int G, int N, int I, float scale, hipStream_t s) {
+    DGE_CHECK(G >= 1 && N >= 1 && I >= 1, "gather_row_groups: G=%d N=%d I=%d", G, N, I);
+    hipLaunchKernelGGL(gather_row_groups_kernel, dim3(blocks_for((long)G * N * I, 1024)), dim3(256), 0, s, w, index, y, G, N, I, scale);
+    DGE_LAUNCH_CHECK("gather_row_groups");
+    return 0;
+}
+
+extern "C" int dge_mask2cam_groups(const float* mask, const float* img, const int* lut, float* heat, float* cam, float* part, float* coef,
+                                   int G, int N, int HW, hipStream_t s) {
+    DGE_CHECK(G >= 1 && N >= 1 && N <= 1024 && (long)G * N <= 65535 && HW >= 1, "mask2cam_groups: G=%d N=%d (1..1024, G*N <= 65535) HW=%d",
+              G, N, HW);
+    const int nblk = dge_mask2cam_blocks(HW), B = G * N;
+    hipLaunchKernelGGL(jet_overlay_kernel, dim3(nblk, B), dim3(256), 0, s, mask, img, lut, heat, cam, part, HW);
+    hipLaunchKernelGGL(cam_norm_coef_groups_kernel, dim3(G), dim3(256), 0, s, part, coef, N, nblk);
+    const long n = (long)B * 3 * HW;
+    hipLaunchKernelGGL(cam_norm_apply_kernel, dim3(blocks_for(n, 4096)), dim3(256), 0, s, cam, coef, (long)3 * HW, n);
+    DGE_LAUNCH_CHECK("mask2cam_groups");
     return 0;
 }

@@ -166,6 +166,44 @@ __global__ __launch_bounds__(256) void image_metrics_u8_finalize_kernel(const lo
 }
 
 // H, W <= 65536 keeps 4 * 255^2 * 3HW (the largest integer formed) below 2^52 and the tile grid inside the launch limits
+// ------------------------------------------------------------------ min-max normalisation of a whole array
+// y = (x - min x) / (max x - min x): the guided-gradient picture of the mis-align scripts (E_mis_align_cropping_s1.py:292-293,
+// `grads -= np.max(np.min(grads), 0); grads /= np.max(grads)` - the 0 is an axis, so this is the global minimum, then the new
+// maximum).  Launch 1: workgroup k writes the extrema of its grid-strided elements to slot k.  Launch 2: every workgroup reduces
+// the <= 1024 slots in the same fixed order (four per thread, then an LDS tree) and applies (x - mn) / (mx - mn) as a subtraction
+// and a correctly rounded division, the two numpy operations.
+constexpr int MMU_MAX_SLOTS = 1024;
+
+__device__ __forceinline__ void mmu_tree(float* lo, float* hi, int t) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) { lo[t] = fminf(lo[t], lo[t + o]); hi[t] = fmaxf(hi[t], hi[t + o]); }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void minmax_slots_kernel(const float* __restrict__ x, float* __restrict__ slots, long n) {
+    __shared__ float lo[256], hi[256];
+    const int t = threadIdx.x;
+    float a = INFINITY, z = -INFINITY;
+    for (long i = blockIdx.x * 256L + t; i < n; i += (long)gridDim.x * 256) { const float v = x[i]; a = fminf(a, v); z = fmaxf(z, v); }
+    lo[t] = a; hi[t] = z;
+    mmu_tree(lo, hi, t);
+    if (t == 0) { slots[2 * blockIdx.x] = lo[0]; slots[2 * blockIdx.x + 1] = hi[0]; }
+}
+
+__global__ __launch_bounds__(256) void minmax_unit_apply_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                                 const float* __restrict__ slots, int nslots, long n) {
+    __shared__ float lo[256], hi[256];
+    const int t = threadIdx.x;
+    float a = INFINITY, z = -INFINITY;
+    for (int k = t; k < nslots; k += 256) { a = fminf(a, slots[2 * k]); z = fmaxf(z, slots[2 * k + 1]); }
+    lo[t] = a; hi[t] = z;
+    mmu_tree(lo, hi, t);
+    const float mn = lo[0], span = hi[0] - mn;
+    for (long i = blockIdx.x * 256L + t; i < n; i += (long)gridDim.x * 256) y[i] = (x[i] - mn) / span;
+}
+
 inline bool metrics_shape_ok(int B, int H, int W) { return B >= 1 && B <= 65535 && H >= 7 && W >= 7 && H <= 65536 && W <= 65536; }
 inline long long metrics_slots(int H, int W) { return (long long)((H - 6 + TH - 1) / TH) * ((3 * (W - 6) + TQ - 1) / TQ); }
 
@@ -205,5 +243,23 @@ extern "C" int dge_image_metrics_u8(const unsigned char* a, const unsigned char*
     hipLaunchKernelGGL(image_metrics_u8_finalize_kernel, dim3(B), dim3(256), 0, s, (const long long*)work, tx * ty, H, W, isums, ssim, out);
     dge_note_kernel("image_metrics_u8");
     DGE_LAUNCH_CHECK("image_metrics_u8_finalize");
+    return 0;
+}
+
+extern "C" int dge_minmax_unit_slots(long n) {
+    const long g = (n + 1023) / 1024;                   // four elements per thread before a second slot is opened
+    return (int)(g < 1 ? 1 : (g > MMU_MAX_SLOTS ? MMU_MAX_SLOTS : g));
+}
+
+extern "C" int dge_minmax_unit(const float* x, float* y, long n, float* slots, hipStream_t s) {
+    DGE_CHECK(x && y && slots && n >= 1, "minmax_unit: bad arguments (n %ld)", n);
+    const int nslots = dge_minmax_unit_slots(n);
+    hipLaunchKernelGGL(minmax_slots_kernel, dim3(nslots), dim3(256), 0, s, x, slots, n);
+    DGE_LAUNCH_CHECK("minmax_slots");
+    long g = (n + 255) / 256;
+    g = g > 4096 ? 4096 : g;
+    hipLaunchKernelGGL(minmax_unit_apply_kernel, dim3((unsigned)g), dim3(256), 0, s, x, y, (const float*)slots, nslots, n);
+    dge_note_kernel("minmax_unit");
+    DGE_LAUNCH_CHECK("minmax_unit_apply");
     return 0;
 }

@@ -105,11 +105,15 @@ class VGG16(nn.Module):
 
     # ------------------------------------------------------------------ forward
     def run(self, inputs):
-        """inputs [N,3,H,W] f32 -> (logits [N,K] f32, saved state for the backward)."""
-        if inputs.dim() != 4 or inputs.shape[1] != 3:
-            raise ValueError(f"inputs must be [N,3,H,W], got {tuple(inputs.shape)}")
+        """inputs [N,3,H,W] f32 -> (logits [N,K] f32, saved state for the backward).  A tuple of such tensors of one shape is their
+        concatenation along N: each is laid into its rows of the first conv's NHWC operand, no concatenated copy is made."""
+        parts = tuple(inputs) if isinstance(inputs, (tuple, list)) else (inputs,)
+        inputs = parts[0]
+        if inputs.dim() != 4 or inputs.shape[1] != 3 or any(p.shape != inputs.shape for p in parts):
+            raise ValueError(f"inputs must be [N,3,H,W] (all of one shape), got {[tuple(p.shape) for p in parts]}")
         npool = sum(1 for p in self.plan if p[0] == "pool")
-        N, _, H, W = inputs.shape
+        n1, _, H, W = inputs.shape
+        N = n1 * len(parts)
         if H % (1 << npool) or W % (1 << npool):
             raise ValueError(f"H and W must be multiples of {1 << npool}, got {H}x{W}")
         dt = _dt(self.compute_dtype)
@@ -117,7 +121,8 @@ class VGG16(nn.Module):
         dev = inputs.device
         one, zero = (C.c_float * 3)(1, 1, 1), (C.c_float * 3)(0, 0, 0)
         x = torch.empty((N, H, W, _CPAD), dtype=ops.tdtype(dt), device=dev)
-        check(L.dge_lpips_prep(_f32(inputs.contiguous()), _p(x), N, H * W, _CPAD, zero, one, dt, _stream()), "dge_lpips_prep")
+        for k, part in enumerate(parts):
+            check(L.dge_lpips_prep(_f32(part.contiguous()), _p(x[k * n1:]), n1, H * W, _CPAD, zero, one, dt, _stream()), "dge_lpips_prep")
         acts = []            # post-ReLU output of every conv, in plan order
         cur = x
         for p in self.plan:
@@ -140,16 +145,28 @@ class VGG16(nn.Module):
         return self.run(inputs)[0]
 
     # ------------------------------------------------------------------ backward of target = mean_n logits[n, index_max]
-    def select_target(self, logits, index=None):
-        """grad_cam.py:166-170 on the device.  Returns (index tensor int32 [1+N]: [index_max, per-row indices], glogits)."""
+    def select_target(self, logits, index=None, groups=1):
+        """grad_cam.py:166-170 on the device.  Returns (index tensor int32 [1+N]: [index_max, per-row indices], glogits).
+        groups=G > 1: the rows are G batches of N/G, each with a vote of its own and target mean over ITS rows; the index tensor is
+        [G, 1+N/G], group g's row and its rows of glogits being what this call returns on that group's slice (dge_class_target_groups)."""
         N, K = logits.shape
         idx_in = None
         if index is not None:
             idx_in = torch.as_tensor(index, dtype=torch.int32).reshape(-1).to(logits.device)
             if idx_in.numel() != N:
                 raise ValueError("index must hold one class id per input")
-        out = torch.empty(1 + N, dtype=torch.int32, device=logits.device)
         g = torch.empty_like(logits)
+        if groups != 1:
+            if groups < 1 or N % groups:
+                raise ValueError(f"groups={groups} must divide the {N} rows")
+            if index is not None and not torch.is_tensor(index) and (min(index) < 0 or max(index) >= K):
+                raise ValueError(f"index must lie in [0, {K})")          # (the winning id addresses a row of the last layer's weight)
+            out = torch.empty((groups, 1 + N // groups), dtype=torch.int32, device=logits.device)
+            check(lib().dge_class_target_groups(_f32(logits), _p(idx_in), _p(out), _f32(g), groups, N // groups, K, _stream()),
+                  "dge_class_target_groups")
+            ops._log_dense("class_target_groups")
+            return out, g
+        out = torch.empty(1 + N, dtype=torch.int32, device=logits.device)
         check(lib().dge_class_target(_f32(logits), _p(idx_in), _p(out), _f32(g), N, K, _stream()), "dge_class_target")
         ops._log_dense("class_target")
         return out, g
@@ -186,16 +203,25 @@ class VGG16(nn.Module):
               "dge_maxpool2_relu_bwd")
         return out
 
-    def backward_to_last_conv(self, st, index_dev, rows=False):
+    def backward_to_last_conv(self, st, index_dev, rows=False, groups=1):
         """Gradient of the target w.r.t. the OUTPUT of the last conv (pre-ReLU), NHWC [N,h,w,C] - what the backward hook
         on `features.28` receives (grad_cam.py:30-40).  rows=True: `index_dev` is select_target_rows' [N] tensor and row n is the
-        gradient of its own target logits[n, index_n] (scale 1, a gather of rows: dge_gather_rows, a launch of its own)."""
+        gradient of its own target logits[n, index_n] (scale 1, a gather of rows: dge_gather_rows, a launch of its own).
+        groups=G > 1: `index_dev` is select_target(..., groups=G)'s [G, 1+N/G] tensor and every group's rows start from its own
+        index_max with its own 1/(N/G) (dge_gather_row_groups); everything behind that first step is per sample."""
         L = lib()
         N, dt = st["N"], st["dt"]
         c0, c3, c6 = (getattr(self.classifier, k) for k in ("0", "3", "6"))
         dev = st["h2"].device
         g2 = torch.empty_like(st["h2"])
-        if rows:
+        if groups != 1:
+            if rows or N % groups or tuple(index_dev.shape) != (groups, 1 + N // groups):
+                raise ValueError("backward_to_last_conv: groups takes select_target(..., groups=G)'s index tensor (and not rows=True)")
+            n = N // groups
+            check(L.dge_gather_row_groups(_f32(c6.weight.detach()), _p(index_dev), _f32(g2), groups, n, g2.shape[1], 1.0 / n, _stream()),
+                  "dge_gather_row_groups")
+            ops._log_dense("gather_row_groups")
+        elif rows:
             check(L.dge_gather_rows(_f32(c6.weight.detach()), _p(index_dev), _f32(g2), N, g2.shape[1], _stream()), "dge_gather_rows")
             ops._log_dense("gather_rows")
         else:
@@ -300,6 +326,26 @@ class GradCAM(object):
         self.feature = st["acts"][-1]
         return self._mask(st), self.net.backward_to_input(st, self.gradient)
 
+    def with_input_gradient_pair(self, imgs1, imgs2, index=None):
+        """with_input_gradient(imgs1) and with_input_gradient(imgs2) from ONE pass over the concatenated 2N images:
+        (mask_1, grad_1, mask_2, grad_2).  The network is per sample throughout; what couples the rows of a batch - the class vote, the
+        1/N of the mean target and its one-row gather - runs in its group form (select_target / backward_to_last_conv with groups=2), so
+        each half votes for its own class as the two separate calls do.  Half the launches on operands twice the size: the conv launches
+        see another M and may tile differently, so the values agree with the separate calls to rounding, not to the bit.
+        `index`: None, or the 2N class ids (imgs1's, then imgs2's).  `self.index` is the [2, 1+N] tensor, `self.feature` / `self.gradient`
+        hold all 2N rows, `self.pair_mask` / `self.pair_grad` the 2N-row tensors the four results are views of."""
+        if not self.net.guided:
+            raise DgeError("with_input_gradient_pair: construct GuidedBackPropagation(net) first (the input gradient is the guided one)")
+        if imgs1.shape != imgs2.shape:
+            raise ValueError(f"with_input_gradient_pair: the two batches must have one shape, got {tuple(imgs1.shape)} and {tuple(imgs2.shape)}")
+        N = imgs1.shape[0]
+        logits, st = self.net.run((imgs1, imgs2))
+        self.index, _ = self.net.select_target(logits, index, groups=2)
+        self.gradient = self.net.backward_to_last_conv(st, self.index, groups=2)
+        self.feature = st["acts"][-1]
+        self.pair_mask, self.pair_grad = mask, grad = self._mask(st), self.net.backward_to_input(st, self.gradient)
+        return mask[:N], grad[:N], mask[N:], grad[N:]
+
 
 class GradCamPlusPlus(GradCAM):
     """grad_cam.py:119-194 (`__call__` :157-194)."""
@@ -337,10 +383,13 @@ def _jet_table():
 _JET = {}
 
 
-def mask2cam(mask, imgs, rows=False):
+def mask2cam(mask, imgs, rows=False, groups=1):
     """grad_cam.py:234-251: mask [N,1,H,W], imgs [N,3,H,W] -> (heatmap, cam), both [N,3,H,W] f32 on the device.  rows=True: every
-    row is normalised on its own - row n is what mask2cam returns on the one-row slices (dge_mask2cam_rows)."""
+    row is normalised on its own - row n is what mask2cam returns on the one-row slices (dge_mask2cam_rows).  groups=G > 1: the
+    sequential normalisation restarts at every N/G rows - group g is what mask2cam returns on its slices (dge_mask2cam_groups)."""
     N, _, H, W = imgs.shape
+    if groups != 1 and (rows or groups < 1 or N % groups):
+        raise ValueError(f"mask2cam: groups={groups} must divide the {N} rows (and excludes rows=True)")
     dev = imgs.device
     if dev not in _JET:
         _JET[dev] = torch.from_numpy(_jet_table()).to(dev).contiguous()
@@ -355,6 +404,11 @@ def mask2cam(mask, imgs, rows=False):
         ops._log_dense("mask2cam_rows")
         return heat, cam
     coef = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    if groups != 1:
+        check(lib().dge_mask2cam_groups(_f32(mask), _f32(imgs), _p(_JET[dev]), _f32(heat), _f32(cam), _f32(part), _f32(coef), groups,
+                                        N // groups, H * W, _stream()), "dge_mask2cam_groups")
+        ops._log_dense("mask2cam_groups")
+        return heat, cam
     check(lib().dge_mask2cam(_f32(mask), _f32(imgs), _p(_JET[dev]), _f32(heat), _f32(cam), _f32(part), _f32(coef), N, H * W,
                              _stream()), "dge_mask2cam")
     ops._log_dense("mask2cam")

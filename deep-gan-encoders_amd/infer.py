@@ -118,6 +118,21 @@ def quantize_u8(img):
 
 
 @torch.no_grad()
+def minmax_unit(x):
+    """(x - min x) / (max x - min x) over the whole float32 device tensor: the guided-gradient picture of the mis-align scripts
+    (E_mis_align_cropping_s1.py:292-293, `grads -= np.max(np.min(grads), 0); grads /= np.max(grads)` - np.max's second argument is an
+    axis, so the first line subtracts the global minimum).  Two launches (dge_minmax_unit), no host read; the minimum maps to exactly
+    0 and the maximum to exactly 1.  A constant tensor divides by zero, as the script does."""
+    x = x.detach().contiguous()
+    y = torch.empty_like(x)
+    n = x.numel()
+    slots = torch.empty((lib().dge_minmax_unit_slots(n), 2), dtype=torch.float32, device=x.device)
+    check(lib().dge_minmax_unit(_f32(x), _f32(y), n, _f32(slots), _stream()), "dge_minmax_unit")
+    ops.log_kernel()
+    return y
+
+
+@torch.no_grad()
 def image_metrics_rows(img1, img2, lpips_model=None, quantize=True):
     """comparing-baseline.py:67-87 for a batch: every pair (img1[i], img2[i]) measured on its own, on 8-bit images as the script
     reads them from files (ToTensor()*255).  Inputs: uint8 [B,H,W,3] (decoded files, `quantize_u8` output), or float [B,3,H,W] in

@@ -684,6 +684,21 @@ int dge_mask2cam(const float* mask, const float* img, const int* lut, float* hea
 int dge_mask2cam_rows(const float* mask, const float* img, const int* lut, float* heat, float* cam, float* part, int B, int HW,
                       dge_stream_t stream);
 
+/* ---- group forms: G groups of N rows in one batch (GradCAM.with_input_gradient_pair: imgs1 and imgs2 through VGG16 once) ---- */
+/* dge_class_target on every group: rows g*N .. g*N+N-1 are group g.  Per row the first maximum of logits (or index_in[row]), per
+ * group the most frequent row index (smallest among ties); glogits[row,k] = (k == index_max_g) / N; index_out [G][1+N] laid out per
+ * group as dge_class_target's [1+N].  One launch, one workgroup per group; plain stores, no atomics, no pre-zeroed buffer: the same
+ * bits in both reduction modes, and group g's slices have the bits of dge_class_target on that group's rows.  N <= 1024. */
+int dge_class_target_groups(const float* logits, const int* index_in, int* index_out, float* glogits, int G, int N, int K,
+                            dge_stream_t stream);
+/* y[row,:] = scale * w[index[g*(1+N)], :], g = row / N (index: dge_class_target_groups' index_out); y [G*N, I].  The bits of
+ * dge_gather_row on every group slice. */
+int dge_gather_row_groups(const float* w, const int* index, float* y, int G, int N, int I, float scale, dge_stream_t stream);
+/* dge_mask2cam with the sequential normalisation restarted at every group: group g's heat / cam have the bits of dge_mask2cam on
+ * its N rows.  part: scratch [G*N, dge_mask2cam_blocks(HW), 3] f32, coef: scratch [G*N, 2] f32.  N <= 1024, G*N <= 65535. */
+int dge_mask2cam_groups(const float* mask, const float* img, const int* lut, float* heat, float* cam, float* part, float* coef, int G,
+                        int N, int HW, dge_stream_t stream);
+
 /* ---- inversion loop (embedding_v2.py; reference embedding_v2_styleGAN1.py / embedding_v2_styleGAN2.py) ----------------- */
 /* out[0] = ||w||_p = (sum |w|^p)^(1/p) over all n values (Tensor.norm(p), integer p >= 1), out_l2[0] = ||w||_2; either may be
  * NULL.  One workgroup, fixed-order tree: the same bits every run. */
@@ -744,6 +759,14 @@ int dge_quantize_u8(const void* x, int dtype, unsigned char* out, int B, int C, 
 int dge_image_metrics_u8_work_bytes(int B, int H, int W);
 int dge_image_metrics_u8(const unsigned char* a, const unsigned char* b, int B, int H, int W, void* work, long long* isums,
                          double* ssim, double* out, dge_stream_t stream);
+
+/* y = (x - min x) / (max x - min x) over all n f32 elements (the guided-gradient picture of the mis-align scripts: `grads -= min;
+ * grads /= max`), y may alias x.  Two launches: per-workgroup extrema to slots [dge_minmax_unit_slots(n)][2] (every slot written),
+ * then every workgroup reduces the slots in one fixed order and applies a subtraction and a correctly rounded division - the
+ * minimum maps to exactly 0, the maximum to exactly 1.  No atomics, no pre-zeroed buffer, no host read.
+ * dge_last_kernel: "minmax_unit". */
+int dge_minmax_unit_slots(long n);
+int dge_minmax_unit(const float* x, float* y, long n, float* slots, dge_stream_t stream);
 
 #ifdef __cplusplus
 }
