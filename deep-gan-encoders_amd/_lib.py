@@ -60,6 +60,8 @@ _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 SIGNATURES = {
     "dge_conv2d": [C.POINTER(ConvDesc), _P],
     "dge_fir_t2d": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "dge_up_dgrad_small": [C.POINTER(ConvDesc), _P],
+    "dge_up_dgrad_small_supported": [_I, _I, _I, _I, _I, _I],
     "dge_s2_style_grads": [C.POINTER(S2GradEntry), _I, _P, _I, _I, _I, _F, _P],
     "dge_conv_small_supported": [_I, _I, _I, _I, _I, _I, _I, _I],
     "dge_torgb_bwd_prep": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _F, _F, _I, _P],

@@ -73,7 +73,9 @@ static std::once_flag g_env_once;
 const DgeEnv& dge_env() { std::call_once(g_env_once, [] { if (!g_env_loaded) env_load(); }); return g_env; }
 extern "C" void dge_env_reload(void) { env_load(); }
 
-extern "C" int dge_conv2d(const dge_conv_desc* d, hipStream_t s) {
+// dge_conv_desc -> ConvParams with the argument checks of dge_conv2d; `units`: the caller is dge_up_dgrad_small (in_t2d with the
+// fragment-ordered unit weights)
+static int conv_desc_to_params(const dge_conv_desc* d, ConvParams& p, bool units) {
     DGE_CHECK(d && d->x && d->w_packed && d->y, "conv2d: null tensor");
     DGE_CHECK(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, "conv2d: bad shape");
     DGE_CHECK(d->dtype == DGE_F32 || d->dtype == DGE_BF16, "conv2d: bad dtype %d", d->dtype);
@@ -87,7 +89,6 @@ extern "C" int dge_conv2d(const dge_conv_desc* d, hipStream_t s) {
     DGE_CHECK(d->gain > 0.f, "conv2d: gain must be positive (it is folded through the activation)");
     DGE_CHECK((((uintptr_t)d->in_scale | (uintptr_t)d->in_shift) & 15) == 0, "conv2d: in_scale/in_shift must be 16-byte aligned");
     DGE_CHECK(!d->noise || d->noise_w, "conv2d: noise without noise_w");
-    ConvParams p;
     p.x = d->x; p.w = d->w_packed; p.y = d->y; p.addend = d->addend; p.dot_src = d->dot_src;
     p.in_scale = d->in_scale; p.in_shift = d->in_shift; p.out_scale = d->out_scale;
     p.bias = d->bias; p.noise = d->noise; p.noise_w = d->noise_w; p.stats = d->stats;
@@ -104,7 +105,7 @@ extern "C" int dge_conv2d(const dge_conv_desc* d, hipStream_t s) {
     p.prep = d->prep ? 1 : 0;
     p.mask_relu = d->mask_relu ? 1 : 0;
     p.in_t2d = d->in_t2d ? 1 : 0;
-    DGE_CHECK(!d->in_t2d || (d->ksize == 3 && !d->up && !d->in_s2d && !d->in_up2 && !d->in_scale && !d->in_shift && d->w_layout == 0),
+    DGE_CHECK(!d->in_t2d || (d->ksize == 3 && !d->up && !d->in_s2d && !d->in_up2 && !d->in_scale && !d->in_shift && (d->w_layout == 0 || units)),
               "conv2d: in_t2d is a plain 3x3 launch (no other read mode, no prologue affine, row-major weights)");
     p.prep_gain = d->prep_gain; p.prep_noise = d->prep_noise; p.prep_ns = d->prep_ns; p.prep_stats = d->prep_stats;
     p.prep_noise_bstride = d->prep_noise_batch > 1 ? OH * OW : 0;
@@ -134,7 +135,28 @@ extern "C" int dge_conv2d(const dge_conv_desc* d, hipStream_t s) {
         DGE_CHECK(dge_conv_rgb_ok(p, d->dtype, d->ksize), "conv2d: the fused toRGB is offered where dge_conv_rgb_supported() says so "
                   "(bf16 3x3 32 -> 32 launches of the streaming kernel)");
     }
+    return 0;
+}
+
+extern "C" int dge_conv2d(const dge_conv_desc* d, hipStream_t s) {
+    ConvParams p;
+    if (const int rc = conv_desc_to_params(d, p, false)) return rc;
     return dge_conv_launch(p, d->dtype, d->ksize, s);
+}
+
+// Phase-form adjoint of a low-resolution up layer on the low-resolution kernel (csrc/conv_small.hip): the launch dge_conv2d(in_t2d = 1)
+// describes - x = dge_fir_t2d's [B,H+1,W+1,Cin], Cin = 4 * the forward layer's out channels - with w_packed = the 9 non-zero units
+// (DGE_PACK_UPT2D_UNITS | DGE_PACK_FRAG), w_layout = 1.  Data-gradient epilogue only (out_scale, addend, dot_src + stats, prep).
+extern "C" int dge_up_dgrad_small(const dge_conv_desc* d, hipStream_t s) {
+    DGE_CHECK(d && d->in_t2d && d->w_layout == 1 && d->ksize == 3 && d->Cin % 4 == 0, "up_dgrad_small: an in_t2d launch with fragment-ordered unit weights");
+    DGE_CHECK(!d->bias && !d->noise && d->act == DGE_ACT_NONE && !d->mask_relu && !d->in_bwd_coef && !d->rgb_out && !d->pool_out && !d->in_relu,
+              "up_dgrad_small: data-gradient epilogue only (out_scale, addend, dot_src + stats, prep)");
+    DGE_CHECK(dge_up_dgrad_small_supported(d->B, d->H, d->W, d->Cin / 4, d->Cout, d->dtype),
+              "up_dgrad_small: unsupported launch %dx%d, %d <- %d channels, dtype %d", d->H, d->W, d->Cout, d->Cin / 4, d->dtype);
+    ConvParams p;
+    if (const int rc = conv_desc_to_params(d, p, true)) return rc;
+    p.Cin = d->Cin / 4;                                        // K of one unit
+    return dge_up_dgrad_small_launch(p, s);
 }
 
 // 1 when an encoder-flavour launch (instance-norm affine, per-sample noise, bias, lrelu; no statistics) of this shape may store the

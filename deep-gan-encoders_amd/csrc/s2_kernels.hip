@@ -65,6 +65,14 @@ __device__ __forceinline__ float upt2d_weight(const float* __restrict__ w, int o
     return w[((size_t)o * Cin + i) * 9 + (2 - ky) * 3 + (2 - kx)];
 }
 
+// DGE_PACK_UPT2D_UNITS (mode 7): the same adjoint as its 9 non-zero (phase, offset) units of K = Cout each, in the order the phase
+// flavour of csrc/conv_small.hip walks them - phase (0,0) with offsets {0,1}^2, phase (0,1) and (1,0) with two offsets each, phase
+// (1,1) with one: unit u reads Z[m + a][p, :] and holds w[o][i][2 - ky][2 - kx], (ky, kx) = 2a + p.  [9][Cin][Cout].
+__device__ __forceinline__ float upt2d_unit_weight(const float* __restrict__ w, int o, int i, int Cin, int unit) {
+    const int ky = (0x158a0 >> (2 * unit)) & 3, kx = (0x18588 >> (2 * unit)) & 3;        // ky: 0 0 2 2 0 2 1 1 1; kx: 0 2 0 2 1 1 0 2 1
+    return w[((size_t)o * Cin + i) * 9 + (2 - ky) * 3 + (2 - kx)];
+}
+
 // DGE_PACK_FRAG (mode bit 0x100): the same [tap][n][k] values stored in MFMA-fragment order for csrc/conv_small.hip, which loads
 // its weight operand straight from global memory: the 32 rows x 16 k block (tap, n/32, k/16) is one contiguous 1 KiB run in
 // lane order - lane = (n % 32) + 32 * ((k % 16) / 8) holds the 8 consecutive k of its v_mfma_f32_32x32x16_bf16 B operand - so a
@@ -81,7 +89,7 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ 
     const int frag = mode & 0x100;
     mode &= 0xff;
     const int ntap = KS * KS;
-    const int Kdim = (mode == 2) ? Cout : ((mode == 3 || mode == 5 || mode == 6) ? 4 * Cout : Cin);
+    const int Kdim = (mode == 2 || mode == 7) ? Cout : ((mode == 3 || mode == 5 || mode == 6) ? 4 * Cout : Cin);
     const int total = ntap * Ntot * Kdim;            // < 2^31 (checked by the launcher): 32-bit index math
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int k = idx % Kdim;
@@ -100,6 +108,8 @@ __global__ void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ 
             if (n < Cin) v = sg1_up_weight(w, n, k % Cout, Cout, k / Cout, 8 - tap);
         } else if (mode == 6) {
             if (n < Cin) v = upt2d_weight(w, k % Cout, n, Cin, k / Cout, tap);
+        } else if (mode == 7) {
+            if (n < Cin) v = upt2d_unit_weight(w, k, n, Cin, tap);
         } else {
             if (n < Cin) v = upfold_weight(w, k % Cout, n, Cin, k / Cout, 8 - tap);
         }
@@ -129,6 +139,7 @@ __device__ __forceinline__ float pack_gather(const float* __restrict__ w, int mo
     if (mode == 4) return n < 4 * Cout ? sg1_up_weight(w, k, n % Cout, Cout, n / Cout, tap) : 0.f;
     if (mode == 5) return n < Cin ? sg1_up_weight(w, n, k % Cout, Cout, k / Cout, 8 - tap) : 0.f;
     if (mode == 6) return n < Cin ? upt2d_weight(w, k % Cout, n, Cin, k / Cout, tap) : 0.f;
+    if (mode == 7) return n < Cin ? upt2d_unit_weight(w, k, n, Cin, tap) : 0.f;
     return n < Cin ? upfold_weight(w, k % Cout, n, Cin, k / Cout, 8 - tap) : 0.f;
 }
 __global__ void pack_multi_kernel(const DgePackDesc* __restrict__ descs, int nd, long long total_pairs) {
@@ -558,11 +569,11 @@ extern "C" int dge_pack_conv_weight(const float* w_oihw, void* out, int cout, in
     const int frag = mode & 0x100;
     const int mode_full = mode;
     mode &= 0xff;
-    DGE_CHECK(mode >= 0 && mode <= 6 && (mode_full & ~0x1ff) == 0, "pack: bad mode %d", mode_full);
+    DGE_CHECK(mode >= 0 && mode <= 7 && (mode_full & ~0x1ff) == 0, "pack: bad mode %d", mode_full);
     DGE_CHECK((mode != 1 && mode < 3) || ksize == 3, "pack: up fold needs a 3x3 kernel");
     const int nvalid = (mode == 1 || mode == 4) ? 4 * cout : (mode >= 2 ? cin : cout);
     const int ntot = dge_packed_n(nvalid);
-    const int kdim = mode == 2 ? cout : ((mode == 3 || mode == 5 || mode == 6) ? 4 * cout : cin);
+    const int kdim = (mode == 2 || mode == 7) ? cout : ((mode == 3 || mode == 5 || mode == 6) ? 4 * cout : cin);
     DGE_CHECK(!frag || (dtype == DGE_BF16 && ntot % 32 == 0 && kdim % 16 == 0), "pack: fragment order needs bf16, N %% 32 == 0, K %% 16 == 0");
     mode = mode_full;
     const long total = (long)ksize * ksize * ntot * kdim;
@@ -593,11 +604,11 @@ extern "C" int dge_pack_conv_weights_multi(const long long* table_host, void* de
         d.dtype = (int)r[4];
         const unsigned bits = (unsigned)r[5]; memcpy(&d.scale, &bits, 4);
         const int bm = d.mode & 0xff;
-        DGE_CHECK(bm >= 0 && bm <= 6 && (d.mode & ~0x1ff) == 0, "pack_multi: bad mode %d", d.mode);
+        DGE_CHECK(bm >= 0 && bm <= 7 && (d.mode & ~0x1ff) == 0, "pack_multi: bad mode %d", d.mode);
         DGE_CHECK((bm != 1 && bm < 3) || d.ks == 3, "pack_multi: up fold needs a 3x3 kernel");
         const int nvalid = (bm == 1 || bm == 4) ? 4 * d.cout : (bm >= 2 ? d.cin : d.cout);
         d.ntot = dge_packed_n(nvalid);
-        d.kdim = bm == 2 ? d.cout : ((bm == 3 || bm == 5 || bm == 6) ? 4 * d.cout : d.cin);
+        d.kdim = (bm == 2 || bm == 7) ? d.cout : ((bm == 3 || bm == 5 || bm == 6) ? 4 * d.cout : d.cin);
         DGE_CHECK(!(d.mode & 0x100) || (d.dtype == DGE_BF16 && d.ntot % 32 == 0 && d.kdim % 16 == 0),
                   "pack_multi: fragment order needs bf16, N %% 32 == 0, K %% 16 == 0");
         d.pair_start = pairs;

@@ -10,6 +10,7 @@ from ._lib import lib, check, ConvDesc, ConvPPDesc, DgeError, last_kernel
 F32, BF16 = 0, 1
 ACT_NONE, ACT_LRELU, ACT_RELU, LIN_RSQRT = 0, 1, 2, 3
 PACK_FWD, PACK_UPFOLD, PACK_DGRAD, PACK_UPFOLD_DGRAD, PACK_SG1_UP, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD = 0, 1, 2, 3, 4, 5, 6
+PACK_UPT2D_UNITS = 7  # the 9 non-zero (phase, offset) units of PACK_UPT2D_DGRAD, [9, Cin, Cout], in up_dgrad_small's walk order
 PACK_FRAG = 0x100     # OR-ed into a pack mode: MFMA-fragment order for the low-resolution kernel (csrc/conv_small.hip)
 import os as _os
 import weakref as _weakref
@@ -213,8 +214,8 @@ def pack_dims(w, mode):
     """(nvalid, kdim) of the packed copy of w [Cout,Cin,k,k] in pack mode `mode`"""
     cout, cin = _pack_io(w, mode)
     mode &= 0xff
-    nvalid = 4 * cout if mode in (PACK_UPFOLD, PACK_SG1_UP) else (cin if mode in (PACK_DGRAD, PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD) else cout)
-    kdim = cout if mode == PACK_DGRAD else (4 * cout if mode in (PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD) else cin)
+    nvalid = 4 * cout if mode in (PACK_UPFOLD, PACK_SG1_UP) else (cin if mode in (PACK_DGRAD, PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD, PACK_UPT2D_UNITS) else cout)
+    kdim = cout if mode in (PACK_DGRAD, PACK_UPT2D_UNITS) else (4 * cout if mode in (PACK_UPFOLD_DGRAD, PACK_SG1_UP_DGRAD, PACK_UPT2D_DGRAD) else cin)
     return nvalid, kdim
 
 
@@ -1428,6 +1429,66 @@ def up_dgrad_stream(g_z, w_packed, d_in, out_scale, addend, stats, dot_src, prep
             "dge_up_dgrad_stream", 9.0 * cin * cout * H * W * B, (B, H, W, 4 * cout, cin, 3, False, True),
             (g_z, out, addend, dot_src, w_packed))
     if not lazy and partial is not stats:
+        check(lib().dge_sum_slots(_p(partial), _p(stats), nslot, stats.numel(), 1, _stream()), "dge_sum_slots")
+    return out
+
+
+# ------------------------------------------------------------------ data gradient of the low-resolution up layers in phase form
+UP_DGRAD_SMALL_UNITS = ((0, 0), (0, 2), (2, 0), (2, 2), (0, 1), (2, 1), (1, 0), (1, 2), (1, 1))     # (ky, kx) of unit u (walk order)
+
+
+def up_dgrad_small_supported(B, Hin, Win, cin, cout, dtype):
+    """True when the data gradient of an up layer cin -> cout on the Hin x Win input grid runs in phase form on the low-resolution
+    kernel (csrc/conv_small.hip, dge_up_dgrad_small): bf16, cout in {256, 512}, cin % 64 == 0, grid <= 32^2; not in deterministic mode
+    (that mode keeps its launches, as with up_dgrad_stream)."""
+    return (not is_deterministic()) and bool(lib().dge_up_dgrad_small_supported(int(B), int(Hin), int(Win), int(cout), int(cin), int(dtype)))
+
+
+def pack_up_dgrad_small(w, dtype=BF16, scale=1.0):
+    """w: [Cout,Cin,3,3] f32 (the forward layer's parameter) -> the 9 non-zero units of the phase-form adjoint, [9, Cin, Cout] in
+    MFMA-fragment order: unit u = scale * w[:, :, 2-ky, 2-kx]^T with (ky, kx) = UP_DGRAD_SMALL_UNITS[u]."""
+    if dtype != BF16:
+        raise DgeError("pack_up_dgrad_small: bf16 only")
+    return pack_conv_weight(w, PACK_UPT2D_UNITS | PACK_FRAG, dtype, scale)
+
+
+def up_dgrad_small(z_t2d, w_packed, out_scale, addend, stats, dot_src, prep=None):
+    """z_t2d = fir_t2d(g_z, d) [B,H+1,W+1,4*Cout] -> [B,H,W,Cin]: what conv2d(z_t2d, PACK_UPT2D_DGRAD weights, in_t2d=True, out_scale=,
+    addend=, stats=, dot_src=, prep=) computes, as the 9 non-zero units on the low-resolution kernel (dge_up_dgrad_small).
+    w_packed: pack_up_dgrad_small's copy; stats: SlotStats(B, Cin) or a zeroed [B,Cin,2] tensor."""
+    B, H1, W1, C4 = z_t2d.shape
+    H, W, cout = H1 - 1, W1 - 1, C4 // 4
+    cin = w_packed.shape[1]
+    dt = dtype_of(z_t2d)
+    if not getattr(w_packed, "_dge_frag", False) or tuple(w_packed.shape) != (9, cin, cout) or w_packed.dtype != z_t2d.dtype:
+        raise DgeError("up_dgrad_small: w_packed must be pack_up_dgrad_small's copy of this layer's weight")
+    if (dot_src is None) != (stats is None):
+        raise DgeError("up_dgrad_small: stats and dot_src come together")
+    if not up_dgrad_small_supported(B, H, W, cin, cout, dt):
+        raise DgeError(f"up_dgrad_small: unsupported launch {cin} <- {cout} channels on {H}x{W}, dtype {dt}")
+    out = torch.empty((B, H, W, cin), dtype=z_t2d.dtype, device=z_t2d.device)
+    d = ConvDesc()
+    d.in_t2d, d.w_layout, d.ksize = 1, 1, 3
+    d.x, d.w_packed, d.y, d.addend, d.dot_src = _p(z_t2d), _p(w_packed), _p(out), _p(addend), _p(dot_src)
+    d.out_scale = _f32(out_scale)
+    partial, nslot = None, 1
+    lazy = isinstance(stats, SlotStats)
+    if stats is not None:
+        nslot = _stats_slots(B, H, W, 16)
+        partial = stats.alloc(nslot) if lazy else (zeros((nslot,) + tuple(stats.shape), z_t2d.device) if nslot > 1 else stats)
+    d.stats, d.stats_slots = _f32(partial), nslot
+    d.B, d.H, d.W, d.Cin, d.Cout = B, H, W, C4, cin
+    nxt = _PREFETCH.link(_stream().value or 0, w_packed)
+    if nxt is not None:
+        d.prefetch_w, d.prefetch_ntot, d.prefetch_cin = C.c_void_p(nxt[0]), int(nxt[1]), int(nxt[2])
+    if prep is not None:
+        if stats is None:
+            raise DgeError("up_dgrad_small: prep needs stats and dot_src")
+        _set_prep(d, prep, nslot)
+    d.noise_batch, d.act, d.bias_scale, d.gain, d.add_scale, d.dtype = 1, ACT_NONE, 1.0, 1.0, 1.0, dt
+    _launch(lib().dge_up_dgrad_small, (C.byref(d), _stream()), "dge_up_dgrad_small", 9.0 * cin * cout * H * W * B,
+            (B, H, W, C4, cin, 3, False, True), (z_t2d, out, addend, dot_src, w_packed), log=True)
+    if partial is not None and not lazy and partial is not stats:
         check(lib().dge_sum_slots(_p(partial), _p(stats), nslot, stats.numel(), 1, _stream()), "dge_sum_slots")
     return out
 

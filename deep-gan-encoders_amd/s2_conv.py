@@ -11,6 +11,7 @@ UP_FOLDED = os.environ.get("DGE_UP_FOLDED") == "1"
 T2D = not os.environ.get("DGE_NO_T2D")
 PP_DG = not os.environ.get("DGE_NO_PP_DG")
 UP_DG_STREAM = not os.environ.get("DGE_NO_UP_DG_STREAM")      # the 64 <- 32 up layer's data gradient as one streaming launch (csrc/upconv_stream_bwd.hip)
+UP_DG_SMALL = not os.environ.get("DGE_NO_UP_DG_SMALL")        # the 512-channel up layers at <= 32^2: phase-form data gradient on the low-resolution kernel (csrc/conv_small.hip)
 
 
 # ------------------------------------------------------------------ forward
@@ -67,8 +68,9 @@ def _up_phase_form(L):
     """Up layers whose data gradient runs in phase form (FIR^T pass + 4-tap conv on the t grid, dge_fir_t2d / in_t2d: 16 tap-units
     per input pixel instead of the 36 of the folded space-to-depth form): the MFMA-bound ones, 32^2 .. 128^2 input (measured at
     batch 8, tools/perf_t2d.py, folded -> FIR pass + conv: 512->512 @32^2 221 -> 174 us, 256<-512 @64^2 310 -> 243, 128<-256 @128^2
-    344 -> 313; at 256^2 / 512^2 the launch is bound by its epilogue and the extra pass loses: 430 -> 504, 951 -> 1223).  The small
-    grids stay on the folded form (low-resolution kernel)."""
+    344 -> 313; at 256^2 / 512^2 the launch is bound by its epilogue and the extra pass loses: 430 -> 504, 951 -> 1223).  On
+    conv2d the small grids stay on the folded form; in fused bf16 mode the 256 / 512-channel layers up to 32^2 take the phase form
+    of the low-resolution kernel instead (_up_small_dgrad, checked first)."""
     return L.up and 32 <= L.res // 2 <= 128 and L.in_c >= 64 and L.in_c % 32 == 0 and L.out_c % 8 == 0 and T2D
 
 
@@ -112,6 +114,17 @@ def _dgrad_weight_stream(L, dtype):
     return c if c is not None else store(L._cache, ("dgs", dtype), L.weight, ops.pack_up_dgrad_stream(L.weight, dtype, L.wscale))
 
 
+def _up_small_dgrad(L, B, dtype, fused):
+    """the data gradient of this up layer runs in phase form on the low-resolution kernel (ops.up_dgrad_small after ops.fir_t2d: 256 /
+    512 channels on a grid <= 32^2, bf16; fused mode only - deterministic mode and f32 keep their launches)"""
+    return UP_DG_SMALL and fused and L.up and L.ksize == 3 and ops.up_dgrad_small_supported(B, L.res // 2, L.res // 2, L.in_c, L.out_c, dtype)
+
+
+def _dgrad_weight_small(L, dtype):
+    c = lookup(L._cache, ("dgu", dtype), L.weight)
+    return c if c is not None else store(L._cache, ("dgu", dtype), L.weight, ops.pack_up_dgrad_small(L.weight, dtype, L.wscale))
+
+
 def dgrad_takes_prep(L, B=None, dtype=None):
     """True when the data-gradient launch of L may carry the tail backward of the layer below in its epilogue (`prep`)
     (the space-to-depth data gradient of a narrow up layer - layer 15: 64 -> 32 channels - loses more in its 64-wide conv_igemm tile
@@ -131,6 +144,10 @@ def dgrad(L, g_y, d_in, dt, fused, prep=None, **epilogue):
         # narrow up layer (64 <- 32): FIR^T, the 9-tap adjoint on the t grid and the epilogue in one streaming pass
         return ops.up_dgrad_stream(g_y, _dgrad_weight_stream(L, dt), d_in, epilogue.get("out_scale"), epilogue.get("addend"),
                                    epilogue.get("stats"), epilogue["dot_src"], prep=prep)
+    if L.up and _up_small_dgrad(L, B, dt, fused) and set(epilogue) <= {"out_scale", "addend", "stats", "dot_src"}:
+        # low-resolution up layers (512 <- 512 at 4^2 .. 32^2): FIR^T to the t grid, then the 9 non-zero units on the low-resolution kernel
+        return ops.up_dgrad_small(ops.fir_t2d(g_y, d_in), _dgrad_weight_small(L, dt), epilogue.get("out_scale"), epilogue.get("addend"),
+                                  epilogue.get("stats"), epilogue.get("dot_src"), prep=prep)
     t2d = _up_phase_form(L)
     if fused and d_in is not None and not t2d and _pp_dgrad(L, B, hg, dt):
         # MFMA-bound launches on the ping-pong kernel (csrc/conv_pp.hip): the demodulation factor is folded into a per-sample

@@ -39,6 +39,7 @@ typedef struct ihipStream_t* dge_stream_t;   /* == hipStream_t */
 #define DGE_PACK_SG1_UP 4    /* w is [Cin][Cout][3][3] (ConvTranspose2d 3,s2,p1 + transform_kernel, lreq.py:129-131) -> [tap][4*Cout][Cin] */
 #define DGE_PACK_SG1_UP_DGRAD 5 /* same parameter layout -> [tap][Cin][4*Cout]: adjoint of DGE_PACK_SG1_UP */
 #define DGE_PACK_UPT2D_DGRAD 6 /* [tap][Cin][4*Cout]: adjoint of the up layer in phase form, read from dge_fir_t2d output (dge_conv_desc.in_t2d) */
+#define DGE_PACK_UPT2D_UNITS 7 /* [unit][Cin][Cout]: the 9 non-zero (phase, offset) units of DGE_PACK_UPT2D_DGRAD in the walk order of dge_up_dgrad_small: (ky,kx) = (0,0) (0,2) (2,0) (2,2) (0,1) (2,1) (1,0) (1,2) (1,1), value w[o][i][2-ky][2-kx] */
 
 const char* dge_last_error(void);
 int dge_version(void);
@@ -534,6 +535,15 @@ int dge_up_dgrad_stream(const void* g_z, const void* w_packed, void* y, const fl
                         const void* addend, const void* dot_src, float* stats, int stats_slots, int prep, float prep_gain,
                         const float* prep_noise, int prep_noise_bstride, const float* prep_ns, float* prep_stats,
                         int B, int H, int W, int Cin, int Cout, int dtype, dge_stream_t stream);
+
+/* ---- Data gradient of the LOW-RESOLUTION up layers in phase form on the low-resolution kernel (csrc/conv_small.hip; bf16, 256 / 512
+ * channels in, a multiple of 64 out).  `d` describes the launch as for dge_conv2d with in_t2d = 1 - x = dge_fir_t2d's
+ * [B,H+1,W+1,Cin], Cin = 4 * C (C = the forward layer's out channels), Cout = N (its in channels), epilogue fields out_scale /
+ * addend / dot_src + stats / prep, prefetch_* - except that w_packed holds the 9 non-zero (phase, offset) units, [9][N][C] from
+ * dge_pack_conv_weight mode DGE_PACK_UPT2D_UNITS | DGE_PACK_FRAG, and w_layout = 1.  Only those 9 K = C GEMMs run (dge_conv2d's
+ * in_t2d form runs 16).  dge_up_dgrad_small_supported: H, W = the up layer's input grid. */
+int dge_up_dgrad_small_supported(int B, int H, int W, int C, int N, int dtype);
+int dge_up_dgrad_small(const dge_conv_desc* d, dge_stream_t stream);
 
 /* ---- The same up layer as a ping-pong implicit GEMM for the MFMA-bound layers (csrc/up_pp.hip; Cin >= 128: layers 7 / 9 / 11 / 13
  * of the 1024^2 generator).  stylegan2_generator.py:879-896 conv_transpose2d + FIR in the reference's FUSED-modulation form
