@@ -209,6 +209,8 @@ SIGNATURES = {
     "dge_latent_pnorm_rows_bwd": [_P, _P, _P, _P, _I, C.c_long, _I, _F, _P],
     "dge_embed_track_rows": [_P, _P, _P, _I, C.c_long, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P],
     "dge_mapping_bwd": [_P, _I, C.POINTER(DenseLayer), _I, _P, _P, _I, _P, _P, _I, _I, _I, _F, _P],
+    "dge_mapping_bwd_wide_work_bytes": [_I],
+    "dge_mapping_bwd_wide": [_P, _I, C.POINTER(DenseLayer), _I, _P, _P, _I, _P, _P, _I, _I, _I, _F, _P, C.c_longlong, _P],
     "dge_quantize_u8": [_P, _I, _P, _I, _I, _I, _I, _P],
     "dge_image_metrics_u8_work_bytes": [_I, _I, _I],
     "dge_image_metrics_u8": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],

@@ -4,6 +4,7 @@ HIP path, for StyleGAN1 (`--mtype 1`: Gs + E_Blur) and StyleGAN2 (`--mtype 2`: S
 
   mode "E" (--optimizeE true):  the encoder is re-loaded per image group and fine-tuned; w1 = E(imgs1) every iteration.
   mode "W" (--optimizeE false): the encoder is frozen and the W+ code w1 itself is optimised (LREQAdam on the leaf w1).
+  mode "Z" (--optimizeE false --space z): the encoder is frozen and z [B, 512] in front of the mapping network is optimised.
 
 Per iteration (both generators):
 
@@ -31,7 +32,7 @@ Decisions where the reference cannot run as written:
   * W mode takes a batch B >= 1 (the reference hard-codes 1); the norm and space_loss terms couple the rows as in the reference.
     StyleGAN2's W-mode start is randn(B, L, 512) from a seeded generator (unseeded in the reference).
   * --optimizeE parses true / false strictly (the reference's `type=bool` cannot be switched off).
-  * `independent` (--independent true; W mode only): the B rows of a group are B inversions of their own, each equal to the
+  * `independent` (--independent true; W mode, and Z mode below): the B rows of a group are B inversions of their own, each equal to the
     batch-1 run of its image.  Every loss and logged value of row b is what the coupled code returns on the one-row slices
     (losses.image_loss_tsa_rows / space_loss_rows, ||w1[b]||_p); phase 1 back-propagates sum_b loss_msiv_b, phase 2
     sum_b (0.01*lat_b + beta*||w1[b]||_p), so row b of w1.grad is the gradient of row b's own loss and Adam (element-wise) gives
@@ -48,6 +49,31 @@ Decisions where the reference cannot run as written:
 Generator kind "pg" (embedding_v2_pggan.PGEmbedStep: PGGAN + E_PG) runs the same iteration on z [B, z_space_dim] through three
 hooks - _latent_shape, _encode (E_PG has no const output: const2 / const3 / loss_c1 are None) and _generate - in StyleGAN1's
 order and with its defaults and tracker rules; "sg1" and "sg2" issue the launches they issued before.
+
+Mode "Z" (StyleGAN1 and StyleGAN2; the baseline every W+ result is compared against, and the only code that stays on the
+generator's sampling distribution).  The reference has no v2 Z-space script (its Z-space baseline is
+baseline_utils/image2stylegan_w2z_opW.py): this is the v2 loop with the latent moved in front of the mapping network, as
+embedding_v2_pggan is for PGGAN.  Per iteration:
+
+    wp = trunc(map(z));  imgs2 = G(wp)
+    phase 1 as above (zero_grad; loss_msiv.backward(retain_graph=True); step on z)
+    w2 = E(imgs2) at the point the generator kind evaluates it above
+    wp' = trunc(map(z)) from the updated z (nine small launches): the Z-mode counterpart of W mode's in-place leaf
+    loss_msLv = 0.01*(space_loss(wp', w2) [+ space_loss(const2, const3), StyleGAN1]) + beta*||z||_p;  zero_grad; backward; step
+
+  * the norm penalty is on z (the optimised leaf, as ||w1||_p is in W mode); the encoder stays the frozen W+ regulariser: it is
+    compared with wp', never with z.
+  * StyleGAN2: psi = `truncation` (default 0.7) on every row of wp - the reading of the wrapper W mode uses; 1 skips it.
+    StyleGAN1: Gm(z, coefs) with the scripts' coefficients (0.7 on the first half of the rows) when Gm carries the truncation
+    centre (center_tensor.pt), the plain broadcast otherwise; const2 = E(imgs1)'s const output, a constant as in W mode.
+  * start code: `w_init` taken as z, else seeded randn with W mode's StyleGAN2 seeds (seed + group; seed + g*B + b per row).
+  * the mapping adjoint runs three times per iteration: in phase 1, and in phase 2 through the old graph (w2 -> imgs2 -> wp) and
+    through wp'.  The pixel-norm adjoint of the old graph reads the updated z (the leaf's storage), as the reference's autograd
+    does after a `p.data` update; the dense layers read the outputs they saved.  StyleGAN2's adjoint is dge_mapping_bwd or
+    dge_mapping_bwd_wide by batch size (MAPPING_BWD_WIDE_MIN_BATCH, from the measurement in the README); StyleGAN1's
+    MappingFunction keeps dge_mapping_bwd.
+  * the tracker follows z; `independent` works as in W mode (the mapping is per-sample already); files are the W-mode set with the
+    z row in models/id*-i*-z*.pt and models/z_all_*.pt [N, 512].
 
 The file side of a group (dump_group, loss_txt_block, finish_group) and the group walk of main() (invert_folder, rows_plan) serve
 embedding_v2_biggan too: its dumps differ in the two file-name patterns and in the Loss.txt block, its walk in labels and
@@ -72,6 +98,9 @@ DEFAULTS = {
     2: dict(iterations=2001, lr=0.005, beta_1=0.0, beta=3e-4, norm_p=2, truncation=0.7),
 }
 IMG_WEIGHTS = (1.0, 0.125 * 3, 0.125 * 5)
+# mode "Z", StyleGAN2: smallest batch at which the mapping adjoint goes through dge_mapping_bwd_wide (None: never) - set from the
+# measurement in the README section "Z-space inversion": the wide form is faster at every measured batch (1, 2, 4, 8)
+MAPPING_BWD_WIDE_MIN_BATCH = 1
 
 
 class _PNorm(torch.autograd.Function):
@@ -123,14 +152,22 @@ class LatentEmbedStep(GraphReplay):
     fused_backward = True          # "pg": the generator backward with ops.pixelnorm_act_bwd (False: the composed launches, for timing)
 
     def __init__(self, G, E, lpips_model, mode="E", generator="sg2", lr=0.005, beta_1=0.0, beta=None, norm_p=2, truncation=None,
-                 iterations=None, arm_iter=None, events_cap=256, seed=0, independent=False):
-        if mode not in ("E", "W"):
-            raise ValueError(f"mode must be 'E' or 'W', got {mode!r}")
-        if independent and mode != "W":
-            raise ValueError("independent=True needs mode 'W': in mode 'E' one encoder is shared by the rows of a group")
+                 iterations=None, arm_iter=None, events_cap=256, seed=0, independent=False, Gm=None, mapping_bwd="auto"):
+        if mode not in ("E", "W", "Z"):
+            raise ValueError(f"mode must be 'E', 'W' or 'Z', got {mode!r}")
+        if independent and mode == "E":
+            raise ValueError("independent=True needs mode 'W' or 'Z': in mode 'E' one encoder is shared by the rows of a group")
         self.independent = bool(independent)
         if generator not in ("sg1", "sg2", "pg"):
             raise ValueError(f"generator must be 'sg1', 'sg2' or 'pg', got {generator!r}")
+        if mode == "Z":
+            if generator == "pg":
+                raise ValueError("mode 'Z' is for StyleGAN1 / StyleGAN2: PGGAN's latent is z already (embedding_v2_pggan)")
+            if generator == "sg1" and Gm is None:
+                raise ValueError("mode 'Z' with generator 'sg1' needs the mapping network: pass Gm=stylegan1.Mapping")
+            if mapping_bwd not in ("auto", "one", "wide"):
+                raise ValueError(f"mapping_bwd must be 'auto', 'one' or 'wide', got {mapping_bwd!r}")
+        self.Gm, self.mapping_bwd = Gm, mapping_bwd
         d = DEFAULTS[2 if generator == "sg2" else 1]          # "pg" (embedding_v2_pggan): StyleGAN1's defaults, rules and order
         self.G, self.E, self.lpips = G, E, lpips_model
         self.mode, self.generator = mode, generator
@@ -148,6 +185,11 @@ class LatentEmbedStep(GraphReplay):
         self.last = {}
         self.w1 = self._const2 = None
         self._tracker = EmbedTracker(self.rules, self.events_cap, rows=self.independent)
+        if mode == "Z" and generator == "sg1":
+            # the scripts' coefficients (embedding_v2_styleGAN1.py: 0.7 on the first half of the rows); without a centre Mapping
+            # takes the plain broadcast whatever they are
+            n = self._num_rows()
+            self._coefs_m = torch.where(torch.arange(n).view(1, n, 1) < n // 2, 0.7, 1.0).float()
         if mode == "E":
             self.opt = LREQAdam([{"params": E.parameters()}], lr=lr, betas=(beta_1, 0.99), weight_decay=0)
             self._ckpt = {k: v.detach().clone() for k, v in E.state_dict().items()}
@@ -163,6 +205,8 @@ class LatentEmbedStep(GraphReplay):
 
     def _latent_shape(self, B):
         """Shape of the latent w1: the W+ code [B, rows, 512]; "pg": z [B, z_space_dim]."""
+        if self.mode == "Z":
+            return (B, 512)
         return (B, self.G.z_space_dim) if self.generator == "pg" else (B, self._num_rows(), 512)
 
     def _encode(self, imgs, noises):
@@ -187,8 +231,23 @@ class LatentEmbedStep(GraphReplay):
             self._reset_opt()
         else:
             with torch.no_grad():
+                if self.mode == "Z" and self.generator == "sg1":          # const2 of the const term, a constant as in W mode
+                    c0 = self.E(imgs1, noises=noises)[0]
+                    if self._const2 is None or self._const2.shape != c0.shape:
+                        self._const2 = torch.empty_like(c0)
+                    self._const2.copy_(c0)
+                if self.mode == "Z" and self.generator == "sg2":
+                    wide = {"one": False, "wide": True}.get(self.mapping_bwd)
+                    if wide is None:
+                        wide = MAPPING_BWD_WIDE_MIN_BATCH is not None and B >= MAPPING_BWD_WIDE_MIN_BATCH
+                    self.G.mapping.wide_bwd = wide
                 if w_init is not None:
                     w0 = w_init.to(dev, torch.float32).reshape(shape)
+                elif self.mode == "Z" and not self.independent:
+                    w0 = torch.randn(shape, generator=torch.Generator().manual_seed(int(self.seed) + self.group))
+                elif self.mode == "Z":
+                    w0 = torch.cat([torch.randn((1,) + shape[1:], generator=torch.Generator().manual_seed(int(self.seed) + self.group * B + r))
+                                    for r in range(B)])
                 elif self.generator == "pg":
                     w0 = self._encode(imgs1, noises)[1]
                 elif self.generator == "sg1":
@@ -222,6 +281,19 @@ class LatentEmbedStep(GraphReplay):
         wt = w1 if self.psi == 1.0 else _WplusLerp.apply(w1, self.G.truncation.w_avg, self.psi)
         return syn(wt, randomize_noise=False)["image"]
 
+    def _wp_of(self, z):
+        """Mode "Z": wp = trunc(map(z)), differentiable w.r.t. z (StyleGAN2: dge_pixelnorm, eight dge_linear, dge_truncation)."""
+        if self.generator == "sg1":
+            return self.Gm(z, coefs_m=self._coefs_m)
+        G = self.G
+        return G.truncation(G.mapping(z)["w"], self.psi, G.num_layers)
+
+    def _synthesise(self, wp, noises):
+        """Mode "Z": imgs2 = G(wp), wp already truncated."""
+        if self.generator == "sg1":
+            return self.G.forward(wp, self.lod, noises=noises)
+        return self.G.synthesis(wp, randomize_noise=False)["image"]
+
     def step(self, imgs1, noises=(None, None, None)):
         """One iteration; `noises` = optional (E(imgs1), G, E(imgs2)) noise lists for parity runs (StyleGAN2: G's is unused, the
         synthesis noise is its fixed buffers; W mode: E(imgs1)'s is unused).  Independent mode: the loss entries of the result
@@ -234,7 +306,9 @@ class LatentEmbedStep(GraphReplay):
             const2, w1 = self._encode(imgs1, noises[0])
         else:
             w1, const2 = self.w1, self._const2
-        imgs2 = self._generate(w1, noises[1])
+        zmode = self.mode == "Z"
+        wp = self._wp_of(w1) if zmode else None
+        imgs2 = self._synthesise(wp, noises[1]) if zmode else self._generate(w1, noises[1])
         if self.generator != "sg2":
             const3, w2 = self._encode(imgs2, noises[2])
         image_loss, latent_loss = (losses.image_loss_tsa_rows, losses.space_loss_rows) if rows else (losses.image_loss_tsa, losses.space_loss)
@@ -244,7 +318,8 @@ class LatentEmbedStep(GraphReplay):
         self.opt.step()
         if self.generator == "sg2":
             const3, w2 = self._encode(imgs2, noises[2])
-        loss_w, info_w = latent_loss(w1, w2, image_space=False)
+        wp_new = self._wp_of(w1) if zmode else None          # the direct term of phase 2 sees the updated code
+        loss_w, info_w = latent_loss(wp_new if zmode else w1, w2, image_space=False)
         lat = loss_w
         loss_c1 = None
         if const2 is not None:
@@ -269,6 +344,8 @@ class LatentEmbedStep(GraphReplay):
                          const3=const3.detach() if const3 is not None else None, loss_msiv=loss_msiv.detach(), info_img=info_img,
                          loss_w=loss_w.detach(), info_w=info_w, loss_c1=loss_c1.detach() if loss_c1 is not None else None, norm=nrm.detach(), loss_mslv=loss_mslv.detach(),
                          w_norm=self._tracker.l2)
+        if zmode:
+            self.last.update(wp=wp.detach(), wp_new=wp_new.detach())
         return self.last
 
     # ------------------------------------------------------------------ hipGraph replay of the iteration
@@ -331,6 +408,7 @@ def rows_plan(n_images, batch_size, labels=None):
 
 # ------------------------------------------------------------------ files of a group (shared with embedding_v2_biggan)
 IMG_NAME, W_NAME = "id{n}_ep{i}-norm{norm:.2f}-imgLoss{loss:f}.jpg", "id{n}-i{k}-w{i}-norm{norm:f}-imgLoss{loss:f}.pt"
+Z_NAME = "id{n}-i{k}-z{i}-norm{norm:f}-imgLoss{loss:f}.pt"          # mode "Z": the saved latent is the z row
 LOSS_TXT_IMAGE = (("info_mask", "loss_small_info"), ("info_Gcam", "loss_medium_info"), ("info_imgs", "loss_imgs_info"))
 LOSS_TXT_LATENT = (("info_w", "loss_w_info"), ("info_c2", "loss_c2_info"))
 
@@ -351,12 +429,15 @@ def loss_txt_block(f, num, i, infos, loss):
     print("Img_loss: %s" % loss, file=f)
 
 
-def dump_group(st, imgs1, r, i, out_dir, group, keep=None, img_name=IMG_NAME, w_name=W_NAME, loss_txt=False):
+def dump_group(st, imgs1, r, i, out_dir, group, keep=None, img_name=IMG_NAME, w_name=None, loss_txt=False):
     """The every-`save_every` dump of iteration i (norm and loss of all rows in one host read): the image pair and one w1 file per
     row; `loss_txt`: a Loss.txt block too.  Coupled form: one pair and one block for the group, named by `group`.  Independent
     form: a pair, a block and a w1 file for each of the first `keep` rows (default: all), named by the image number group * B + b,
-    with that row's norm and loss.  `img_name` / `w_name`: format patterns of n (number), i, k (row of the file set), norm, loss."""
+    with that row's norm and loss.  `img_name` / `w_name`: format patterns of n (number), i, k (row of the file set), norm, loss
+    (`w_name` None: W_NAME, Z_NAME for a step in mode "Z")."""
     from .infer import save_image_grid
+    if w_name is None:
+        w_name = Z_NAME if getattr(st, "mode", None) == "Z" else W_NAME
     B = imgs1.shape[0]
     vals = torch.stack((r["w_norm"], r["loss_msiv"])).reshape(2, -1).cpu()
     infos = {k: r[k].cpu() for k, _ in LOSS_TXT_IMAGE + LOSS_TXT_LATENT if k in r} if loss_txt else {}
@@ -388,11 +469,11 @@ def finish_group(st, r, B, out_dir, group, keep=None):
     return dict(r, tracker=tr)
 
 
-def invert_folder(invert, imgs, bs, independent, out, labels=None, save_imgs=False):
+def invert_folder(invert, imgs, bs, independent, out, labels=None, save_imgs=False, all_name="w_all_%d.pt"):
     """The group walk of the CLIs: `invert(imgs1, group=g, **kw)` runs one group.  Coupled: the n // bs full groups, one line, one
     `summaries/<g>_rec.png` and w1[0] per group, models/w_all_<groups-1>.pt.  Independent: every image (rows_plan), a line and a w1
     per kept row, models/w_all_<n-1>.pt; `labels` (one class id per image) go to `invert` row by row.  `save_imgs`: the kept
-    reconstructions too, as models/img_all_*.pt."""
+    reconstructions too, as models/img_all_*.pt.  `all_name`: the pattern of the stacked latents' file (mode "Z": z_all_%d.pt)."""
     from .infer import save_image_grid
     n = imgs.shape[0]
     plan = rows_plan(n, bs, labels) if independent else [(g * bs, bs, list(range(g * bs, (g + 1) * bs)), None) for g in range(n // bs)]
@@ -410,7 +491,7 @@ def invert_folder(invert, imgs, bs, independent, out, labels=None, save_imgs=Fal
                 img_all.append(r["imgs2"][b].clone().cpu())
         save_image_grid(r["imgs2"][:keep], os.path.join(out, "summaries", "%s_rec.png" % str(g).rjust(5, "0")), nrow=bs)
     if w_all:
-        torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", "w_all_%d.pt" % (len(w_all) - 1)))
+        torch.save(torch.stack(w_all, dim=0), os.path.join(out, "models", all_name % (len(w_all) - 1)))
         if save_imgs:
             torch.save(torch.stack(img_all, dim=0), os.path.join(out, "models", "img_all_%d.pt" % (len(w_all) - 1)))
 
@@ -476,9 +557,23 @@ def build_models_v2(mtype, img_size=1024, start_features=16, compute_dtype="bf16
     return G, E, LP
 
 
-def load_checkpoints(G, E, mtype, gan=None, enc=None):
+def build_mapping_sg1(G, device="cuda", seed=0):
+    """Mode "Z", mtype 1: the StyleGAN1 mapping network for the synthesis `G` (frozen, seeded random-init, no truncation centre)."""
+    from .stylegan1 import Mapping
+    torch.manual_seed(seed + 1)
+    Gm = Mapping(num_layers=2 * G.layer_count, mapping_layers=8, latent_size=512, dlatent_size=512, mapping_fmaps=512).to(device)
+    for p in Gm.parameters():
+        p.requires_grad_(False)
+    return Gm
+
+
+def load_checkpoints(G, E, mtype, gan=None, enc=None, Gm=None):
     """The checkpoint containers of models.load_models: mtype 2 a dict holding `generator_smooth` (or `generator`), mtype 1 a
-    directory with Gs_dict.pth; the encoder a bare state_dict."""
+    directory with Gs_dict.pth (and, for `Gm`, Gm_dict.pth and - optional - center_tensor.pt); the encoder a bare state_dict."""
+    if gan and Gm is not None:
+        Gm.load_state_dict(torch.load(gan + "Gm_dict.pth", map_location="cpu"))
+        if os.path.exists(gan + "center_tensor.pt"):
+            Gm.buffer1 = torch.load(gan + "center_tensor.pt", map_location="cpu")
     if gan:
         if mtype == 2:
             ckpt = torch.load(gan, map_location="cpu")
@@ -510,6 +605,8 @@ def make_parser():
     p.set_defaults(mtype=1)
     p.add_argument("--img_dir", default="./real_imgs/", help="a directory of images or a .pt tensor in [0,1]")
     p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise W+ directly")
+    p.add_argument("--space", choices=("w", "z"), default="w",
+                   help="with --optimizeE false: optimise the W+ code (w) or z in front of the mapping network (z; --mtype 1 or 2)")
     p.add_argument("--independent", type=strict_bool, default=False,
                    help="true (with --optimizeE false): every image of a batch is an inversion of its own, equal to its batch-1 run")
     p.add_argument("--encoder", choices=ENCODERS, default="blur",
@@ -530,6 +627,13 @@ def make_parser():
 def parse_args(argv=None):
     """Parsed flags with the per-`--mtype` defaults filled in."""
     args = make_parser().parse_args(argv)
+    if args.space == "z":
+        if args.optimizeE:
+            raise SystemExit("embedding_v2: --space z needs --optimizeE false (z is optimised against the frozen encoder)")
+        if args.mtype not in (1, 2):
+            raise SystemExit("embedding_v2: --space z is for --mtype 1 (StyleGAN1) or 2 (StyleGAN2); PGGAN and BigGAN optimise z already")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("embedding_v2: --space z runs in one process (WORLD_SIZE > 1 is not supported)")
     if args.mtype not in DEFAULTS:
         raise SystemExit("embedding_v2: --mtype must be 1 (StyleGAN1) or 2 (StyleGAN2)")
     if args.independent and args.optimizeE:
@@ -555,17 +659,19 @@ def main(argv=None):
     dev = "cuda"
     G, E, LP = build_models_v2(args.mtype, args.img_size, args.start_features, args.compute_dtype, device=dev, seed=args.seed,
                                fmaps_base=args.fmaps_base, fmaps_max=args.fmaps_max, enc_maxf=args.enc_maxf, encoder=args.encoder)
-    load_checkpoints(G, E, args.mtype, args.checkpoint_dir_GAN, args.checkpoint_dir_E)
+    zspace = args.space == "z"
+    Gm = build_mapping_sg1(G, dev, args.seed) if zspace and args.mtype == 1 else None
+    load_checkpoints(G, E, args.mtype, args.checkpoint_dir_GAN, args.checkpoint_dir_E, Gm=Gm)
     load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
     out = args.experiment_dir or "./realimg_embedding_result/7"
     for sub in ("", "imgs", "models", "summaries"):
         os.makedirs(os.path.join(out, sub), exist_ok=True)
     imgs = _load_imgs(args.img_dir, args.img_size, dev)
-    st = LatentEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", generator="sg1" if args.mtype == 1 else "sg2", lr=args.lr,
+    st = LatentEmbedStep(G, E, LP, mode="E" if args.optimizeE else ("Z" if zspace else "W"), Gm=Gm, generator="sg1" if args.mtype == 1 else "sg2", lr=args.lr,
                          beta_1=args.beta_1, beta=args.beta, norm_p=args.norm_p, truncation=args.truncation,
                          iterations=args.iterations, seed=args.seed, independent=args.independent)
     invert_folder(lambda imgs1, **kw: invert_v2(st, imgs1, args.iterations, launch=args.launch, save_every=args.save_every, out_dir=out, **kw),
-                  imgs, args.batch_size, args.independent, out)
+                  imgs, args.batch_size, args.independent, out, all_name="z_all_%d.pt" if zspace else "w_all_%d.pt")
     return st
 
 

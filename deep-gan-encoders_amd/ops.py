@@ -311,10 +311,21 @@ def _dense_layers(layers):
     return arr
 
 
-def mapping_bwd(z, layers, g, coefs=None, acts=None, pixelnorm=True, eps=1e-8):
+def mapping_bwd_work_bytes(B):
+    """Bytes of the workspace dge_mapping_bwd_wide needs for B samples."""
+    n = lib().dge_mapping_bwd_wide_work_bytes(int(B))
+    if n < 0:
+        check(n, "dge_mapping_bwd_wide_work_bytes")
+    return n
+
+
+def mapping_bwd(z, layers, g, coefs=None, acts=None, pixelnorm=True, eps=1e-8, wide=False, work=None, out=None):
     """Data gradient of w+ = lerp(avg, broadcast_L(chain(z)), coefs) in one launch (dge_mapping_bwd): z [B, I] f32, g = dL/dw+
     [B, L, O] f32, coefs [L] f32 or None (plain broadcast), acts: the forward's layer outputs ([B, O_l] each; the leaky-relu masks
-    are read off them) or None (the launch recomputes the forward) -> dz [B, I].  The same bits every run."""
+    are read off them) or None (the launch recomputes the forward) -> dz [B, I].  The same bits every run.
+    wide=True: dge_mapping_bwd_wide, one chip-wide launch per layer and a tail (acts required; `work`: a uint8 workspace of
+    mapping_bwd_work_bytes(B) bytes, allocated when None); row b has the bits of the row run alone.  `out`: dz goes into this
+    [B, I] f32 tensor (unit inner stride, any row stride)."""
     B, L = g.shape[0], g.shape[1]
     if not z.is_cuda or z.stride(1) != 1:
         raise DgeError("mapping_bwd: z must be a CUDA tensor with unit inner stride")
@@ -331,9 +342,31 @@ def mapping_bwd(z, layers, g, coefs=None, acts=None, pixelnorm=True, eps=1e-8):
             raise DgeError("mapping_bwd: acts must hold one [B, O_l] output per layer")
         arr = (C.c_void_p * len(acts))(*[_f32(a).value for a in acts])
         arr_p = C.cast(arr, C.c_void_p)
-    dz = torch.empty((B, z.shape[1]), dtype=torch.float32, device=z.device)
+    if out is None:
+        dz = torch.empty((B, z.shape[1]), dtype=torch.float32, device=z.device)
+    else:
+        dz = out
+        if not dz.is_cuda or dz.dtype != torch.float32 or tuple(dz.shape) != (B, z.shape[1]) or dz.stride(1) != 1:
+            raise DgeError("mapping_bwd: out must be a [B, I] f32 CUDA tensor with unit inner stride")
+    coefs_p = _f32(None if coefs is None else coefs.contiguous())
+    if wide:
+        if acts is None:
+            raise DgeError("mapping_bwd: wide=True needs the saved layer outputs (acts); the recompute form is the one-launch kernel's")
+        need = mapping_bwd_work_bytes(B)
+        if work is None:
+            work = torch.empty(need, dtype=torch.uint8, device=z.device)
+        elif not work.is_cuda or work.dtype != torch.uint8 or not work.is_contiguous() or work.numel() < need:
+            raise DgeError(f"mapping_bwd: work must be a contiguous uint8 CUDA tensor of at least {need} bytes")
+        if z.dtype != torch.float32:
+            raise DgeError(f"expected float32, got {z.dtype}")
+        # (z and dz by address: rows of any stride)
+        check(lib().dge_mapping_bwd_wide(C.c_void_p(z.data_ptr()), z.stride(0), _dense_layers(layers), len(layers), arr_p, _p(g), L, coefs_p,
+                                         C.c_void_p(dz.data_ptr()), dz.stride(0), B, 1 if pixelnorm else 0, float(eps), _p(work), work.numel(), _stream()),
+              "dge_mapping_bwd_wide")
+        _log_dense("dge_mapping_bwd_wide")
+        return dz
     check(lib().dge_mapping_bwd(_f32(z), z.stride(0), _dense_layers(layers), len(layers), arr_p, _p(g), L,
-                                _f32(None if coefs is None else coefs.contiguous()), _p(dz), dz.stride(0), B, 1 if pixelnorm else 0,
+                                coefs_p, _p(dz), dz.stride(0), B, 1 if pixelnorm else 0,
                                 float(eps), _stream()), "dge_mapping_bwd")
     return dz
 

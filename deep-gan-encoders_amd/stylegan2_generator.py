@@ -9,6 +9,7 @@ arguments, forward signatures, returned dict keys and state_dict keys (165 keys 
   modulated 3x3 conv    -> dge_conv2d           (:855-922; up layers :879-896 folded, see csrc)
   toRGB + skip upsample -> dge_torgb            (:465-474, :515-522, :603-615)
   mapping / truncation  -> dge_pixelnorm, dge_linear, dge_truncation (:246-278, :311-333)
+  d/dz of both          -> dge_mapping_bwd / dge_mapping_bwd_wide (one call: pixel-norm adjoint, transposed chain, truncation sum)
 
 Activations are NHWC in `compute_dtype` ('bf16': bf16 storage + f32 MFMA accumulation; 'f32':
 exact-f32 MFMA, the parity path).  Images and latents stay NCHW / row-major f32 like the
@@ -63,8 +64,44 @@ class DenseBlock(nn.Module):
                           self.gain, out=out)
 
 
+class _MappingFunction(torch.autograd.Function):
+    """w = mapping(z) from layer outputs the forward already computed; dz from dge_mapping_bwd (one row, no coefficients).  No
+    mapping weight gradient is formed: the omission of stylegan1.MappingFunction, for its reason (no optimizer reads it)."""
+
+    @staticmethod
+    def forward(ctx, z, M, z32, acts):
+        ctx.M, ctx.z32, ctx.acts, ctx.z_dtype = M, z32, acts, z.dtype
+        return acts[-1].view_as(acts[-1])
+
+    @staticmethod
+    def backward(ctx, g):
+        dz = ops.mapping_bwd(ctx.z32, ctx.M.layers(), g.unsqueeze(1), coefs=None, acts=ctx.acts, wide=ctx.M.wide_bwd)
+        return dz.to(ctx.z_dtype), None, None, None
+
+
+class _MappingTruncFunction(torch.autograd.Function):
+    """wp = truncation(mapping(z)) from the w the mapping forward computed (one dge_truncation launch); dz from one dge_mapping_bwd
+    call: the pixel-norm adjoint, the transposed chain and sum_l coefs[l] * g[b, l, :], coefs[l] = psi below `layers`, else 1."""
+
+    @staticmethod
+    def forward(ctx, z, M, z32, acts, T, psi, layers):
+        ctx.M, ctx.z32, ctx.acts, ctx.z_dtype = M, z32, acts, z.dtype
+        ctx.coefs = T.coefs(psi, layers, z32.device)
+        return ops.truncation(acts[-1], T.w_avg, T.num_layers, psi, layers)
+
+    @staticmethod
+    def backward(ctx, g):
+        dz = ops.mapping_bwd(ctx.z32, ctx.M.layers(), g, coefs=ctx.coefs, acts=ctx.acts, wide=ctx.M.wide_bwd)
+        return (dz.to(ctx.z_dtype),) + (None,) * 6
+
+
 class MappingModule(nn.Module):
-    """z -> w: pixel norm + 8 dense layers (reference :199-278)."""
+    """z -> w: pixel norm + 8 dense layers (reference :199-278).  With grad enabled and `z.requires_grad` the result is
+    differentiable w.r.t. z: the same launches, their layer outputs kept, dz from dge_mapping_bwd (`wide_bwd`: from the chip-wide
+    dge_mapping_bwd_wide; embedding_v2's mode "Z" sets it per batch size in begin_image).  z is saved by reference: a backward
+    after an in-place update of z takes the pixel-norm adjoint at the updated z, as the reference's autograd does after a
+    `p.data` update, while every dense layer reads the output it saved."""
+    wide_bwd = False
 
     def __init__(self, input_space_dim=512, hidden_space_dim=512, final_space_dim=512, num_layers=8, lr_mul=0.01):
         super().__init__()
@@ -79,8 +116,10 @@ class MappingModule(nn.Module):
         if z.ndim != 2 or z.shape[1] != self.input_space_dim:
             raise ValueError(f"Input latent code should be with shape [batch_size, input_dim], where `input_dim` "
                              f"equals to {self.input_space_dim}!\nBut `{z.shape}` is received!")
+        if torch.is_grad_enabled() and z.requires_grad:
+            return self._forward_grad(z, label)
         zn = ops.pixelnorm(z.float().contiguous())
-        layers = [getattr(self, f"dense{i}") for i in range(self.num_layers)]
+        layers = self.layers()
         if _DENSE_CHAIN and self.num_layers <= 8 and all(max(L.weight.shape) <= 1024 for L in layers):
             # the 8 dense layers in one launch, bit-identical to the per-layer calls.  OFF by default: one workgroup per sample
             # leaves a 256-CU part idle behind a latency-bound chain (round 4: +0.8 ms per mapping pass at batch 8 against
@@ -90,6 +129,24 @@ class MappingModule(nn.Module):
             w = zn
             for L in layers:
                 w = L(w)
+        return {"z": zn, "label": label, "w": w}
+
+    def layers(self):
+        return [getattr(self, f"dense{i}") for i in range(self.num_layers)]
+
+    def _forward_grad(self, z, label):
+        """The per-layer launches of forward() with every layer output kept (what dge_mapping_bwd reads the leaky-relu masks off)."""
+        if self.num_layers > 8 or any(max(L.weight.shape) > 512 or L.weight.shape[1] % 4 for L in self.layers()):
+            raise ops.DgeError("MappingModule: d/dz needs at most 8 layers of widths up to 512 (multiples of 4)")
+        with torch.no_grad():
+            z32 = z.detach().float().contiguous()
+            zn = ops.pixelnorm(z32)
+            acts, x = [], zn
+            for L in self.layers():
+                x = L(x)
+                acts.append(x)
+        w = _MappingFunction.apply(z, self, z32, acts)
+        w._dge_mapping = (z, self, z32, acts)          # TruncationModule chains z -> wp through one adjoint call
         return {"z": zn, "label": label, "w": w}
 
 
@@ -109,7 +166,23 @@ class TruncationModule(nn.Module):
             assert w.ndim == 3 and tuple(w.shape[1:]) == (self.num_layers, self.w_space_dim)
         psi = 1.0 if trunc_psi is None else trunc_psi
         layers = 0 if trunc_layers is None else trunc_layers
+        src = getattr(w, "_dge_mapping", None)
+        if src is not None and torch.is_grad_enabled() and w.requires_grad:
+            return _MappingTruncFunction.apply(*src, self, psi, layers)
         return ops.truncation(w, self.w_avg, self.num_layers, psi, layers)
+
+    def coefs(self, psi, layers, dev):
+        """d wp[b, l, :] / d w[b, :] of forward(w, psi, layers) as the [L] device vector dge_mapping_bwd takes; None: all ones."""
+        n = min(int(layers), self.num_layers)
+        if not (psi < 1.0 and n > 0):          # dge_truncation's condition (reference :326)
+            return None
+        key = (float(psi), n, str(dev))
+        hit = self.__dict__.setdefault("_coefs_cache", {})
+        if key not in hit:
+            c = torch.ones(self.num_layers, dtype=torch.float32)
+            c[:n] = float(psi)
+            hit[key] = c.to(dev)
+        return hit[key]
 
 
 class UpsamplingLayer(nn.Module):
@@ -267,12 +340,15 @@ class StyleGAN2Generator(nn.Module):
         """Extra keywords: `mix_mask` (device [L] mask, hipGraph form of the style mixing) and `new_z` (the second latent of the
         style mixing, reference :187 `torch.randn_like(z)`; default: drawn by the counter-based device generator, which under
         data parallelism yields the rank's rows of the global-batch draw)."""
-        if z.requires_grad and torch.is_grad_enabled():
-            # the reference lets autograd run through the mapping network (baseline_utils/image2stylegan_w2z_opW.py optimises z);
-            # the HIP mapping has no backward: refuse loudly instead of returning a silently constant w
-            raise ops.DgeError("StyleGAN2Generator.forward: d/dz through the mapping network is not implemented on the HIP path; "
-                               "optimise w / wp (synthesis has a hand-written data gradient) or call under torch.no_grad()")
-        with torch.no_grad():
+        grad_z = z.requires_grad and torch.is_grad_enabled()
+        if grad_z and self.training and (w_moving_decay < 1 or style_mixing_prob > 0):
+            # the reference lets autograd run through the mapping network (baseline_utils/image2stylegan_w2z_opW.py optimises z, in
+            # eval mode); the train-mode side effects have no z gradient here: refuse loudly instead of returning a wrong one
+            active = ["the w_avg moving-average update (call .eval() or pass w_moving_decay=1)"] if w_moving_decay < 1 else []
+            active += ["style mixing (call .eval() or pass style_mixing_prob=0)"] if style_mixing_prob > 0 else []
+            raise ops.DgeError("StyleGAN2Generator.forward: d/dz through the mapping network is not implemented with a train-mode "
+                               "side effect active: " + " and ".join(active) + ", or call under torch.no_grad()")
+        with torch.set_grad_enabled(grad_z):
             mapping_results = self.mapping(z, label)
             w = mapping_results["w"]
             # train-mode side effects the reference keeps active during E_align (SURVEY Q1)

@@ -748,6 +748,17 @@ int dge_embed_track_rows(const float* loss, const float* norm, const float* w, i
  * read off them; NULL: the forward is recomputed with dge_dense_chain's arithmetic.  One workgroup per sample, no atomics. */
 int dge_mapping_bwd(const float* z, int ldz, const dge_dense_layer* layers, int n, const float* const* acts, const float* g, int L,
                     const float* coefs, float* dz, int lddz, int B, int pixelnorm, float eps, dge_stream_t stream);
+/* The same adjoint on saved activations (acts required; the recompute form stays with dge_mapping_bwd) as n + 1 chip-wide launches:
+ * one per layer, last layer first - grid = (128-column tiles of W) x (32-row groups of W) x (8-row batch tiles); a workgroup keeps
+ * the accumulators of its batch tile in registers, so W is read once per batch tile - and a tail (one workgroup per sample) with
+ * the pixel-norm adjoint.  The head sum_l coefs[l] * g[b, l, :] rides the first launch.  Partial sums go with plain stores to a
+ * slot of their own in `work` (dge_mapping_bwd_wide_work_bytes(B) bytes, 16-byte aligned, nothing pre-zeroed) and the next launch
+ * adds them in slot order: no atomics, no waiting between workgroups; the same bits every run, in either reduction mode, and for
+ * a row alone or inside a batch.  B up to 32767 (work_bytes returns -1 above). */
+int dge_mapping_bwd_wide_work_bytes(int B);
+int dge_mapping_bwd_wide(const float* z, int ldz, const dge_dense_layer* layers, int n, const float* const* acts, const float* g, int L,
+                         const float* coefs, float* dz, int lddz, int B, int pixelnorm, float eps, void* work, long long work_bytes,
+                         dge_stream_t stream);
 
 /* ---- evaluation metrics on 8-bit images (comparing-baseline.py:21-45, one image pair at a time) ------------------------------ */
 /* x [B,C,H,W] f32 or bf16 (dtype) in [-1,1] -> out [B,H,W,C] uint8 (4-byte aligned), the bytes torchvision.utils.save_image

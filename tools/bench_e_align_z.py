@@ -2,7 +2,11 @@
 mapping backward (dge_mapping_bwd, one launch) against the same math built from existing ops (8 dge_linear_t plus elementwise
 work), both on the activations a per-layer forward saved, timed with device events in the same process - dev/bench tool.
 Random-init weights, seeded stand-in LPIPS.
-    python tools/bench_e_align_z.py [--img-size 1024] [--batches 2 8] [--iters 10] [--dtype bf16]"""
+    python tools/bench_e_align_z.py [--img-size 1024] [--batches 2 8] [--iters 10] [--dtype bf16]
+--mapping-only: the mapping adjoint alone on a 8 x 512 mapping network with L W+ rows - dge_mapping_bwd on saved activations (one
+launch, one workgroup per sample), dge_mapping_bwd_wide (one chip-wide launch per layer) and the dge_linear_t composition - one
+process, the three alternating round by round, medians of --rounds rounds with the round spread (max - min).
+    python tools/bench_e_align_z.py --mapping-only [--batches 1 2 4 8] [--rows 18] [--rounds 5]"""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -40,13 +44,46 @@ def _time(fn, iters):
     return t0.elapsed_time(t1) / 1e3 / iters
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
+
+
+def mapping_only(a):
+    from dge_amd.stylegan1 import Mapping
+    torch.manual_seed(0)
+    res = {}
+    Gm = Mapping(num_layers=a.rows).cuda()
+    for B in a.batches:
+        z = torch.randn(B, 512, device="cuda")
+        g = torch.randn(B, a.rows, 512, device="cuda")
+        coefs = torch.where(torch.arange(a.rows) < a.rows // 2, 0.7, 1.0).float().cuda()
+        acts = Gm.activations(z)
+        work = torch.empty(ops.mapping_bwd_work_bytes(B), dtype=torch.uint8, device="cuda")
+        cfg = {"one_launch": lambda: ops.mapping_bwd(z, Gm.chain(), g, coefs=coefs, acts=acts),
+               "wide": lambda: ops.mapping_bwd(z, Gm.chain(), g, coefs=coefs, acts=acts, wide=True, work=work),
+               "composed": lambda: composed_mapping_bwd(Gm, z, g, coefs, acts=acts)}
+        t = {k: [] for k in cfg}
+        for _ in range(a.rounds):
+            for k, f in cfg.items():
+                t[k].append(_time(f, 200) * 1e6)
+        res[f"B{B}"] = {k: dict(us=round(_median(v), 1), spread=round(max(v) - min(v), 1), rounds=[round(q, 1) for q in v]) for k, v in t.items()}
+        print(f"mapping adjoint alone, B = {B}, L = {a.rows} (us per call, 200 back-to-back calls between two device events; median of "
+              f"{a.rounds} rounds, spread): " + ", ".join(f"{k} {_median(v):.1f} ({max(v) - min(v):.1f})" for k, v in t.items()), flush=True)
+    print(json.dumps(res))
+
+
 def main():
     from dge_amd.e_align_z import EAlignZStep, build_models_z
     ap = argparse.ArgumentParser()
     ap.add_argument("--img-size", type=int, default=1024); ap.add_argument("--start-features", type=int, default=16)
     ap.add_argument("--batches", type=int, nargs="+", default=[2, 8]); ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--dtype", default="bf16")
+    ap.add_argument("--mapping-only", action="store_true"); ap.add_argument("--rows", type=int, default=18)
+    ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
+    if a.mapping_only:
+        return mapping_only(a)
     res = {}
     for B in a.batches:
         Gs, Gm, E, LP = build_models_z(a.img_size, a.start_features, a.dtype)
@@ -66,13 +103,17 @@ def main():
         acts = Gm.activations(z)                 # saved by MappingFunction.forward in the step
         fused = _time(lambda: ops.mapping_bwd(z, Gm.chain(), g, coefs=coefs, acts=acts), 200)
         recomp = _time(lambda: ops.mapping_bwd(z, Gm.chain(), g, coefs=coefs), 200)
+        work = torch.empty(ops.mapping_bwd_work_bytes(B), dtype=torch.uint8, device="cuda")
+        wide = _time(lambda: ops.mapping_bwd(z, Gm.chain(), g, coefs=coefs, acts=acts, wide=True, work=work), 200)
         comp = _time(lambda: composed_mapping_bwd(Gm, z, g, coefs, acts=acts), 200)
         ref = composed_mapping_bwd(Gm, z, g, coefs, acts=acts)
         err = ((ops.mapping_bwd(z, Gm.chain(), g, coefs=coefs, acts=acts) - ref).abs().max() / ref.abs().max()).item()
         res[f"mapping_bwd_fused_us_b{B}"] = round(fused * 1e6, 1)
         res[f"mapping_bwd_fused_recompute_us_b{B}"] = round(recomp * 1e6, 1)
         res[f"mapping_bwd_composed_us_b{B}"] = round(comp * 1e6, 1)
-        print(f"mapping backward, batch {B} (activations saved by the forward): fused {fused * 1e6:.1f} us, composed {comp * 1e6:.1f} us; "
+        res[f"mapping_bwd_wide_us_b{B}"] = round(wide * 1e6, 1)
+        print(f"mapping backward, batch {B} (activations saved by the forward): fused {fused * 1e6:.1f} us, wide {wide * 1e6:.1f} us, "
+              f"composed {comp * 1e6:.1f} us; "
               f"fused with the forward recomputed inside {recomp * 1e6:.1f} us; max rel diff {err:.2e}", flush=True)
         del st, Gs, Gm, E, LP
         torch.cuda.empty_cache()

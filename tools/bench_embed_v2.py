@@ -11,6 +11,10 @@ process, the configurations alternating, medians over --rounds rounds.
 --last-stage: the last stage of E.BE's backward alone when the image carries a gradient, at [B,1024,1024,16] for B in --batches:
 the one launch (ops.in_bwd_fromrgb_img) against the passes it replaces (in_bwd -> fromrgb_dgrad [-> fromrgb_bwd]), frozen and
 trained encoder, alternating, medians over --rounds rounds.
+--space z: the Z-space loop (mode "Z") under hipGraph replay at batch 1 (coupled) and --batches independent rows, with each
+route of the mapping adjoint (dge_mapping_bwd / dge_mapping_bwd_wide), beside mode W on the same box, one process, the
+configurations alternating, medians over --rounds rounds with the round spread.
+    python tools/bench_embed_v2.py --space z --batches 8
     python tools/bench_embed_v2.py --compare-encoders --batches 8
     python tools/bench_embed_v2.py --last-stage --batches 1,8"""
 import argparse, json, os, sys, time
@@ -24,6 +28,7 @@ ap.add_argument("--img-size", type=int, default=1024); ap.add_argument("--start-
 ap.add_argument("--iters", type=int, default=20); ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--encoder", choices=("blur", "be"), default="blur"); ap.add_argument("--compare-encoders", action="store_true")
 ap.add_argument("--last-stage", action="store_true")
+ap.add_argument("--space", choices=("w", "z"), default="w")
 ap.add_argument("--independent", action="store_true"); ap.add_argument("--batches", default="2,4,8"); ap.add_argument("--rounds", type=int, default=5)
 a = ap.parse_args()
 res = {}
@@ -86,6 +91,32 @@ def bench_independent():
     print(json.dumps(res))
 
 
+def bench_space_z():
+    batches = [int(v) for v in a.batches.split(",")]
+    G, E, LP = build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0, encoder=a.encoder)
+    with torch.no_grad():
+        imgs = G.synthesis(torch.randn(max(batches + [1]), G.synthesis.num_layers, 512, device="cuda"))["image"].detach().clamp(-1, 1).contiguous()
+    runs = {}
+    for shape, B, ind in [("B1_coupled", 1, False)] + [(f"B{B}_independent", B, True) for B in batches]:
+        for name, kw in (("W", dict(mode="W")), ("Z_one_launch", dict(mode="Z", mapping_bwd="one")), ("Z_wide", dict(mode="Z", mapping_bwd="wide"))):
+            st = LatentEmbedStep(G, E, LP, generator="sg2", independent=ind, **kw)
+            st.begin_image(imgs[:B].contiguous())
+            st.capture(imgs[:B].contiguous(), warmup=1)
+            for _ in range(3):
+                st.replay()
+            runs[f"{shape}_{name}"] = (st, B)
+    ms = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for name, (st, B) in runs.items():
+            ms[name].append(timed(st.replay, a.iters))
+    for name, (st, B) in runs.items():
+        m = median(ms[name])
+        res[name] = dict(ms_per_iteration=round(m, 3), spread=round(max(ms[name]) - min(ms[name]), 3), rounds=[round(v, 3) for v in ms[name]])
+        print(f"embedding_v2 replay, StyleGAN2-{a.img_size} + {ENC_NAME[a.encoder]}, {a.dtype}, {name}: {m:.3f} ms/iteration "
+              f"(spread {max(ms[name]) - min(ms[name]):.3f}), {m / B:.3f} ms/image-iteration", flush=True)
+    print(json.dumps(res))
+
+
 def bench_compare_encoders():
     batches = [int(v) for v in a.batches.split(",")]
     models = {enc: build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0, encoder=enc) for enc in ("blur", "be")}
@@ -145,6 +176,9 @@ def bench_last_stage():
     print(json.dumps(res))
 
 
+if a.space == "z":
+    bench_space_z()
+    sys.exit(0)
 if a.independent:
     bench_independent()
     sys.exit(0)
