@@ -231,6 +231,8 @@ extern "C" int dge_affine_relu_bwd(const void* gu, const void* x, const float* a
     DGE_CHECK(C % ep == 0 && ((C / ep) & (C / ep - 1)) == 0, "affine_relu_bwd: C=%d must be a power-of-two multiple of %d", C, ep);
     const int Cg = C / ep > 256 ? 256 * ep : C;
     dim3 grid(dge_stream_grid(HW, 256 / (Cg / ep), B), B, C / Cg);
+    DGE_CHECK(dge_det_fits((long long)B * (C / Cg), grid.x, 2 * Cg),
+              "affine_relu_bwd: B=%d HW=%d C=%d does not fit the deterministic-mode workspace", B, HW, C);
     if (dtype == DGE_BF16) hipLaunchKernelGGL(affine_relu_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)gu, (const bf16_t*)x, a, b, (bf16_t*)gx, stats, HW, C, Cg);
     else hipLaunchKernelGGL(affine_relu_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)gu, (const float*)x, a, b, (float*)gx, stats, HW, C, Cg);
     DGE_LAUNCH_CHECK("affine_relu_bwd");
@@ -370,7 +372,14 @@ extern "C" int dge_sn_group(const void* entries, int n, int maxO, int maxK, floa
     DGE_CHECK(n > 0 && maxO > 0 && maxK > 0, "sn_group: empty group");
     const SnEntry* E = (const SnEntry*)entries;
     if (training) {
-        hipLaunchKernelGGL(sn_wtu_kernel, dim3((maxK + 255) / 256, (maxO + 63) / 64, n), dim3(256), 0, s, E);
+        // deterministic mode: a launch over m entries takes kb * m domains of `slabs` slots of 256 floats from the shared workspace
+        // (the domain index is local to a launch), so the table is walked in sub-ranges that fit it
+        const int kb = (maxK + 255) / 256, slabs = (maxO + 63) / 64;
+        int per = n;
+        while (per > 0 && !dge_det_fits((long long)kb * per, slabs, 256)) per--;
+        DGE_CHECK(per > 0, "sn_group: a weight of %d x %d does not fit the deterministic-mode workspace", maxO, maxK);
+        for (int e0 = 0; e0 < n; e0 += per)
+            hipLaunchKernelGGL(sn_wtu_kernel, dim3(kb, slabs, n - e0 < per ? n - e0 : per), dim3(256), 0, s, E + e0);
         hipLaunchKernelGGL(sn_norm_v_kernel, dim3(n), dim3(256), 0, s, E, eps);
     }
     hipLaunchKernelGGL(sn_wv_kernel, dim3((maxO + 3) / 4, n), dim3(256), 0, s, E);
