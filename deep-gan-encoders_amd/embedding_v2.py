@@ -46,9 +46,11 @@ Decisions where the reference cannot run as written:
         captured iteration keeps its shape) and discards the padded rows' outputs;
       - the encoder is shared by a group, so mode "E" has no independent form (ValueError).
 
-Generator kind "pg" (embedding_v2_pggan.PGEmbedStep: PGGAN + E_PG) runs the same iteration on z [B, z_space_dim] through three
-hooks - _latent_shape, _encode (E_PG has no const output: const2 / const3 / loss_c1 are None) and _generate - in StyleGAN1's
-order and with its defaults and tracker rules; "sg1" and "sg2" issue the launches they issued before.
+What differs between the generator kinds "sg1", "sg2" and "pg" is one table (KINDS): the defaults and tracker rules, the latent
+shape, how E and G are called, whether E(imgs2) runs before or after the phase-1 step, and where the W-mode start code comes
+from.  Kind "pg" (embedding_v2_pggan.PGEmbedStep: PGGAN + E_PG) runs the iteration on z [B, z_space_dim] in StyleGAN1's order
+and with its defaults and rules; E_PG has no const output: const2 / const3 / loss_c1 are None.  The constructor tail, the start of
+a group, the optimiser phase and the hipGraph plumbing are embed_step.TwoPhaseEmbedStep's, shared with embedding_v2_biggan.
 
 Mode "Z" (StyleGAN1 and StyleGAN2; the baseline every W+ result is compared against, and the only code that stays on the
 generator's sampling distribution).  The reference has no v2 Z-space script (its Z-space baseline is
@@ -75,21 +77,22 @@ embedding_v2_pggan is for PGGAN.  Per iteration:
   * the tracker follows z; `independent` works as in W mode (the mapping is per-sample already); files are the W-mode set with the
     z row in models/id*-i*-z*.pt and models/z_all_*.pt [N, 512].
 
-The file side of a group (dump_group, loss_txt_block, finish_group) and the group walk of main() (invert_folder, rows_plan) serve
-embedding_v2_biggan too: its dumps differ in the two file-name patterns and in the Loss.txt block, its walk in labels and
-img_all_*.pt.
+The loop over the iterations of a group (invert_group), its file side (dump_group, loss_txt_block, finish_group), the group walk
+of main() (invert_folder, rows_plan) and the common part of the command lines (add_inversion_args, open_run, run_inversion) serve
+embedding_v2_pggan and embedding_v2_biggan too: their dumps differ in the file-name patterns and in the Loss.txt block, BigGAN's
+walk in labels and img_all_*.pt.
 """
 import argparse
+import collections
 import math
 import os
 
 import torch
 
-from . import losses, ops, weight_cache
-from .custom_adam import LREQAdam
-from .embed_track import EVENT_LOSS, EVENT_NORM, EmbedTracker, tracker_rules, write_tracker_files  # noqa: F401 (re-exported)
+from . import losses, ops
+from .embed_step import TwoPhaseEmbedStep, several_processes
+from .embed_track import EVENT_LOSS, EVENT_NORM, tracker_rules, write_tracker_files  # noqa: F401 (re-exported)
 from .embedding import select_launch
-from .graph_step import GraphReplay
 from .models import add_model_args, blur_encoder, load_lpips_weights
 
 # per-generator defaults (embedding_v2_styleGAN1.py:195-209 + :118,128-131; embedding_v2_styleGAN2.py:214-232 + :136,153-166)
@@ -104,35 +107,20 @@ MAPPING_BWD_WIDE_MIN_BATCH = 1
 
 
 class _PNorm(torch.autograd.Function):
-    """||w||_p (dge_latent_pnorm_fwd) with its gradient (dge_latent_pnorm_bwd)."""
+    """||w||_p (dge_latent_pnorm_fwd) with its gradient (dge_latent_pnorm_bwd); `rows`: ||w[b]||_p for every row b -> [B]
+    (dge_latent_pnorm_rows_fwd / dge_latent_pnorm_rows_bwd)."""
 
     @staticmethod
-    def forward(ctx, w, p):
-        ctx.w, ctx.p = w.detach(), p
-        ctx.n = ops.latent_pnorm(ctx.w, p)
+    def forward(ctx, w, p, rows):
+        ctx.w, ctx.p, ctx.rows = w.detach(), p, rows
+        ctx.n = (ops.latent_pnorm_rows if rows else ops.latent_pnorm)(ctx.w, p)
         return ctx.n.clone()
 
     @staticmethod
     def backward(ctx, go):
         g = torch.zeros_like(ctx.w)
-        ops.latent_pnorm_bwd(ctx.w, ctx.n, g, ctx.p, 1.0, gout=go.contiguous().float())
-        return g, None
-
-
-class _PNormRows(torch.autograd.Function):
-    """||w[b]||_p for every row b -> [B] (dge_latent_pnorm_rows_fwd) with its gradient (dge_latent_pnorm_rows_bwd)."""
-
-    @staticmethod
-    def forward(ctx, w, p):
-        ctx.w, ctx.p = w.detach(), p
-        ctx.n = ops.latent_pnorm_rows(ctx.w, p)
-        return ctx.n.clone()
-
-    @staticmethod
-    def backward(ctx, go):
-        g = torch.zeros_like(ctx.w)
-        ops.latent_pnorm_rows_bwd(ctx.w, ctx.n, g, ctx.p, 1.0, gout=go.contiguous().float())
-        return g, None
+        (ops.latent_pnorm_rows_bwd if ctx.rows else ops.latent_pnorm_bwd)(ctx.w, ctx.n, g, ctx.p, 1.0, gout=go.contiguous().float())
+        return g, None, None
 
 
 class _WplusLerp(torch.autograd.Function):
@@ -148,17 +136,63 @@ class _WplusLerp(torch.autograd.Function):
         return ops.wplus_lerp_bwd(g, ctx.psi), None, None
 
 
-class LatentEmbedStep(GraphReplay):
+# What a generator kind is to LatentEmbedStep.  `defaults`: row of DEFAULTS; `rules`: name for tracker_rules; `latent_shape(st, B)`;
+# `encode(st, imgs, noises)` -> (const, w); `generate(st, code, noises, truncate)` -> imgs2; `encode_first`: E(imgs2) runs before
+# the phase-1 step (StyleGAN1's order) or after it; `start`: the W-mode start code is E(imgs1) ("encoder") or a seeded randn;
+# `own_mapping`: mode "Z" maps z with the step's Gm (StyleGAN1) instead of G.mapping and G.truncation.
+Kind = collections.namedtuple("Kind", "defaults rules latent_shape encode generate encode_first start own_mapping", defaults=(False,))
+
+
+def _wplus_shape(st, B):
+    return (B, st._num_rows(), 512)
+
+
+def _encode(st, imgs, noises):
+    return st.E(imgs, noises=noises)
+
+
+def _generate_sg1(st, w, noises, truncate):
+    return st.G.forward(w, st.G.layer_count - 1, noises=noises)
+
+
+def _generate_sg2(st, w, noises, truncate):
+    # (the synthesis backward reads its saved activations only, never wp: w itself may be the input when psi == 1)
+    wt = w if st.psi == 1.0 or not truncate else _WplusLerp.apply(w, st.G.truncation.w_avg, st.psi)
+    return st.G.synthesis(wt, randomize_noise=False)["image"]
+
+
+def _generate_pg(st, z, noises, truncate):          # (lod given: the generator does not read its `lod` buffer back, a captured iteration cannot)
+    return st.G(z, lod=0, fused_backward=st.fused_backward)["image"]
+
+
+KINDS = {
+    "sg1": Kind(1, "sg1", _wplus_shape, _encode, _generate_sg1, encode_first=True, start="encoder", own_mapping=True),
+    "sg2": Kind(2, "sg2", _wplus_shape, _encode, _generate_sg2, encode_first=False, start="randn"),
+    # PGGAN + E_PG (embedding_v2_pggan): StyleGAN1's defaults, rules and order; E_PG has no const output -> (None, z)
+    "pg": Kind(1, "sg1", lambda st, B: (B, st.G.z_space_dim), lambda st, imgs, noises: (None, _encode(st, imgs, noises)[1]), _generate_pg,
+               encode_first=True, start="encoder"),
+}
+
+
+def seeded_start(shape, seed, group, rows):
+    """The seeded start code of group `group`: randn(shape) from manual_seed(seed + group); `rows`: row r is the randn(1, ...) from
+    manual_seed(seed + group * B + r), the draw a batch-1 run makes for image number group * B + r."""
+    def draw(number, shp):
+        return torch.randn(shp, generator=torch.Generator().manual_seed(int(seed) + number))
+    if not rows:
+        return draw(group, shape)
+    return torch.cat([draw(group * shape[0] + r, (1,) + shape[1:]) for r in range(shape[0])])
+
+
+class LatentEmbedStep(TwoPhaseEmbedStep):
+    MODES = ("E", "W", "Z")
     fused_backward = True          # "pg": the generator backward with ops.pixelnorm_act_bwd (False: the composed launches, for timing)
 
     def __init__(self, G, E, lpips_model, mode="E", generator="sg2", lr=0.005, beta_1=0.0, beta=None, norm_p=2, truncation=None,
                  iterations=None, arm_iter=None, events_cap=256, seed=0, independent=False, Gm=None, mapping_bwd="auto"):
-        if mode not in ("E", "W", "Z"):
-            raise ValueError(f"mode must be 'E', 'W' or 'Z', got {mode!r}")
         if independent and mode == "E":
             raise ValueError("independent=True needs mode 'W' or 'Z': in mode 'E' one encoder is shared by the rows of a group")
-        self.independent = bool(independent)
-        if generator not in ("sg1", "sg2", "pg"):
+        if generator not in KINDS:
             raise ValueError(f"generator must be 'sg1', 'sg2' or 'pg', got {generator!r}")
         if mode == "Z":
             if generator == "pg":
@@ -167,157 +201,89 @@ class LatentEmbedStep(GraphReplay):
                 raise ValueError("mode 'Z' with generator 'sg1' needs the mapping network: pass Gm=stylegan1.Mapping")
             if mapping_bwd not in ("auto", "one", "wide"):
                 raise ValueError(f"mapping_bwd must be 'auto', 'one' or 'wide', got {mapping_bwd!r}")
-        self.Gm, self.mapping_bwd = Gm, mapping_bwd
-        d = DEFAULTS[2 if generator == "sg2" else 1]          # "pg" (embedding_v2_pggan): StyleGAN1's defaults, rules and order
-        self.G, self.E, self.lpips = G, E, lpips_model
-        self.mode, self.generator = mode, generator
-        self.lr, self.beta_1 = lr, beta_1
+        self.generator, self.kind = generator, KINDS[generator]
+        d = DEFAULTS[self.kind.defaults]
+        super().__init__(G, E, lpips_model, mode, self.kind.rules, lr, beta_1, d["iterations"] if iterations is None else iterations,
+                         arm_iter, events_cap, independent)
+        self.Gm, self.mapping_bwd, self.seed = Gm, mapping_bwd, seed
         self.beta = d["beta"] if beta is None else float(beta)
         self.norm_p = int(norm_p)
-        self.psi = (d["truncation"] if truncation is None else float(truncation)) if generator == "sg2" else None
-        self.iterations = d["iterations"] if iterations is None else int(iterations)
-        self.rules = tracker_rules("sg2" if generator == "sg2" else "sg1", self.iterations)
-        if arm_iter is not None:
-            self.rules["arm_iter"] = int(arm_iter)
-        self.events_cap, self.seed = int(events_cap), seed
-        self.lod = G.layer_count - 1 if generator == "sg1" else None
-        self.group = -1
-        self.last = {}
-        self.w1 = self._const2 = None
-        self._tracker = EmbedTracker(self.rules, self.events_cap, rows=self.independent)
-        if mode == "Z" and generator == "sg1":
+        self.psi = None if d["truncation"] is None else (d["truncation"] if truncation is None else float(truncation))
+        self._const2 = None
+        if mode == "Z" and self.kind.own_mapping:
             # the scripts' coefficients (embedding_v2_styleGAN1.py: 0.7 on the first half of the rows); without a centre Mapping
             # takes the plain broadcast whatever they are
             n = self._num_rows()
             self._coefs_m = torch.where(torch.arange(n).view(1, n, 1) < n // 2, 0.7, 1.0).float()
-        if mode == "E":
-            self.opt = LREQAdam([{"params": E.parameters()}], lr=lr, betas=(beta_1, 0.99), weight_decay=0)
-            self._ckpt = {k: v.detach().clone() for k, v in E.state_dict().items()}
-        else:
-            for p in E.parameters():          # frozen: the encoder backward computes the data gradient only
-                p.requires_grad_(False)
+        if mode != "E":
             E.eval()
-            self.opt = None
 
     # ------------------------------------------------------------------ per image group
     def _num_rows(self):
         return self.E.layer_count * 2
 
     def _latent_shape(self, B):
-        """Shape of the latent w1: the W+ code [B, rows, 512]; "pg": z [B, z_space_dim]."""
-        if self.mode == "Z":
-            return (B, 512)
-        return (B, self.G.z_space_dim) if self.generator == "pg" else (B, self._num_rows(), 512)
+        """Shape of the latent w1: the W+ code [B, rows, 512]; "pg": z [B, z_space_dim]; mode "Z": z [B, 512]."""
+        return (B, 512) if self.mode == "Z" else self.kind.latent_shape(self, B)
 
-    def _encode(self, imgs, noises):
-        """(const, w) = E(imgs); "pg": E_PG has no const output -> (None, z)."""
-        const, w = self.E(imgs, noises=noises)
-        return (None if self.generator == "pg" else const), w
-
-    def begin_image(self, imgs1, w_init=None, noises=None):
-        """Start an image group: E mode re-loads the encoder checkpoint and clears the Adam state (embedding_v2_*.py: the
-        per-group `E.load_state_dict`); W mode starts a fresh w1 (StyleGAN1: E(imgs1) detached, StyleGAN2: seeded randn or
-        `w_init`) with a fresh Adam state.  The tracker's iteration counter and event log restart (in place: a captured
-        iteration stays valid); the StyleGAN1 minima restart too, the StyleGAN2 ones carry over (independent mode: the minima of
-        every row restart, and a StyleGAN2 row draws its start code from the seed of its image number).  `noises`: optional noise
-        list of the StyleGAN1 W-mode E(imgs1) (parity runs)."""
-        dev = imgs1.device
-        B = imgs1.shape[0]
-        self.group += 1
-        shape = self._latent_shape(B)
-        if self.mode == "E":
-            self.E.load_state_dict(self._ckpt)
-            weight_cache.written(self.E.parameters())
-            self._reset_opt()
-        else:
-            with torch.no_grad():
-                if self.mode == "Z" and self.generator == "sg1":          # const2 of the const term, a constant as in W mode
-                    c0 = self.E(imgs1, noises=noises)[0]
-                    if self._const2 is None or self._const2.shape != c0.shape:
-                        self._const2 = torch.empty_like(c0)
-                    self._const2.copy_(c0)
-                if self.mode == "Z" and self.generator == "sg2":
-                    wide = {"one": False, "wide": True}.get(self.mapping_bwd)
-                    if wide is None:
-                        wide = MAPPING_BWD_WIDE_MIN_BATCH is not None and B >= MAPPING_BWD_WIDE_MIN_BATCH
-                    self.G.mapping.wide_bwd = wide
-                if w_init is not None:
-                    w0 = w_init.to(dev, torch.float32).reshape(shape)
-                elif self.mode == "Z" and not self.independent:
-                    w0 = torch.randn(shape, generator=torch.Generator().manual_seed(int(self.seed) + self.group))
-                elif self.mode == "Z":
-                    w0 = torch.cat([torch.randn((1,) + shape[1:], generator=torch.Generator().manual_seed(int(self.seed) + self.group * B + r))
-                                    for r in range(B)])
-                elif self.generator == "pg":
-                    w0 = self._encode(imgs1, noises)[1]
-                elif self.generator == "sg1":
-                    c0, w0 = self.E(imgs1, noises=noises)
-                    if self._const2 is None or self._const2.shape != c0.shape:
-                        self._const2 = torch.empty_like(c0)
-                    self._const2.copy_(c0)
-                elif self.independent:
-                    w0 = torch.cat([torch.randn((1,) + shape[1:], generator=torch.Generator().manual_seed(int(self.seed) + self.group * B + r))
-                                    for r in range(B)])
-                else:
-                    gen = torch.Generator().manual_seed(int(self.seed) + self.group)
-                    w0 = torch.randn(shape, generator=gen)
-                if self.w1 is None or tuple(self.w1.shape) != shape or self.w1.device != dev:
-                    if self.captured:
-                        raise ValueError("LatentEmbedStep.begin_image: the captured iteration works on a different latent shape")
-                    self.w1 = torch.zeros(shape, dtype=torch.float32, device=dev, requires_grad=True)
-                    self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
-                self.w1.copy_(w0)
-            self._reset_opt()
-        self._tracker.reset(shape, dev)
+    def _start_code(self, imgs1, shape, noises, needed):
+        """begin_image (TwoPhaseEmbedStep) for a frozen encoder: w1 starts from E(imgs1) detached (StyleGAN1, PGGAN) or a seeded
+        randn (StyleGAN2, mode "Z"), unless `w_init` is given (`needed` False).  The StyleGAN1 minima of the tracker restart with
+        the group, the StyleGAN2 ones carry over (independent mode: the minima of every row restart, and a row draws its start code
+        from the seed of its image number).  `noises`: optional noise list of the E(imgs1) below (parity runs)."""
+        zmode = self.mode == "Z"
+        encoded = needed and not zmode and self.kind.start == "encoder"
+        w0 = None
+        if encoded or (zmode and self.kind.own_mapping):          # (mode "Z", StyleGAN1: for const2 alone, a constant as in W mode)
+            c0, w0 = self.kind.encode(self, imgs1, noises)
+            if c0 is not None:
+                if self._const2 is None or self._const2.shape != c0.shape:
+                    self._const2 = torch.empty_like(c0)
+                self._const2.copy_(c0)
+        if zmode and not self.kind.own_mapping:
+            wide = {"one": False, "wide": True}.get(self.mapping_bwd)
+            if wide is None:
+                wide = MAPPING_BWD_WIDE_MIN_BATCH is not None and shape[0] >= MAPPING_BWD_WIDE_MIN_BATCH
+            self.G.mapping.wide_bwd = wide
+        return w0 if encoded or not needed else seeded_start(shape, self.seed, self.group, self.independent)
 
     # ------------------------------------------------------------------ one iteration
     def _generate(self, w1, noises):
-        if self.generator == "sg1":
-            return self.G.forward(w1, self.lod, noises=noises)
-        if self.generator == "pg":          # (lod given: the generator does not read its `lod` buffer back, a captured iteration cannot)
-            return self.G(w1, lod=0, fused_backward=self.fused_backward)["image"]
-        syn = self.G.synthesis
-        # (the synthesis backward reads its saved activations only, never wp: w1 itself may be the input when psi == 1)
-        wt = w1 if self.psi == 1.0 else _WplusLerp.apply(w1, self.G.truncation.w_avg, self.psi)
-        return syn(wt, randomize_noise=False)["image"]
+        return self.kind.generate(self, w1, noises, truncate=True)
 
     def _wp_of(self, z):
         """Mode "Z": wp = trunc(map(z)), differentiable w.r.t. z (StyleGAN2: dge_pixelnorm, eight dge_linear, dge_truncation)."""
-        if self.generator == "sg1":
+        if self.kind.own_mapping:
             return self.Gm(z, coefs_m=self._coefs_m)
         G = self.G
         return G.truncation(G.mapping(z)["w"], self.psi, G.num_layers)
 
     def _synthesise(self, wp, noises):
         """Mode "Z": imgs2 = G(wp), wp already truncated."""
-        if self.generator == "sg1":
-            return self.G.forward(wp, self.lod, noises=noises)
-        return self.G.synthesis(wp, randomize_noise=False)["image"]
+        return self.kind.generate(self, wp, noises, truncate=False)
 
     def step(self, imgs1, noises=(None, None, None)):
         """One iteration; `noises` = optional (E(imgs1), G, E(imgs2)) noise lists for parity runs (StyleGAN2: G's is unused, the
         synthesis noise is its fixed buffers; W mode: E(imgs1)'s is unused).  Independent mode: the loss entries of the result
         (`loss_msiv`, `loss_w`, `loss_c1`, `norm`, `loss_mslv`, `w_norm`) are [B], `info_img` is [B,3,8]."""
-        rows = self.independent
+        rows, kind = self.independent, self.kind
         if self.group < 0:
             raise RuntimeError("LatentEmbedStep.step: call begin_image() first")
         ops.zero_arena_begin(imgs1.device)
         if self.mode == "E":
-            const2, w1 = self._encode(imgs1, noises[0])
+            const2, w1 = kind.encode(self, imgs1, noises[0])
         else:
             w1, const2 = self.w1, self._const2
         zmode = self.mode == "Z"
         wp = self._wp_of(w1) if zmode else None
         imgs2 = self._synthesise(wp, noises[1]) if zmode else self._generate(w1, noises[1])
-        if self.generator != "sg2":
-            const3, w2 = self._encode(imgs2, noises[2])
+        if kind.encode_first:
+            const3, w2 = kind.encode(self, imgs2, noises[2])
         image_loss, latent_loss = (losses.image_loss_tsa_rows, losses.space_loss_rows) if rows else (losses.image_loss_tsa, losses.space_loss)
         loss_msiv, info_img = image_loss(imgs1, imgs2, self.lpips, weights=IMG_WEIGHTS, grad_windows=(True, True, True))
-        self.opt.zero_grad()
-        loss_msiv.backward(retain_graph=True)
-        self.opt.step()
-        if self.generator == "sg2":
-            const3, w2 = self._encode(imgs2, noises[2])
+        self._opt_phase(loss_msiv, retain_graph=True)
+        if not kind.encode_first:
+            const3, w2 = kind.encode(self, imgs2, noises[2])
         wp_new = self._wp_of(w1) if zmode else None          # the direct term of phase 2 sees the updated code
         loss_w, info_w = latent_loss(wp_new if zmode else w1, w2, image_space=False)
         lat = loss_w
@@ -325,11 +291,9 @@ class LatentEmbedStep(GraphReplay):
         if const2 is not None:
             loss_c1, info_c = latent_loss(const2, const3, image_space=False)
             lat = lat + loss_c1
-        nrm = (_PNormRows if rows else _PNorm).apply(w1, self.norm_p)
+        nrm = _PNorm.apply(w1, self.norm_p, rows)
         loss_mslv = lat * 0.01 + (nrm.sum() if rows else nrm) * self.beta
-        self.opt.zero_grad()
-        loss_mslv.backward()
-        self.opt.step()
+        self._opt_phase(loss_mslv)
         w1d = w1.detach()
         if rows:      # the values of every row: the [B] columns of the info tensors (the scalars above are their sums over the rows)
             loss_msiv = info_img[:, 0, 0] * IMG_WEIGHTS[0] + info_img[:, 1, 0] * IMG_WEIGHTS[1] + info_img[:, 2, 0] * IMG_WEIGHTS[2]
@@ -347,41 +311,6 @@ class LatentEmbedStep(GraphReplay):
         if zmode:
             self.last.update(wp=wp.detach(), wp_new=wp_new.detach())
         return self.last
-
-    # ------------------------------------------------------------------ hipGraph replay of the iteration
-    def capture(self, imgs1, noises=(None, None, None), warmup=GraphReplay.WARMUP):
-        """`warmup` real iterations, then one recorded (not executed) iteration (GraphReplay._capture).  Adam's step factors come
-        through graph_advance, the noise seed is a device scalar; in W mode the graph updates the static leaf w1 in place.
-        begin_image() must have run for the group."""
-        self._g_imgs1 = imgs1.detach().clone()
-        self.opt.graph_begin(2, imgs1.device)          # two optimizer calls per iteration
-        ops.noise_graph_begin(imgs1.device)
-        self.graph_iteration = 0
-        warm = {}
-
-        def keep_last():    # results of the last executed iteration (the captured one is only recorded)
-            if warmup:
-                warm.update({k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.last.items()})
-        out = self._capture(lambda: self.step(self._g_imgs1, noises), warmup, after_warmup=keep_last)
-        self.last = warm
-        return out
-
-    def _graph_inputs(self, iteration):
-        self.opt.graph_advance()
-        ops.noise_graph_seed(iteration)
-
-    def set_image(self, imgs1):
-        """Copies a new image group into the static input of the captured iteration (call begin_image() for the group too)."""
-        self._set_static("_g_imgs1", imgs1)
-
-    def replay(self):
-        self.last = super().replay()
-        return self.last
-
-    # ------------------------------------------------------------------ tracker read-out (one host read)
-    def tracker(self):
-        """The tracker's state on the host; independent mode: a list with one such read-out per row."""
-        return self._tracker.read()
 
 
 def group_plan(n_images, batch_size):
@@ -496,25 +425,30 @@ def invert_folder(invert, imgs, bs, independent, out, labels=None, save_imgs=Fal
             torch.save(torch.stack(img_all, dim=0), os.path.join(out, "models", "img_all_%d.pt" % (len(w_all) - 1)))
 
 
+def invert_group(st, imgs1, iterations, launch, save_every, out_dir, group, keep, begin_kw={}, dump_kw={}, infos=None):
+    """The loop of invert_v2, embedding_v2_pggan.invert_pg and embedding_v2_biggan.invert_big: begin_image(imgs1, **begin_kw),
+    `iterations` iterations through `launch`, a dump_group(..., **dump_kw) at every `save_every`-th with `out_dir`, finish_group.
+    `infos(r)`: the result dict with the info vectors under the keys loss_txt_block prints."""
+    st.begin_image(imgs1, **begin_kw)
+    if launch not in ("graph", "eager"):
+        raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
+    run, done = select_launch(st, imgs1, launch)
+    r = st.last
+    for i in range(max(iterations, done)):
+        if i >= done:                                # (with done == 1, iteration 0 ran as capture()'s warm-up)
+            r = run()
+        if out_dir is not None and save_every and i % save_every == 0:
+            dump_group(st, imgs1, r if infos is None else infos(r), i, out_dir, group, keep, **dump_kw)
+    return finish_group(st, r, imgs1.shape[0], out_dir, group, keep)
+
+
 def invert_v2(st, imgs1, iterations, launch="graph", save_every=100, out_dir=None, group=0, w_init=None, keep=None):
     """`iterations` iterations on one image group.  launch="graph" captures the iteration once (its warm-up iteration is a real one)
     and replays it; later groups go through set_image.  With `out_dir` the reference's every-`save_every` dumps (dump_group: image
     pair, per-row w1) are written and, at the end, the trackers' files (finish_group).  Returns the last result dict with the tracker
     read-out under "tracker".  Independent mode: files carry the image number group*B + b and that row's norm and loss; only the
     first `keep` rows (default: all) are written, and "tracker" is the list of per-row read-outs."""
-    st.begin_image(imgs1, w_init=w_init)
-    if launch not in ("graph", "eager"):
-        raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
-    run, done = select_launch(st, imgs1, launch)
-    r = st.last
-    dumps = out_dir is not None and save_every
-    if done and dumps:
-        dump_group(st, imgs1, r, 0, out_dir, group, keep)          # iteration 0 ran as capture()'s warm-up
-    for i in range(done, iterations):
-        r = run()
-        if dumps and i % save_every == 0:
-            dump_group(st, imgs1, r, i, out_dir, group, keep)
-    return finish_group(st, r, imgs1.shape[0], out_dir, group, keep)
+    return invert_group(st, imgs1, iterations, launch, save_every, out_dir, group, keep, dict(w_init=w_init))
 
 
 ENCODERS = ("blur", "be")
@@ -576,15 +510,20 @@ def load_checkpoints(G, E, mtype, gan=None, enc=None, Gm=None):
             Gm.buffer1 = torch.load(gan + "center_tensor.pt", map_location="cpu")
     if gan:
         if mtype == 2:
-            ckpt = torch.load(gan, map_location="cpu")
-            G.load_state_dict(ckpt["generator_smooth"] if "generator_smooth" in ckpt else ckpt["generator"])
+            load_generator_smooth(G, gan)
         else:
             G.load_state_dict(torch.load(gan + "Gs_dict.pth", map_location="cpu"))
     if enc:
         E.load_state_dict(torch.load(enc, map_location="cpu"))
 
 
-# ------------------------------------------------------------------ CLI
+def load_generator_smooth(G, path):
+    """The generator container of models.load_models for --mtype 2 and 3: a dict holding `generator_smooth` (or `generator`)."""
+    ckpt = torch.load(path, map_location="cpu")
+    G.load_state_dict(ckpt["generator_smooth"] if "generator_smooth" in ckpt else ckpt["generator"])
+
+
+# ------------------------------------------------------------------ CLI (the common part serves embedding_v2_pggan / _biggan too)
 def strict_bool(s):
     v = str(s).strip().lower()
     if v in ("true", "1", "yes"):
@@ -594,33 +533,47 @@ def strict_bool(s):
     raise argparse.ArgumentTypeError(f"expected true or false, got {s!r}")
 
 
-def make_parser():
-    p = argparse.ArgumentParser(description="real-image inversion (embedding_v2_styleGAN1.py / embedding_v2_styleGAN2.py)")
-    p.add_argument("--iterations", type=int, default=None, help="default: 1501 (mtype 1), 2001 (mtype 2)")
-    p.add_argument("--lr", type=float, default=None, help="default 0.005")
-    p.add_argument("--beta_1", type=float, default=None, help="default 0.0")
-    p.add_argument("--batch_size", type=int, default=1)
+def _refuse(msg):
+    """argparse type of a flag that is not offered: any value is an error with `msg`."""
+    def parse(_):
+        raise argparse.ArgumentTypeError(msg)
+    return parse
+
+
+def add_inversion_args(p, defaults, mtype, img_dir, latent, launch=True, helps={}):
+    """The flags every inversion CLI has.  `defaults`: of --iterations / --lr / --beta_1 / --batch_size (absent: None, filled in later;
+    batch_size 1), `helps`: their help texts; `latent`: what --optimizeE false optimises, for its help text; `launch`: offer --launch."""
+    for name, typ in (("iterations", int), ("lr", float), ("beta_1", float)):
+        p.add_argument("--" + name, type=typ, default=defaults.get(name), help=helps.get(name))
+    p.add_argument("--batch_size", type=int, default=defaults.get("batch_size", 1))
     p.add_argument("--experiment_dir", default=None)
     add_model_args(p)
-    p.set_defaults(mtype=1)
-    p.add_argument("--img_dir", default="./real_imgs/", help="a directory of images or a .pt tensor in [0,1]")
-    p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise W+ directly")
-    p.add_argument("--space", choices=("w", "z"), default="w",
-                   help="with --optimizeE false: optimise the W+ code (w) or z in front of the mapping network (z; --mtype 1 or 2)")
+    p.set_defaults(mtype=mtype)
+    p.add_argument("--img_dir", default=img_dir, help="a directory of images or a .pt tensor in [0,1]")
+    p.add_argument("--optimizeE", type=strict_bool, default=True, help=f"true: fine-tune the encoder; false: optimise {latent} directly")
     p.add_argument("--independent", type=strict_bool, default=False,
                    help="true (with --optimizeE false): every image of a batch is an inversion of its own, equal to its batch-1 run")
-    p.add_argument("--encoder", choices=ENCODERS, default="blur",
-                   help="blur: E_Blur; be: E.BE, the encoder E_align trains (--checkpoint_dir_E then takes its checkpoints)")
-    p.add_argument("--beta", type=float, default=None, help="weight of ||w1||_p: default 1e-3 (mtype 1), 3e-4 (mtype 2)")
-    p.add_argument("--norm_p", type=int, default=None, help="p of ||w1||_p (default 2)")
-    p.add_argument("--truncation", type=float, default=None, help="StyleGAN2: psi of avg + psi*(w1 - avg) (default 0.7; 1: none)")
-    p.add_argument("--launch", choices=("eager", "graph"), default="graph")
+    if launch:
+        p.add_argument("--launch", choices=("eager", "graph"), default="graph")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--save_every", type=int, default=100)
     p.add_argument("--vgg_weights", default=None)
     p.add_argument("--lpips_weights", default=None)
     p.add_argument("--allow_standin_lpips", action="store_true")
     p.add_argument("--deterministic", action="store_true")
+
+
+def make_parser():
+    p = argparse.ArgumentParser(description="real-image inversion (embedding_v2_styleGAN1.py / embedding_v2_styleGAN2.py)")
+    add_inversion_args(p, {}, 1, "./real_imgs/", "W+",
+                       helps=dict(iterations="default: 1501 (mtype 1), 2001 (mtype 2)", lr="default 0.005", beta_1="default 0.0"))
+    p.add_argument("--space", choices=("w", "z"), default="w",
+                   help="with --optimizeE false: optimise the W+ code (w) or z in front of the mapping network (z; --mtype 1 or 2)")
+    p.add_argument("--encoder", choices=ENCODERS, default="blur",
+                   help="blur: E_Blur; be: E.BE, the encoder E_align trains (--checkpoint_dir_E then takes its checkpoints)")
+    p.add_argument("--beta", type=float, default=None, help="weight of ||w1||_p: default 1e-3 (mtype 1), 3e-4 (mtype 2)")
+    p.add_argument("--norm_p", type=int, default=None, help="p of ||w1||_p (default 2)")
+    p.add_argument("--truncation", type=float, default=None, help="StyleGAN2: psi of avg + psi*(w1 - avg) (default 0.7; 1: none)")
     return p
 
 
@@ -632,7 +585,7 @@ def parse_args(argv=None):
             raise SystemExit("embedding_v2: --space z needs --optimizeE false (z is optimised against the frozen encoder)")
         if args.mtype not in (1, 2):
             raise SystemExit("embedding_v2: --space z is for --mtype 1 (StyleGAN1) or 2 (StyleGAN2); PGGAN and BigGAN optimise z already")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        if several_processes(env=True):
             raise SystemExit("embedding_v2: --space z runs in one process (WORLD_SIZE > 1 is not supported)")
     if args.mtype not in DEFAULTS:
         raise SystemExit("embedding_v2: --mtype must be 1 (StyleGAN1) or 2 (StyleGAN2)")
@@ -652,6 +605,22 @@ def _load_imgs(path, size, device):
     return load_images([os.path.join(path, n) for n in names], size, bicubic=True, device=device)
 
 
+def open_run(args, LP, default_out, dev):
+    """Behind the models of a CLI run: the LPIPS weights, the output tree (--experiment_dir) and the images -> (out, imgs)."""
+    load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
+    out = args.experiment_dir or default_out
+    for sub in ("", "imgs", "models", "summaries"):
+        os.makedirs(os.path.join(out, sub), exist_ok=True)
+    return out, _load_imgs(args.img_dir, args.img_size, dev)
+
+
+def run_inversion(args, st, invert, imgs, out, **walk_kw):
+    """The tail of a CLI run: invert_folder over `imgs` with `invert` (invert_v2, invert_pg, invert_big) on the step `st`."""
+    kw = dict(save_every=args.save_every, out_dir=out, **({"launch": args.launch} if "launch" in args else {}))
+    invert_folder(lambda imgs1, **gk: invert(st, imgs1, args.iterations, **kw, **gk), imgs, args.batch_size, args.independent, out, **walk_kw)
+    return st
+
+
 def main(argv=None):
     args = parse_args(argv)
     if args.deterministic:
@@ -662,17 +631,11 @@ def main(argv=None):
     zspace = args.space == "z"
     Gm = build_mapping_sg1(G, dev, args.seed) if zspace and args.mtype == 1 else None
     load_checkpoints(G, E, args.mtype, args.checkpoint_dir_GAN, args.checkpoint_dir_E, Gm=Gm)
-    load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
-    out = args.experiment_dir or "./realimg_embedding_result/7"
-    for sub in ("", "imgs", "models", "summaries"):
-        os.makedirs(os.path.join(out, sub), exist_ok=True)
-    imgs = _load_imgs(args.img_dir, args.img_size, dev)
+    out, imgs = open_run(args, LP, "./realimg_embedding_result/7", dev)
     st = LatentEmbedStep(G, E, LP, mode="E" if args.optimizeE else ("Z" if zspace else "W"), Gm=Gm, generator="sg1" if args.mtype == 1 else "sg2", lr=args.lr,
                          beta_1=args.beta_1, beta=args.beta, norm_p=args.norm_p, truncation=args.truncation,
                          iterations=args.iterations, seed=args.seed, independent=args.independent)
-    invert_folder(lambda imgs1, **kw: invert_v2(st, imgs1, args.iterations, launch=args.launch, save_every=args.save_every, out_dir=out, **kw),
-                  imgs, args.batch_size, args.independent, out, all_name="z_all_%d.pt" if zspace else "w_all_%d.pt")
-    return st
+    return run_inversion(args, st, invert_v2, imgs, out, all_name="z_all_%d.pt" if zspace else "w_all_%d.pt")
 
 
 if __name__ == "__main__":

@@ -6,8 +6,8 @@ generator) with the conditional-BN encoder E_BIG, in two modes:
 
 Once:      embed = G.embeddings(one_hot(label));  z0 = truncated_noise_sample(0.4, B, seed=iterations % 30000)
            cond_vector = cat(z0, embed)            (a constant: E's condition in every call)
-Per group: [W] const1, w1 = E(imgs1, cond_vector) detached -> leaf w1, fresh LREQAdam on it
-           [E] the encoder checkpoint is re-loaded, the Adam state cleared
+Per group: [W] const1, w1 = E(imgs1, cond_vector) detached -> copied into the leaf w1, the Adam state cleared
+           [E] the encoder checkpoint is re-loaded, the Adam state cleared          (embed_step.TwoPhaseEmbedStep.begin_image)
 Per iteration:
     [E] const1, w1 = E(imgs1, cond_vector)
     imgs2, _ = G(w1, conditions, truncation);   const2, w2 = E(imgs2, cond_vector)
@@ -32,8 +32,8 @@ Decisions:
     called: the guided-backprop gradients and the heat maps the script also computes are unused and are not produced.
     attention=True is the default (it needs the vgg16 network); --attention false leaves the two terms out.
   * Tracker.  embed_track.EmbedTracker (the device-side dge_embed_track) with tracker_rules("sg1", iterations): armed at
-    iterations // 2, hysteresis 1.05, no norm tracker, minima restart per group; files through embedding_v2.finish_group (the
-    script's names), the dumps through embedding_v2.dump_group, the folder walk of main() through embedding_v2.invert_folder.
+    iterations // 2, hysteresis 1.05, no norm tracker, minima restart per group; the loop of a group is embedding_v2.invert_group
+    (files through finish_group - the script's names - and dump_group), the folder walk of main() embedding_v2.invert_folder.
   * Not offered, each a ValueError / SystemExit with a clear message: capture() / hipGraph replay (the power iterations are
     host-sequenced; --mtype 4 is excluded from capture elsewhere too), independent=True on BigEmbedStep (the rows form is a class of
     its own, below), more than one process, and --beta / --norm_p (the norm term is commented out in the script, :163).
@@ -52,18 +52,15 @@ Decisions:
   * Without --config_dir the generator is BigGAN-deep-256 (BIGGAN_DEEP256, the released configuration).
 """
 import argparse
-import collections
 import numbers
 import os
 
 import torch
 
-from . import losses, ops, weight_cache
-from .custom_adam import LREQAdam
-from .embed_track import EmbedTracker, tracker_rules
-from .embedding_v2 import _load_imgs, dump_group, finish_group, invert_folder, rows_plan, strict_bool  # noqa: F401 (rows_plan: re-exported)
+from . import losses, ops
+from .embed_step import TwoPhaseEmbedStep, several_processes
+from .embedding_v2 import _refuse, add_inversion_args, invert_group, open_run, rows_plan, run_inversion, strict_bool  # noqa: F401 (rows_plan: re-exported)
 from .generators import truncated_noise_sample
-from .models import add_model_args, load_lpips_weights
 
 DEFAULTS = dict(iterations=1501, lr=0.0003, beta_1=0.0, batch_size=1, img_size=256, z_dim=128, start_features=64, label=30,
                 truncation=0.4)
@@ -83,34 +80,25 @@ MSG_NORM = "embedding_v2_biggan: --beta / --norm_p are not offered (the norm ter
 IMG_NAME, W_NAME = "id{n}_ep{i}-norm{norm:.2f}.jpg", "id{n}-i{k}-w{i}-norm{norm:f}.pt"
 
 
-class BigEmbedStep:
+class BigEmbedStep(TwoPhaseEmbedStep):
+    independent = False          # the rows form: BigEmbedRowsStep
+
     def __init__(self, G, E, lpips_model, mode="E", vgg16=None, attention=True, label=30, lr=0.0003, beta_1=0.0, truncation=0.4,
                  iterations=1501, arm_iter=None, events_cap=256, independent=False):
         """`vgg16`: dge_amd.grad_cam.VGG16 (torchvision vgg16 layout) for the attention terms; needed unless attention=False."""
-        if mode not in ("E", "W"):
-            raise ValueError(f"mode must be 'E' or 'W', got {mode!r}")
         if independent:
             raise ValueError(MSG_INDEPENDENT)
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        if several_processes():
             raise ValueError(MSG_DIST)
         if attention and vgg16 is None:
             raise ValueError("BigEmbedStep: attention=True needs the vgg16 network (dge_amd.grad_cam.VGG16); pass attention=False to "
                              "leave the attention terms out")
-        self.G, self.E, self.lpips = G, E, lpips_model
-        self.mode, self.attention = mode, bool(attention)
-        self.label, self.lr, self.beta_1 = int(label), lr, beta_1
+        # (tracker_rules("sg1"): armed at iterations // 2, the minima restart per group, embedding_v2_BigGAN.py:88)
+        super().__init__(G, E, lpips_model, mode, "sg1", lr, beta_1, iterations, arm_iter, events_cap, type(self).independent)
+        self.attention, self.label = bool(attention), int(label)
         self.truncation = torch.tensor(float(truncation), dtype=torch.float)      # float32 tensor, on the host (generators.BigGANAdapter)
         self.z_truncation = float(truncation)
-        self.iterations = int(iterations)
-        self.rules = tracker_rules("sg1", self.iterations)
-        if arm_iter is not None:
-            self.rules["arm_iter"] = int(arm_iter)
-        self.events_cap = int(events_cap)
-        self._tracker = EmbedTracker(self.rules, self.events_cap, rows=self.independent)
-        self.group = -1
-        self.last = {}
-        self.w1 = self._const1 = None
-        self.conditions = self.cond_vector = None
+        self._const1 = self.labels = self.conditions = self.cond_vector = None
         for p in G.parameters():
             p.requires_grad_(False)
         G.train(); E.train()                    # the script never leaves train mode
@@ -118,82 +106,71 @@ class BigEmbedStep:
             from .grad_cam import GradCamPlusPlus, GuidedBackPropagation
             self.grad_cam_plus_plus = GradCamPlusPlus(vgg16, vgg16.final_layer)
             self.gbp = GuidedBackPropagation(vgg16)          # shared network: the masks' backward is the guided one, as in the script
-        if mode == "E":
-            self.opt = LREQAdam([{"params": E.parameters()}], lr=lr, betas=(beta_1, 0.99), weight_decay=0)
-            self._ckpt = {k: v.detach().clone() for k, v in E.state_dict().items()}
-        else:
-            for p in E.parameters():          # frozen: the encoder backward computes the data gradient only
-                p.requires_grad_(False)
-            self.opt = None
-
-    captured = independent = False
 
     def capture(self, *a, **kw):
         raise ValueError(MSG_CAPTURE)
 
     replay = capture
 
-    # ------------------------------------------------------------------ once per batch size
-    def _setup(self, B, dev):
-        """embedding_v2_BigGAN.py:37-47: the class condition, its embedding and the constant condition vector of the encoder."""
-        if self.cond_vector is not None and self.cond_vector.shape[0] == B and self.cond_vector.device == dev:
+    # ------------------------------------------------------------------ once per set of row labels
+    def _setup(self, labels, dev):
+        """embedding_v2_BigGAN.py:37-47: the class conditions of the rows (`labels`: one class id per row), their embeddings and the
+        constant condition vector of the encoder; rebuilt when the labels (coupled form: their number) or the device change."""
+        if self.cond_vector is not None and self.labels == labels and self.cond_vector.device == dev:
             return
-        cfg = self.G.config
+        cfg, B = self.G.config, len(labels)
+        self.labels = labels
         self.conditions = torch.zeros(B, cfg.num_classes, device=dev)
-        self.conditions[:, self.label] = 1.0
+        self.conditions[torch.arange(B, device=dev), torch.tensor(labels, device=dev)] = 1.0
         with torch.no_grad():
             embed = ops.linear(self.conditions, self.G.embeddings.weight.detach())
-        z0 = truncated_noise_sample(truncation=self.z_truncation, batch_size=B, dim_z=cfg.z_dim, seed=self.iterations % 30000)
-        self.cond_vector = torch.cat((torch.tensor(z0, dtype=torch.float).to(dev), embed), dim=1).contiguous()
+        # rows form: the batch-1 draw for every row (rows 1.. of a batch-B draw are other numbers: no batch-1 run would see them)
+        z0 = truncated_noise_sample(truncation=self.z_truncation, batch_size=1 if self.independent else B, dim_z=cfg.z_dim,
+                                    seed=self.iterations % 30000)
+        self.cond_vector = torch.cat((torch.tensor(z0, dtype=torch.float).to(dev).expand(B, -1), embed), dim=1).contiguous()
 
-    # ------------------------------------------------------------------ per image group
-    def begin_image(self, imgs1, w_init=None, noises=None):
-        """Start an image group.  Mode E re-loads the encoder checkpoint and clears the Adam state; mode W starts the leaf w1 from
-        E(imgs1, cond_vector) (or `w_init`) with a fresh Adam state, const1 of that call stays as the logged constant.  The tracker
-        restarts.  `noises`: optional noise list of the W-mode E(imgs1) (parity runs)."""
-        dev = imgs1.device
-        B = imgs1.shape[0]
-        self._setup(B, dev)
-        self.group += 1
-        shape = (B, self.G.config.z_dim)
-        if self.mode == "E":
-            self.E.load_state_dict(self._ckpt)
-            weight_cache.written(self.E.parameters())
-            self.opt.state = collections.defaultdict(dict)
-        else:
-            self._start_w(imgs1, shape, w_init, noises)
-        self._tracker.reset(shape, dev)          # (sg1 rules: the minima restart per group, :88)
+    # ------------------------------------------------------------------ per image group (begin_image: TwoPhaseEmbedStep)
+    def _begin_group(self, imgs1):
+        self._setup((self.label,) * imgs1.shape[0], imgs1.device)
 
-    def _start_w(self, imgs1, shape, w_init, noises):
-        """Mode W: const1, w1 = E(imgs1, cond_vector) under no_grad - const1 stays as the logged constant, w1 (or `w_init`) becomes
-        the leaf, with a fresh LREQAdam on it."""
-        with torch.no_grad():
-            c0, w0 = self.E(imgs1, self.cond_vector, noises=noises)
-            self._const1 = c0.detach().clone()
-            if w_init is not None:
-                w0 = w_init.to(imgs1.device, torch.float32).reshape(shape)
-        self.w1 = w0.detach().clone().requires_grad_(True)
-        self.opt = LREQAdam([{"params": [self.w1]}], lr=self.lr, betas=(self.beta_1, 0.99), weight_decay=0)
+    def _latent_shape(self, B):
+        return (B, self.G.config.z_dim)
+
+    def _start_code(self, imgs1, shape, noises, needed):
+        """Mode W: const1, w1 = E(imgs1, cond_vector) - const1 stays as the logged constant, w1 is the start code unless `w_init` is
+        given; the call runs either way (it advances the spectral-norm buffers)."""
+        c0, w0 = self.E(imgs1, self.cond_vector, noises=noises)
+        self._const1 = c0.detach().clone()
+        return w0
 
     # ------------------------------------------------------------------ one iteration
     def _attention_terms(self, imgs1, imgs2):
-        """space_loss(mask_1, mask_2) and space_loss(cam_1, cam_2) as values (:96-107,129-140)."""
+        """space_loss(mask_1, mask_2) and space_loss(cam_1, cam_2) as values (:96-107,129-140).  Rows form: per row, every row's mask
+        towards its own arg-max class and every cam normalised on its own."""
         from .grad_cam import mask2cam
+        rows, cam = self.independent, self.grad_cam_plus_plus
+        mask_of, image_loss = (cam.call_per_image, losses.space_loss_image_rows) if rows else (cam, losses.space_loss)
         with torch.no_grad():
-            mask_1 = self.grad_cam_plus_plus(imgs1.detach(), None)
-            mask_2 = self.grad_cam_plus_plus(imgs2.detach(), None)
-            _, cam_1 = mask2cam(mask_1, imgs1)
-            _, cam_2 = mask2cam(mask_2, imgs2)
-            l_mask, info_mask = losses.space_loss(mask_1, mask_2, lpips_model=self.lpips)
-            l_cam, info_cam = losses.space_loss(cam_1, cam_2, lpips_model=self.lpips)
+            mask_1 = mask_of(imgs1.detach(), None)
+            mask_2 = mask_of(imgs2.detach(), None)
+            _, cam_1 = mask2cam(mask_1, imgs1, rows=rows)
+            _, cam_2 = mask2cam(mask_2, imgs2, rows=rows)
+            l_mask, info_mask = image_loss(mask_1, mask_2, lpips_model=self.lpips)
+            l_cam, info_cam = image_loss(cam_1, cam_2, lpips_model=self.lpips)
+        if rows:
+            l_mask, l_cam = info_mask[:, 0].contiguous(), info_cam[:, 0].contiguous()
         return dict(mask_1=mask_1, mask_2=mask_2, cam_1=cam_1, cam_2=cam_2, loss_mask=l_mask, loss_Gcam=l_cam, info_mask=info_mask,
                     info_Gcam=info_cam)
 
     def step(self, imgs1, noises=(None, None)):
-        """One iteration; `noises` = optional (E(imgs1), E(imgs2)) noise lists for parity runs (mode W: E(imgs1)'s is unused)."""
-        E = self.E
+        """One iteration; `noises` = optional (E(imgs1), E(imgs2)) noise lists for parity runs (mode W: E(imgs1)'s is unused).  The
+        attention terms are values (the script detaches them): they enter loss_msiv, not the gradient.  Rows form: an iteration of
+        every row - phase 1 back-propagates sum_b space_loss_b(imgs1, imgs2), phase 2 0.01 * sum_b space_loss_b(w1, w2), and the
+        logged values are the [B] columns of the info tensors."""
+        E, rows = self.E, self.independent
         if self.group < 0:
-            raise RuntimeError("BigEmbedStep.step: call begin_image() first")
+            raise RuntimeError(f"{type(self).__name__}.step: call begin_image() first")
+        image_loss, latent_loss = (losses.space_loss_image_rows, losses.space_loss_rows) if rows else (losses.space_loss, losses.space_loss)
         ops.zero_arena_begin(imgs1.device)
         if self.mode == "E":
             const1, w1 = E(imgs1, self.cond_vector, noises=noises[0])
@@ -201,21 +178,22 @@ class BigEmbedStep:
             w1, const1 = self.w1, self._const1
         imgs2, _ = self.G(w1, self.conditions, self.truncation)
         const2, w2 = E(imgs2, self.cond_vector, noises=noises[1])
-        loss_imgs, info_imgs = losses.space_loss(imgs1, imgs2, lpips_model=self.lpips)
+        loss_imgs, info_imgs = image_loss(imgs1, imgs2, lpips_model=self.lpips)
+        if rows:          # the returned scalar is the sum over the rows: what phase 1 back-propagates
+            loss_sum, loss_imgs = loss_imgs, info_imgs[:, 0].contiguous()
         loss_msiv, att = loss_imgs, {}
         if self.attention:
             att = self._attention_terms(imgs1, imgs2)
             loss_msiv = loss_imgs + att["loss_mask"] + att["loss_Gcam"]
-        self.opt.zero_grad()
-        loss_msiv.backward(retain_graph=True)
-        self.opt.step()
-        loss_w, info_w = losses.space_loss(w1, w2, image_space=False)
+        self._opt_phase(loss_sum if rows else loss_msiv, retain_graph=True)
+        loss_w, info_w = latent_loss(w1, w2, image_space=False)
         with torch.no_grad():
-            loss_c2, info_c2 = losses.space_loss(const1, const2, image_space=False)          # logged only
+            loss_c2, info_c2 = latent_loss(const1, const2, image_space=False)          # logged only
         loss_mslv = loss_w * 0.01
-        self.opt.zero_grad()
-        loss_mslv.backward()
-        self.opt.step()
+        self._opt_phase(loss_mslv)
+        if rows:
+            loss_w, loss_c2 = info_w[:, 0].contiguous(), info_c2[:, 0].contiguous()
+            loss_mslv = loss_w * 0.01
         w1d = w1.detach()
         self._tracker.update(loss_msiv.detach(), w1d)
         ops.zero_arena_end()
@@ -224,11 +202,6 @@ class BigEmbedStep:
                          info_w=info_w, loss_c2=loss_c2.detach(), info_c2=info_c2, loss_mslv=loss_mslv.detach(),
                          w_norm=self._tracker.l2, **att)
         return self.last
-
-    # ------------------------------------------------------------------ tracker read-out (one host read)
-    def tracker(self):
-        """The tracker's state on the host; rows form: a list with one such read-out per row."""
-        return self._tracker.read()
 
 
 class BigEmbedRowsStep(BigEmbedStep):
@@ -246,7 +219,6 @@ class BigEmbedRowsStep(BigEmbedStep):
         if kw.pop("independent", True) is not True:
             raise ValueError("BigEmbedRowsStep is the independent form; the coupled loop is BigEmbedStep")
         super().__init__(G, E, lpips_model, mode="W", **kw)
-        self.labels = None
 
     def _row_labels(self, labels, B):
         if labels is None:
@@ -261,79 +233,9 @@ class BigEmbedRowsStep(BigEmbedStep):
             raise ValueError(f"BigEmbedRowsStep: class ids must lie in [0, {K}), got {labels}")
         return tuple(labels)
 
-    def _setup(self, B, dev, labels):
-        """The per-row class conditions and condition vectors; rebuilt when the group's labels change."""
-        if self.cond_vector is not None and self.labels == labels and self.cond_vector.device == dev:
-            return
-        cfg = self.G.config
-        self.labels = labels
-        self.conditions = torch.zeros(B, cfg.num_classes, device=dev)
-        self.conditions[torch.arange(B, device=dev), torch.tensor(labels, device=dev)] = 1.0
-        with torch.no_grad():
-            embed = ops.linear(self.conditions, self.G.embeddings.weight.detach())
-        # the batch-1 draw for every row (rows 1.. of a batch-B draw are other numbers: no batch-1 run would see them)
-        z0 = truncated_noise_sample(truncation=self.z_truncation, batch_size=1, dim_z=cfg.z_dim, seed=self.iterations % 30000)
-        z0 = torch.tensor(z0, dtype=torch.float).to(dev).expand(B, -1)
-        self.cond_vector = torch.cat((z0, embed), dim=1).contiguous()
-
-    def begin_image(self, imgs1, labels=None, w_init=None, noises=None):
-        """Start a group of B images: `labels` (an int or one class id per row; default: the constructor's `label`) set the rows'
-        conditions, w1 starts from E(imgs1, cond_vector) (or `w_init`) with a fresh Adam state, and every row's tracker restarts."""
-        dev = imgs1.device
-        B = imgs1.shape[0]
-        self._setup(B, dev, self._row_labels(labels, B))
-        self.group += 1
-        shape = (B, self.G.config.z_dim)
-        self._start_w(imgs1, shape, w_init, noises)
-        self._tracker.reset(shape, dev)
-
-    def _attention_terms(self, imgs1, imgs2):
-        """Per row: space_loss_b(mask_1, mask_2) and space_loss_b(cam_1, cam_2) as values, every row's mask towards its own arg-max
-        class and every cam normalised on its own."""
-        from .grad_cam import mask2cam
-        with torch.no_grad():
-            mask_1 = self.grad_cam_plus_plus.call_per_image(imgs1.detach(), None)
-            mask_2 = self.grad_cam_plus_plus.call_per_image(imgs2.detach(), None)
-            _, cam_1 = mask2cam(mask_1, imgs1, rows=True)
-            _, cam_2 = mask2cam(mask_2, imgs2, rows=True)
-            _, info_mask = losses.space_loss_image_rows(mask_1, mask_2, lpips_model=self.lpips)
-            _, info_cam = losses.space_loss_image_rows(cam_1, cam_2, lpips_model=self.lpips)
-        return dict(mask_1=mask_1, mask_2=mask_2, cam_1=cam_1, cam_2=cam_2, loss_mask=info_mask[:, 0].contiguous(),
-                    loss_Gcam=info_cam[:, 0].contiguous(), info_mask=info_mask, info_Gcam=info_cam)
-
-    def step(self, imgs1, noises=(None, None)):
-        """One iteration of every row; `noises` as BigEmbedStep.step.  The attention terms are values (the script detaches them): they
-        enter every row's loss_msiv, and phase 1 back-propagates sum_b space_loss_b(imgs1, imgs2)."""
-        E = self.E
-        if self.group < 0:
-            raise RuntimeError("BigEmbedRowsStep.step: call begin_image() first")
-        ops.zero_arena_begin(imgs1.device)
-        w1, const1 = self.w1, self._const1
-        imgs2, _ = self.G(w1, self.conditions, self.truncation)
-        const2, w2 = E(imgs2, self.cond_vector, noises=noises[1])
-        loss_sum, info_imgs = losses.space_loss_image_rows(imgs1, imgs2, lpips_model=self.lpips)
-        loss_imgs = info_imgs[:, 0].contiguous()
-        loss_msiv, att = loss_imgs, {}
-        if self.attention:
-            att = self._attention_terms(imgs1, imgs2)
-            loss_msiv = loss_imgs + att["loss_mask"] + att["loss_Gcam"]
-        self.opt.zero_grad()
-        loss_sum.backward(retain_graph=True)
-        self.opt.step()
-        lat_sum, info_w = losses.space_loss_rows(w1, w2, image_space=False)
-        with torch.no_grad():
-            _, info_c2 = losses.space_loss_rows(const1, const2, image_space=False)          # logged only
-        self.opt.zero_grad()
-        (lat_sum * 0.01).backward()
-        self.opt.step()
-        loss_w = info_w[:, 0].contiguous()
-        w1d = w1.detach()
-        self._tracker.update(loss_msiv, w1d)
-        ops.zero_arena_end()
-        self.last = dict(w1=w1d, imgs2=imgs2.detach(), w2=w2.detach(), const1=const1.detach(), const2=const2.detach(),
-                         loss_msiv=loss_msiv, loss_imgs=loss_imgs, info_imgs=info_imgs, loss_w=loss_w, info_w=info_w,
-                         loss_c2=info_c2[:, 0].contiguous(), info_c2=info_c2, loss_mslv=loss_w * 0.01, w_norm=self._tracker.l2, **att)
-        return self.last
+    def _begin_group(self, imgs1, labels=None):
+        """`labels` of begin_image: an int or one class id per row (default: the constructor's `label`) - the rows' conditions."""
+        self._setup(self._row_labels(labels, imgs1.shape[0]), imgs1.device)
 
 
 def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0, labels=None, keep=None):
@@ -342,18 +244,10 @@ def invert_big(st, imgs1, iterations, save_every=100, out_dir=None, group=0, lab
     Returns the last result dict with the tracker read-out under "tracker".  Rows form (BigEmbedRowsStep; `labels`: one class id per
     row): files carry the image number group * B + b, Loss.txt gets a block per image, only the first `keep` rows (default: all) are
     written, and "tracker" is the list of per-row read-outs."""
-    if st.independent:
-        st.begin_image(imgs1, labels=labels)
-    elif labels is not None or keep is not None:
+    if not st.independent and (labels is not None or keep is not None):
         raise ValueError("invert_big: labels / keep belong to the rows form (BigEmbedRowsStep)")
-    else:
-        st.begin_image(imgs1)
-    r = st.last
-    for i in range(iterations):
-        r = st.step(imgs1)
-        if out_dir is not None and save_every and i % save_every == 0:
-            dump_group(st, imgs1, r, i, out_dir, group, keep, IMG_NAME, W_NAME, loss_txt=True)
-    return finish_group(st, r, imgs1.shape[0], out_dir, group, keep)
+    return invert_group(st, imgs1, iterations, "eager", save_every, out_dir, group, keep, dict(labels=labels) if st.independent else {},
+                        dict(img_name=IMG_NAME, w_name=W_NAME, loss_txt=True))
 
 
 def build_models_big_v2(config=None, img_size=256, start_features=64, compute_dtype="bf16", device="cuda", seed=0, attention=True):
@@ -371,37 +265,18 @@ def build_models_big_v2(config=None, img_size=256, start_features=64, compute_dt
 
 
 # ------------------------------------------------------------------ CLI
-def _refuse_norm(_):
-    raise argparse.ArgumentTypeError(MSG_NORM)
-
-
 def make_parser():
     p = argparse.ArgumentParser(description="BigGAN-deep real-image inversion (embedding_v2_BigGAN.py)")
-    p.add_argument("--iterations", type=int, default=DEFAULTS["iterations"])
-    p.add_argument("--lr", type=float, default=DEFAULTS["lr"])
-    p.add_argument("--beta_1", type=float, default=DEFAULTS["beta_1"])
-    p.add_argument("--batch_size", type=int, default=DEFAULTS["batch_size"])
-    p.add_argument("--experiment_dir", default=None)
-    add_model_args(p)
-    p.set_defaults(mtype=4, img_size=DEFAULTS["img_size"], z_dim=DEFAULTS["z_dim"], start_features=DEFAULTS["start_features"])
-    p.add_argument("--img_dir", default="./bigGAN_inversion/id30/", help="a directory of images or a .pt tensor in [0,1]")
-    p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise the latent directly")
+    add_inversion_args(p, DEFAULTS, 4, "./bigGAN_inversion/id30/", "the latent", launch=False)
+    p.set_defaults(img_size=DEFAULTS["img_size"], z_dim=DEFAULTS["z_dim"], start_features=DEFAULTS["start_features"])
     p.add_argument("--attention", type=strict_bool, default=True, help="false: leave the Grad-CAM++ mask / cam terms out of loss_msiv")
     p.add_argument("--label", type=int, default=DEFAULTS["label"], help="ImageNet class id of the condition (30: frog)")
-    p.add_argument("--independent", type=strict_bool, default=False,
-                   help="true (with --optimizeE false): every image of a batch is an inversion of its own, equal to its batch-1 run")
     p.add_argument("--labels", default=None, help="with --independent true: one class id per image in the sorted order of --img_dir, "
                                                   "as a comma list or a text file with one id per line (default: --label for all)")
     p.add_argument("--truncation", type=float, default=DEFAULTS["truncation"])
-    p.add_argument("--beta", type=_refuse_norm, default=None, help="not offered: the norm term is commented out in the script")
-    p.add_argument("--norm_p", type=_refuse_norm, default=None, help="not offered: the norm term is commented out in the script")
+    p.add_argument("--beta", type=_refuse(MSG_NORM), default=None, help="not offered: the norm term is commented out in the script")
+    p.add_argument("--norm_p", type=_refuse(MSG_NORM), default=None, help="not offered: the norm term is commented out in the script")
     p.add_argument("--vgg16_weights", default=None, help="torchvision vgg16 checkpoint for the attention terms (seeded stand-in without)")
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--save_every", type=int, default=100)
-    p.add_argument("--vgg_weights", default=None)
-    p.add_argument("--lpips_weights", default=None)
-    p.add_argument("--allow_standin_lpips", action="store_true")
-    p.add_argument("--deterministic", action="store_true")
     return p
 
 
@@ -453,11 +328,7 @@ def main(argv=None):
         E.load_state_dict(torch.load(args.checkpoint_dir_E, map_location="cpu"))
     if vgg is not None and args.vgg16_weights:
         vgg.load_pretrained(args.vgg16_weights)
-    load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
-    out = args.experiment_dir or "./result_bigGAN_id30_GradCAM/mis_aligh_bigGAN_v1_opE"
-    for sub in ("", "imgs", "models", "summaries"):
-        os.makedirs(os.path.join(out, sub), exist_ok=True)
-    imgs = _load_imgs(args.img_dir, args.img_size, dev)
+    out, imgs = open_run(args, LP, "./result_bigGAN_id30_GradCAM/mis_aligh_bigGAN_v1_opE", dev)
     kw = dict(vgg16=vgg, attention=args.attention, label=args.label, lr=args.lr, beta_1=args.beta_1, truncation=args.truncation,
               iterations=args.iterations)
     labels = None
@@ -466,9 +337,7 @@ def main(argv=None):
         st = BigEmbedRowsStep(G, E, LP, **kw)
     else:
         st = BigEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", **kw)
-    invert_folder(lambda imgs1, **gk: invert_big(st, imgs1, args.iterations, save_every=args.save_every, out_dir=out, **gk),
-                  imgs, args.batch_size, args.independent, out, labels=labels, save_imgs=True)
-    return st
+    return run_inversion(args, st, invert_big, imgs, out, labels=labels, save_imgs=True)
 
 
 if __name__ == "__main__":

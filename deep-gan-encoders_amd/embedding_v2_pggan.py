@@ -23,7 +23,7 @@ Decisions (none of them is taken from a PGGAN script: there is none):
   * The mode-W start code is E(imgs1) detached, or `w_init` if given (StyleGAN1's start; a random z would start far from the image).
   * The defaults are StyleGAN1's: iterations 1501, lr 0.005, beta_1 0, beta 1e-3, norm_p 2, and the tracker rules are
     tracker_rules("sg1", iterations) - armed at iterations // 2, hysteresis 1.05, minima restart per group.
-  * capture() / replay() are LatentEmbedStep's: E_PG's noise draws go through enc_steps.draw_noises and the device seed scalar, the
+  * capture() / replay() are those of every LatentEmbedStep (embed_step.TwoPhaseEmbedStep): E_PG's noise draws go through enc_steps.draw_noises and the device seed scalar, the
     generator is called with lod=0 (validated once here: the captured iteration cannot read the `lod` buffer back).
   * independent=True (mode W): one tracker per row, per-row losses, ||z[b]||_p per row, as embedding_v2 describes it.
   * Refused with a message: independent with mode E, more than one process, --encoder be, --truncation (PGGAN has neither a W+
@@ -33,14 +33,13 @@ Decisions (none of them is taken from a PGGAN script: there is none):
 """
 import argparse
 import math
-import os
 
 import torch
 
 from . import ops
-from .embedding import select_launch
-from .embedding_v2 import DEFAULTS as _V2_DEFAULTS, LatentEmbedStep, _load_imgs, dump_group, finish_group, invert_folder, strict_bool
-from .models import add_model_args, load_lpips_weights
+from .embed_step import several_processes
+from .embedding_v2 import DEFAULTS as _V2_DEFAULTS, LatentEmbedStep, _refuse, add_inversion_args, invert_group, load_generator_smooth, \
+    open_run, run_inversion
 
 DEFAULTS = {k: _V2_DEFAULTS[1][k] for k in ("iterations", "lr", "beta_1", "beta", "norm_p")}          # StyleGAN1's
 MSG_INDEPENDENT = "PGEmbedStep: independent=True needs mode 'W': in mode 'E' one encoder is shared by the rows of a group"
@@ -56,7 +55,7 @@ class PGEmbedStep(LatentEmbedStep):
                  events_cap=256, seed=0, independent=False):
         if independent and mode == "E":
             raise ValueError(MSG_INDEPENDENT)
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        if several_processes():
             raise ValueError(MSG_DIST)
         if not getattr(E, "pggan", False):
             raise ValueError("PGEmbedStep: the encoder needs its z head (PGBE(pggan=True))")
@@ -80,19 +79,8 @@ def invert_pg(st, imgs1, iterations, launch="graph", save_every=100, out_dir=Non
     """`iterations` iterations on one image group, as embedding_v2.invert_v2 (launch="graph": the iteration is captured once and
     replayed; later groups go through set_image).  With `out_dir` the every-`save_every` dumps (image pair, per-row z, a Loss.txt
     block) and, at the end, the tracker's files.  Returns the last result dict with the tracker read-out under "tracker"."""
-    st.begin_image(imgs1, w_init=w_init)
-    if launch not in ("graph", "eager"):
-        raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
-    run, done = select_launch(st, imgs1, launch)
-    r = st.last
-    dumps = out_dir is not None and save_every
-    if done and dumps:
-        dump_group(st, imgs1, _loss_txt_infos(r), 0, out_dir, group, keep, loss_txt=True)          # iteration 0 ran as capture()'s warm-up
-    for i in range(done, iterations):
-        r = run()
-        if dumps and i % save_every == 0:
-            dump_group(st, imgs1, _loss_txt_infos(r), i, out_dir, group, keep, loss_txt=True)
-    return finish_group(st, r, imgs1.shape[0], out_dir, group, keep)
+    return invert_group(st, imgs1, iterations, launch, save_every, out_dir, group, keep, dict(w_init=w_init), dict(loss_txt=True),
+                        infos=_loss_txt_infos)
 
 
 def build_models_pg_v2(img_size=1024, start_features=16, compute_dtype="bf16", device="cuda", seed=0, lpips=True, fmaps_base=None,
@@ -116,43 +104,19 @@ def load_checkpoints(G, E, gan=None, enc=None):
     """The --mtype 3 containers of models.load_models: the generator a dict holding `generator_smooth` (or `generator`), the encoder
     a bare state_dict."""
     if gan:
-        ckpt = torch.load(gan, map_location="cpu")
-        G.load_state_dict(ckpt["generator_smooth"] if "generator_smooth" in ckpt else ckpt["generator"])
+        load_generator_smooth(G, gan)
     if enc:
         E.load_state_dict(torch.load(enc, map_location="cpu"))
 
 
 # ------------------------------------------------------------------ CLI
-def _refuse(msg):
-    def parse(_):
-        raise argparse.ArgumentTypeError(msg)
-    return parse
-
-
 def make_parser():
     p = argparse.ArgumentParser(description="PGGAN real-image inversion with the E_PG encoder (the v2 loop of embedding_v2_styleGAN1.py)")
-    p.add_argument("--iterations", type=int, default=DEFAULTS["iterations"])
-    p.add_argument("--lr", type=float, default=DEFAULTS["lr"])
-    p.add_argument("--beta_1", type=float, default=DEFAULTS["beta_1"])
-    p.add_argument("--batch_size", type=int, default=1)
-    p.add_argument("--experiment_dir", default=None)
-    add_model_args(p)
-    p.set_defaults(mtype=3)
-    p.add_argument("--img_dir", default="./real_imgs/", help="a directory of images or a .pt tensor in [0,1]")
-    p.add_argument("--optimizeE", type=strict_bool, default=True, help="true: fine-tune the encoder; false: optimise z directly")
-    p.add_argument("--independent", type=strict_bool, default=False,
-                   help="true (with --optimizeE false): every image of a batch is an inversion of its own, equal to its batch-1 run")
+    add_inversion_args(p, DEFAULTS, 3, "./real_imgs/", "z")
     p.add_argument("--beta", type=float, default=DEFAULTS["beta"], help="weight of ||z||_p")
     p.add_argument("--norm_p", type=int, default=DEFAULTS["norm_p"], help="p of ||z||_p")
     p.add_argument("--encoder", type=_refuse(MSG_ENCODER), default=None, help="not offered: E_PG is the encoder of this loop")
     p.add_argument("--truncation", type=_refuse(MSG_TRUNCATION), default=None, help="not offered: PGGAN has no W+ code")
-    p.add_argument("--launch", choices=("eager", "graph"), default="graph")
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--save_every", type=int, default=100)
-    p.add_argument("--vgg_weights", default=None)
-    p.add_argument("--lpips_weights", default=None)
-    p.add_argument("--allow_standin_lpips", action="store_true")
-    p.add_argument("--deterministic", action="store_true")
     return p
 
 
@@ -163,8 +127,7 @@ def parse_args(argv=None):
                          "dge_amd.embedding_v2_biggan")
     if args.independent and args.optimizeE:
         raise SystemExit("embedding_v2_pggan: --independent true needs --optimizeE false (the fine-tuned encoder is shared by a group)")
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1 or \
-            int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if several_processes(env=True):
         raise SystemExit("embedding_v2_pggan: " + MSG_DIST.split(": ", 1)[1])
     return args
 
@@ -177,16 +140,10 @@ def main(argv=None):
     G, E, LP = build_models_pg_v2(args.img_size, args.start_features, args.compute_dtype, device=dev, seed=args.seed,
                                   fmaps_base=args.fmaps_base, fmaps_max=args.fmaps_max, enc_maxf=args.enc_maxf)
     load_checkpoints(G, E, args.checkpoint_dir_GAN, args.checkpoint_dir_E)
-    load_lpips_weights(LP, args.vgg_weights, args.lpips_weights, allow_standin=args.allow_standin_lpips)
-    out = args.experiment_dir or "./realimg_embedding_result/pggan"
-    for sub in ("", "imgs", "models", "summaries"):
-        os.makedirs(os.path.join(out, sub), exist_ok=True)
-    imgs = _load_imgs(args.img_dir, args.img_size, dev)
+    out, imgs = open_run(args, LP, "./realimg_embedding_result/pggan", dev)
     st = PGEmbedStep(G, E, LP, mode="E" if args.optimizeE else "W", lr=args.lr, beta_1=args.beta_1, beta=args.beta, norm_p=args.norm_p,
                      iterations=args.iterations, seed=args.seed, independent=args.independent)
-    invert_folder(lambda imgs1, **kw: invert_pg(st, imgs1, args.iterations, launch=args.launch, save_every=args.save_every, out_dir=out, **kw),
-                  imgs, args.batch_size, args.independent, out)
-    return st
+    return run_inversion(args, st, invert_pg, imgs, out)
 
 
 if __name__ == "__main__":

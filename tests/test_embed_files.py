@@ -1,5 +1,5 @@
-"""The files the inversion loops write (dge_amd.embedding_v2.invert_v2, dge_amd.embedding_v2_biggan.invert_big,
-write_tracker_files): names, the text of loss_min.txt and Loss.txt, and every saved latent.  A duck-typed step stands in for the
+"""The files the inversion loops write (dge_amd.embedding_v2.invert_v2, dge_amd.embedding_v2_pggan.invert_pg,
+dge_amd.embedding_v2_biggan.invert_big, write_tracker_files): names, the text of loss_min.txt and Loss.txt, and every saved latent.  A duck-typed step stands in for the
 GPU loops, so this runs on the CPU without the library.  Every expectation below is a literal recorded once from the commit before
 the dump / tracker-file code was shared (this file passes there unchanged), not from the code under test.
 
@@ -14,11 +14,12 @@ B, ITERS, SAVE_EVERY, GROUP, KEEP = 3, 5, 2, 1, 2
 
 class FakeStep:
     """step() of iteration i returns: w1 = arange(36).reshape(3,3,4) + 100*i, w_norm 2 + i (row b: + b/4), loss_msiv 0.5 + i/4 (row b:
-    + b/8), infos arange(8)/2 + i + 10*k for the k-th info tensor (row b: + 100*b)."""
+    + b/8), infos arange(8)/2 + i + 10*k for the k-th info tensor (row b: + 100*b).  `info_img` (the "pg" form): also the window
+    rows of embedding_v2's image loss, info_img[w] = the info tensor number 5 + w -> [3,8] (rows form [B,3,8])."""
     captured = False
 
-    def __init__(self, independent, attention=True):
-        self.independent, self.attention = independent, attention
+    def __init__(self, independent, attention=True, info_img=False):
+        self.independent, self.attention, self.info_img = independent, attention, info_img
         self.last = {}
         self.i = 0
         self.begun = []
@@ -39,6 +40,9 @@ class FakeStep:
         for k, name in enumerate(names):
             info = torch.arange(8, dtype=torch.float32) / 2 + i + 10 * k
             r[name] = (info[None] + 100 * col[:, None]) if rows else info
+        if self.info_img:
+            img = torch.arange(8, dtype=torch.float32) / 2 + i + 10 * torch.arange(5, 8, dtype=torch.float32)[:, None]
+            r["info_img"] = (img[None] + 100 * col[:, None, None]) if rows else img
         self.last = r
         return r
 
@@ -55,16 +59,17 @@ class FakeStep:
 def run(which, rows, tmp_path, attention=True, out=True):
     from dge_amd.embedding_v2 import invert_v2
     from dge_amd.embedding_v2_biggan import invert_big
+    from dge_amd.embedding_v2_pggan import invert_pg
     out_dir = None
     if out:
         out_dir = str(tmp_path)
         for sub in ("imgs", "models"):
             os.makedirs(os.path.join(out_dir, sub))
-    st = FakeStep(rows, attention)
+    st = FakeStep(rows, attention, info_img=which == "pg")
     imgs1 = torch.linspace(1, -1, B * 3 * 8 * 8).reshape(B, 3, 8, 8)
     kw = dict(save_every=SAVE_EVERY, out_dir=out_dir, group=GROUP, **(dict(keep=KEEP) if rows else {}))
-    if which == "v2":
-        r = invert_v2(st, imgs1, ITERS, launch="eager", **kw)
+    if which in ("v2", "pg"):
+        r = (invert_v2 if which == "v2" else invert_pg)(st, imgs1, ITERS, launch="eager", **kw)
     else:
         r = invert_big(st, imgs1, ITERS, **kw)
     assert st.i == ITERS and len(st.begun) == 1
@@ -446,8 +451,99 @@ EXPECT = {'v2_coupled': {'names': ['imgs/id1_ep0-norm2.00-imgLoss0.500000.jpg',
                             'models/id4-iter3-norm-min4.250000-imgLoss2.250000.pt': ((1, 3, 4), 10000.0),
                             'models/id4-iter4-norm6.500000-imgLoss-min1.750000.pt': ((1, 3, 4), 2000.0)}}}
 
+# The "pg" forms (embedding_v2_pggan.invert_pg), recorded from the commit before the three per-group loops were shared with only this
+# file changed: the names, loss_min.txt and the saved latents are those of the "v2" forms, plus a Loss.txt whose image-space lines
+# are the window rows of `info_img` (small = row 2, medium = row 1, imgs = row 0).
+_HEAD = '[loss_imgs_mse[img,img_mean,img_std], loss_imgs_kl, loss_imgs_cosine, loss_imgs_ssim, loss_imgs_lpips]\n'
+_PG_LOSS_TXT = {
+    'pg_coupled': 'id_1_____i_0\n' + _HEAD +
+                  '---------ImageSpace--------\n'
+                  'loss_small_info: [[70.5, 71.0, 71.5], 72.0, 72.5, 73.0, 73.5]\n'
+                  'loss_medium_info: [[60.5, 61.0, 61.5], 62.0, 62.5, 63.0, 63.5]\n'
+                  'loss_imgs_info: [[50.5, 51.0, 51.5], 52.0, 52.5, 53.0, 53.5]\n'
+                  '---------LatentSpace--------\n'
+                  'loss_w_info: [[30.5, 31.0, 31.5], 32.0, 32.5, 33.0, 33.5]\n'
+                  'loss_c2_info: [[40.5, 41.0, 41.5], 42.0, 42.5, 43.0, 43.5]\n'
+                  'Img_loss: 0.5\n'
+                  'id_1_____i_2\n' + _HEAD +
+                  '---------ImageSpace--------\n'
+                  'loss_small_info: [[72.5, 73.0, 73.5], 74.0, 74.5, 75.0, 75.5]\n'
+                  'loss_medium_info: [[62.5, 63.0, 63.5], 64.0, 64.5, 65.0, 65.5]\n'
+                  'loss_imgs_info: [[52.5, 53.0, 53.5], 54.0, 54.5, 55.0, 55.5]\n'
+                  '---------LatentSpace--------\n'
+                  'loss_w_info: [[32.5, 33.0, 33.5], 34.0, 34.5, 35.0, 35.5]\n'
+                  'loss_c2_info: [[42.5, 43.0, 43.5], 44.0, 44.5, 45.0, 45.5]\n'
+                  'Img_loss: 1.0\n'
+                  'id_1_____i_4\n' + _HEAD +
+                  '---------ImageSpace--------\n'
+                  'loss_small_info: [[74.5, 75.0, 75.5], 76.0, 76.5, 77.0, 77.5]\n'
+                  'loss_medium_info: [[64.5, 65.0, 65.5], 66.0, 66.5, 67.0, 67.5]\n'
+                  'loss_imgs_info: [[54.5, 55.0, 55.5], 56.0, 56.5, 57.0, 57.5]\n'
+                  '---------LatentSpace--------\n'
+                  'loss_w_info: [[34.5, 35.0, 35.5], 36.0, 36.5, 37.0, 37.5]\n'
+                  'loss_c2_info: [[44.5, 45.0, 45.5], 46.0, 46.5, 47.0, 47.5]\n'
+                  'Img_loss: 1.5\n',
+    'pg_rows': 'id_3_____i_0\n' + _HEAD +
+               '---------ImageSpace--------\n'
+               'loss_small_info: [[70.5, 71.0, 71.5], 72.0, 72.5, 73.0, 73.5]\n'
+               'loss_medium_info: [[60.5, 61.0, 61.5], 62.0, 62.5, 63.0, 63.5]\n'
+               'loss_imgs_info: [[50.5, 51.0, 51.5], 52.0, 52.5, 53.0, 53.5]\n'
+               '---------LatentSpace--------\n'
+               'loss_w_info: [[30.5, 31.0, 31.5], 32.0, 32.5, 33.0, 33.5]\n'
+               'loss_c2_info: [[40.5, 41.0, 41.5], 42.0, 42.5, 43.0, 43.5]\n'
+               'Img_loss: 0.5\n'
+               'id_4_____i_0\n' + _HEAD +
+               '---------ImageSpace--------\n'
+               'loss_small_info: [[170.5, 171.0, 171.5], 172.0, 172.5, 173.0, 173.5]\n'
+               'loss_medium_info: [[160.5, 161.0, 161.5], 162.0, 162.5, 163.0, 163.5]\n'
+               'loss_imgs_info: [[150.5, 151.0, 151.5], 152.0, 152.5, 153.0, 153.5]\n'
+               '---------LatentSpace--------\n'
+               'loss_w_info: [[130.5, 131.0, 131.5], 132.0, 132.5, 133.0, 133.5]\n'
+               'loss_c2_info: [[140.5, 141.0, 141.5], 142.0, 142.5, 143.0, 143.5]\n'
+               'Img_loss: 0.625\n'
+               'id_3_____i_2\n' + _HEAD +
+               '---------ImageSpace--------\n'
+               'loss_small_info: [[72.5, 73.0, 73.5], 74.0, 74.5, 75.0, 75.5]\n'
+               'loss_medium_info: [[62.5, 63.0, 63.5], 64.0, 64.5, 65.0, 65.5]\n'
+               'loss_imgs_info: [[52.5, 53.0, 53.5], 54.0, 54.5, 55.0, 55.5]\n'
+               '---------LatentSpace--------\n'
+               'loss_w_info: [[32.5, 33.0, 33.5], 34.0, 34.5, 35.0, 35.5]\n'
+               'loss_c2_info: [[42.5, 43.0, 43.5], 44.0, 44.5, 45.0, 45.5]\n'
+               'Img_loss: 1.0\n'
+               'id_4_____i_2\n' + _HEAD +
+               '---------ImageSpace--------\n'
+               'loss_small_info: [[172.5, 173.0, 173.5], 174.0, 174.5, 175.0, 175.5]\n'
+               'loss_medium_info: [[162.5, 163.0, 163.5], 164.0, 164.5, 165.0, 165.5]\n'
+               'loss_imgs_info: [[152.5, 153.0, 153.5], 154.0, 154.5, 155.0, 155.5]\n'
+               '---------LatentSpace--------\n'
+               'loss_w_info: [[132.5, 133.0, 133.5], 134.0, 134.5, 135.0, 135.5]\n'
+               'loss_c2_info: [[142.5, 143.0, 143.5], 144.0, 144.5, 145.0, 145.5]\n'
+               'Img_loss: 1.125\n'
+               'id_3_____i_4\n' + _HEAD +
+               '---------ImageSpace--------\n'
+               'loss_small_info: [[74.5, 75.0, 75.5], 76.0, 76.5, 77.0, 77.5]\n'
+               'loss_medium_info: [[64.5, 65.0, 65.5], 66.0, 66.5, 67.0, 67.5]\n'
+               'loss_imgs_info: [[54.5, 55.0, 55.5], 56.0, 56.5, 57.0, 57.5]\n'
+               '---------LatentSpace--------\n'
+               'loss_w_info: [[34.5, 35.0, 35.5], 36.0, 36.5, 37.0, 37.5]\n'
+               'loss_c2_info: [[44.5, 45.0, 45.5], 46.0, 46.5, 47.0, 47.5]\n'
+               'Img_loss: 1.5\n'
+               'id_4_____i_4\n' + _HEAD +
+               '---------ImageSpace--------\n'
+               'loss_small_info: [[174.5, 175.0, 175.5], 176.0, 176.5, 177.0, 177.5]\n'
+               'loss_medium_info: [[164.5, 165.0, 165.5], 166.0, 166.5, 167.0, 167.5]\n'
+               'loss_imgs_info: [[154.5, 155.0, 155.5], 156.0, 156.5, 157.0, 157.5]\n'
+               '---------LatentSpace--------\n'
+               'loss_w_info: [[134.5, 135.0, 135.5], 136.0, 136.5, 137.0, 137.5]\n'
+               'loss_c2_info: [[144.5, 145.0, 145.5], 146.0, 146.5, 147.0, 147.5]\n'
+               'Img_loss: 1.625\n'}
+for _form, _txt in _PG_LOSS_TXT.items():
+    _v2 = EXPECT["v2" + _form[2:]]
+    EXPECT[_form] = dict(names=["Loss.txt"] + _v2["names"], texts=dict(_v2["texts"], **{"Loss.txt": _txt}), pts=_v2["pts"])
 
-@pytest.mark.parametrize("form", ["v2_coupled", "v2_rows", "big_coupled", "big_rows", "big_coupled_noatt", "big_rows_noatt"])
+
+@pytest.mark.parametrize("form", ["v2_coupled", "v2_rows", "big_coupled", "big_rows", "big_coupled_noatt", "big_rows_noatt", "pg_coupled",
+                                  "pg_rows"])
 def test_files_of_an_inversion(form, tmp_path):
     which, kind = form.split("_", 1)
     st, r = run(which, kind.startswith("rows"), tmp_path, attention=not kind.endswith("noatt"))
@@ -461,7 +557,7 @@ def test_files_of_an_inversion(form, tmp_path):
     assert torch.equal(r["w1"], st.last["w1"])
 
 
-@pytest.mark.parametrize("which", ["v2", "big"])
+@pytest.mark.parametrize("which", ["v2", "big", "pg"])
 @pytest.mark.parametrize("rows", [False, True])
 def test_without_out_dir_nothing_is_written(which, rows, tmp_path):
     st, r = run(which, rows, tmp_path, out=False)

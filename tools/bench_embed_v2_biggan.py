@@ -81,7 +81,7 @@ def bench_loop():
     for mode in ("W", "E"):
         G, E, LP, vgg = build_models_big_v2(None, a.img_size, a.start_features, a.dtype, seed=0, attention=a.attention)
         st = BigEmbedStep(G, E, LP, mode=mode, vgg16=vgg, attention=a.attention, iterations=1501)
-        st._setup(B, torch.device("cuda", torch.cuda.current_device()))
+        st._setup((st.label,) * B, torch.device("cuda", torch.cuda.current_device()))
         with torch.no_grad():
             imgs1 = G(st.cond_vector[:, :G.config.z_dim].contiguous(), st.conditions, st.truncation)[0].detach().clamp(-1, 1).contiguous()
         st.begin_image(imgs1)
@@ -111,7 +111,7 @@ def bench_independent():
     runs = {}
 
     def add(name, st, B, **kw):
-        st._setup(B, dev, *([tuple(labels[b % 8] for b in range(B))] if kw else []))
+        st._setup(tuple(labels[b % 8] for b in range(B)) if kw else (st.label,) * B, dev)
         with torch.no_grad():
             imgs1 = G(st.cond_vector[:, :G.config.z_dim].contiguous(), st.conditions, st.truncation)[0].detach().clamp(-1, 1).contiguous()
         runs[name] = (st, imgs1, B, kw)
