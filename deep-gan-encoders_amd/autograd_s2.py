@@ -114,102 +114,110 @@ def synthesis_run(mod, wp, randomize_noise=False, save=False):
     return results, saved
 
 
-def synthesis_backward(mod, wp, saved, g_image):
-    """d(image)/d(wp) contracted with g_image [B,3,R,R] -> g_wp [B,num_layers,512].
+def _torgb_adjoint(mod, saved, i, g_img, x_in, emit):
+    """The toRGB block that reads x_in, the output of layer i - 1 (even layers carry one): (its gradient w.r.t. x_in - the addend
+    of layer i's data gradient - or None, g_img brought down to the resolution of the block below).  The block's style gradient goes
+    to emit(g_srgb, block, row of g_wp)."""
+    if i < 1 or (i - 1) % 2:
+        return None, g_img
+    k = (i - 1) // 2
+    O = getattr(mod, f"output{k}")
+    addend, g_srgb = ops.torgb_bwd(g_img, x_in, O.weight.detach().reshape(3, -1), saved["rgb"][k]["s"], O.wscale)
+    emit(g_srgb, O, i)
+    return addend, (ops.up2_bwd(g_img) if k > 0 else g_img)
 
-    The gradient travels down the chain as g_z (w.r.t. the pre-activation z = yraw*d + noise*ns + bias of each layer,
-    stylegan2_generator.py:908-921): the data-gradient conv of layer i+1 differentiates layer i's noise / bias / lrelu tail in its own
-    epilogue (it streams layer i's stored output as `dot_src` anyway) and also leaves the two per-(b,c) sums of the demodulation
-    gradient there; the demodulation factor d multiplies g_z in the NEXT conv's prologue.  `fused=False` (deterministic mode) runs
-    the same math with the tail backward as a pass of its own (dge_modconv_bwd_prep)."""
-    B = wp.shape[0]
-    dev = wp.device
-    nl = mod.num_layers
-    g_wp = ops.zeros((B, nl, mod.w_space_dim), dev)
-    layers = saved["layers"]
-    dt = ops.dtype_of(saved["const"])
-    g_img = g_image.float().contiguous()
-    fused = not ops.is_deterministic()
+
+def _style_grads(L, rec, dt, R, st, g_wp_row):
+    """style / demodulation gradients of a layer whose tail backward ran as a pass of its own (sums in R), st [B,in_c,2] -> g_wp[:, i]"""
+    B = st.shape[0]
+    t = ops.demod_bwd(R, rec["d"], L.bias.detach(), L.noise_strength.detach().reshape(1), L.bscale)
+    gs_view = st.view(B, -1)      # [B, 2*Cin]: element (b, 2*i) = g_s[b,i]
+    ops.linear_t(t, L._prepared(dt)[1], gs_view, mul=rec["s"], accumulate=True, incy=2, ldy=2 * L.in_c)
+    ops.linear_t(gs_view, L.style.weight.detach(), g_wp_row, scale=L.style.wscale, accumulate=True, incx=2, ldx=2 * L.in_c, O=L.in_c)
+
+
+def _backward_fused(mod, saved, g_img, g_wp, dt):
+    """Atomics mode.  The gradient travels down the chain as g_z, w.r.t. the pre-activation of each layer: the data-gradient launch
+    of layer i + 1 differentiates layer i's noise / bias / lrelu tail in its own epilogue (`prep`: it streams layer i's stored
+    output as dot_src anyway) and leaves the two per-(b,c) sums of the demodulation gradient in P; the demodulation factor d
+    multiplies g_z in the NEXT launch.  Every style gradient leaves in ONE launch at the end (dge_s2_style_grads): none feeds the
+    chain.  Where the route of layer i + 1 does not take prep (s2_conv.dgrad_route), layer i runs its tail as a pass of its own and
+    finishes its style gradient as the deterministic chain does."""
+    B, dev, layers, top = g_wp.shape[0], g_wp.device, saved["layers"], mod.num_layers - 2
+    blocks = []
+    emit = lambda g_srgb, O, row: blocks.append(dict(gs=g_srgb, wstyle=O.style.weight.detach(), row=row))
     # top layer: its output only feeds the last toRGB (image_k = rgb_k + up(image_{k-1}), :515-522)
-    top = nl - 2
     Lt, Ot = getattr(mod, f"layer{top}"), getattr(mod, f"output{top // 2}")
-    P = None
-    if fused:
-        g_x, g_srgb, P = ops.torgb_bwd_prep(g_img, layers[top]["y"], Ot.weight.detach().reshape(3, -1), saved["rgb"][top // 2]["s"], Ot.wscale,
-                                            layers[top]["noise"], Lt.noise_strength.detach().reshape(1), Lt.gain)
-    else:
-        g_x, g_srgb = ops.torgb_bwd(g_img, layers[top]["y"], Ot.weight.detach().reshape(3, -1), saved["rgb"][top // 2]["s"], Ot.wscale)
-    # fused mode: every style gradient leaves in ONE launch at the end (dge_s2_style_grads) - none of them feeds the chain
-    blocks = [] if fused else None
-    if fused:
-        blocks.append(dict(gs=g_srgb, wstyle=Ot.style.weight.detach(), row=top + 1))
-    else:
-        ops.linear_t(g_srgb, Ot.style.weight.detach(), g_wp[:, top + 1], scale=Ot.style.wscale, accumulate=True)
+    g_x, g_srgb, P = ops.torgb_bwd_prep(g_img, layers[top]["y"], Ot.weight.detach().reshape(3, -1), saved["rgb"][top // 2]["s"], Ot.wscale,
+                                        layers[top]["noise"], Lt.noise_strength.detach().reshape(1), Lt.gain)
+    emit(g_srgb, Ot, top + 1)
     if top // 2 > 0:
         g_img = ops.up2_bwd(g_img)
     for i in range(top, -1, -1):
-        L = getattr(mod, f"layer{i}")
-        rec = layers[i]
-        # ---- backward through noise/bias/act/demod of layer i
+        L, rec = getattr(mod, f"layer{i}"), layers[i]
         if P is not None:
-            g_y, d_in = g_x, rec["d"]                  # g_x is g_z already (with its sums in P); d joins in the conv prologue
+            g_y, d_in = g_x, rec["d"]                  # g_x is g_z already (with its sums in P); d joins in the launch
         else:
             R = ops.zeros((B, L.out_c, 3), dev)
             g_y, d_in = ops.modconv_bwd_prep(g_x, rec["y"], rec["d"], rec["noise"], L.gain, R), None
         x_in = saved["const"] if i == 0 else layers[i - 1]["y"]
-        # toRGB gradient of the previous (even) layer joins through the epilogue addend
-        addend = None
-        if i >= 1 and (i - 1) % 2 == 0:
-            kp = (i - 1) // 2
-            Op = getattr(mod, f"output{kp}")
-            # g_img has already been brought down to this resolution by up2_bwd above
-            addend, g_srgb = ops.torgb_bwd(g_img, x_in, Op.weight.detach().reshape(3, -1), saved["rgb"][kp]["s"], Op.wscale)
-            if fused:
-                blocks.append(dict(gs=g_srgb, wstyle=Op.style.weight.detach(), row=i))
-            else:
-                ops.linear_t(g_srgb, Op.style.weight.detach(), g_wp[:, i], scale=Op.style.wscale, accumulate=True)
-            if kp > 0:
-                g_img = ops.up2_bwd(g_img)
-        st = ops.SlotStats(B, L.in_c, dev) if fused else ops.zeros((B, L.in_c, 2), dev)
+        addend, g_img = _torgb_adjoint(mod, saved, i, g_img, x_in, emit)
+        st = ops.SlotStats(B, L.in_c, dev)
+        route = s2_conv.dgrad_route(L, B, dt, True, d_in is not None)
         prep, P_next = None, None
-        if fused and i >= 1 and s2_conv.dgrad_takes_prep(L, B, dt):
+        if route.takes_prep and i >= 1:
             Lp = getattr(mod, f"layer{i - 1}")
             P_next = ops.SlotStats(B, L.in_c, dev)
             prep = dict(gain=Lp.gain, noise=layers[i - 1]["noise"], ns=Lp.noise_strength.detach().reshape(1), stats=P_next)
-        g_xprev = s2_conv.dgrad(L, g_y, d_in, dt, fused, prep=prep, out_scale=rec["s"], addend=addend, stats=st, dot_src=x_in)
-        # ---- style / demodulation gradients -> g_wp[:, i]
-        _, wsq = L._prepared(dt)
-        if fused and P is not None:
-            blocks.append(dict(P=P, st=st, d=rec["d"], s=rec["s"], bias=L.bias.detach(), wsq=wsq, bscale=L.bscale,
-                               wstyle=L.style.weight.detach(), row=i))
-            g_x, P = g_xprev, P_next
-            continue
-        if fused:            # (a layer whose tail backward ran as a pass of its own: its sums sit in R)
-            st_t = ops.zeros((B, L.in_c, 2), dev)
-            ops.check(ops.lib().dge_sum_slots(ops._p(st.buf), ops._p(st_t), st.nslot, st_t.numel(), 0, ops._stream()), "dge_sum_slots")
-            st = st_t
+        g_x = s2_conv.dgrad(L, route, g_y, d_in, dt, prep, rec["s"], addend, st, x_in)
         if P is not None:
-            t = ops.demod_bwd_prep(P, rec["d"], L.bias.detach(), L.bscale)
+            blocks.append(dict(P=P, st=st, d=rec["d"], s=rec["s"], bias=L.bias.detach(), wsq=L._prepared(dt)[1], bscale=L.bscale,
+                               wstyle=L.style.weight.detach(), row=i))
         else:
-            t = ops.demod_bwd(R, rec["d"], L.bias.detach(), L.noise_strength.detach().reshape(1), L.bscale)
-        gs_view = st.view(B, -1)      # [B, 2*Cin]: element (b, 2*i) = g_s[b,i]
-        ops.linear_t(t, wsq, gs_view, mul=rec["s"], accumulate=True, incy=2, ldy=2 * L.in_c)
-        ops.linear_t(gs_view, L.style.weight.detach(), g_wp[:, i], scale=L.style.wscale, accumulate=True, incx=2,
-                     ldx=2 * L.in_c, O=L.in_c)
-        g_x, P = g_xprev, P_next
-    if blocks:
-        ops.s2_style_grads(blocks, g_wp, getattr(mod, "layer0").style.wscale)
+            _style_grads(L, rec, dt, R, ops.sum_slots(st.buf, ops.zeros((B, L.in_c, 2), dev), accumulate=False), g_wp[:, i])
+        P = P_next
+    ops.s2_style_grads(blocks, g_wp, getattr(mod, "layer0").style.wscale)
+
+
+def _backward_det(mod, saved, g_img, g_wp, dt):
+    """Deterministic mode: the same math with no atomics.  The gradient travels as g_x, w.r.t. each layer's output; the tail backward
+    is a pass of its own per layer (dge_modconv_bwd_prep, which applies d), and each layer's style gradient is finished on the spot."""
+    B, dev, layers, top = g_wp.shape[0], g_wp.device, saved["layers"], mod.num_layers - 2
+    emit = lambda g_srgb, O, row: ops.linear_t(g_srgb, O.style.weight.detach(), g_wp[:, row], scale=O.style.wscale, accumulate=True)
+    # top layer: its output only feeds the last toRGB (image_k = rgb_k + up(image_{k-1}), :515-522)
+    Ot = getattr(mod, f"output{top // 2}")
+    g_x, g_srgb = ops.torgb_bwd(g_img, layers[top]["y"], Ot.weight.detach().reshape(3, -1), saved["rgb"][top // 2]["s"], Ot.wscale)
+    emit(g_srgb, Ot, top + 1)
+    if top // 2 > 0:
+        g_img = ops.up2_bwd(g_img)
+    for i in range(top, -1, -1):
+        L, rec = getattr(mod, f"layer{i}"), layers[i]
+        R = ops.zeros((B, L.out_c, 3), dev)
+        g_y = ops.modconv_bwd_prep(g_x, rec["y"], rec["d"], rec["noise"], L.gain, R)
+        x_in = saved["const"] if i == 0 else layers[i - 1]["y"]
+        addend, g_img = _torgb_adjoint(mod, saved, i, g_img, x_in, emit)
+        st = ops.zeros((B, L.in_c, 2), dev)
+        g_x = s2_conv.dgrad(L, s2_conv.dgrad_route(L, B, dt, False, False), g_y, None, dt, None, rec["s"], addend, st, x_in)
+        _style_grads(L, rec, dt, R, st, g_wp[:, i])
+
+
+def synthesis_backward(mod, wp, saved, g_image):
+    """d(image)/d(wp) contracted with g_image [B,3,R,R] -> g_wp [B,num_layers,512], layer by layer from the top (the pre-activation
+    of a layer is z = yraw*d + noise*ns + bias, stylegan2_generator.py:908-921), in the form of the library's mode."""
+    g_wp = ops.zeros((wp.shape[0], mod.num_layers, mod.w_space_dim), wp.device)
+    chain = _backward_det if ops.is_deterministic() else _backward_fused
+    chain(mod, saved, g_image.float().contiguous(), g_wp, ops.dtype_of(saved["const"]))
     return g_wp
 
 
 class SynthesisFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod, wp, randomize_noise):
+    def forward(ctx, mod, wp, randomize_noise, keys):
         need = ctx.needs_input_grad[1]
         results, saved = synthesis_run(mod, wp.detach(), randomize_noise, save=need)
         ctx.mod, ctx.saved_acts, ctx.wp = mod, saved, wp.detach()
-        ctx.keys = [k for k in results if k not in ("wp", "image")]
-        outs = [results[k] for k in ctx.keys]
+        keys += [k for k in results if k not in ("wp", "image")]          # (the caller's list: the order synthesis_run produced)
+        outs = [results[k] for k in keys]
         ctx.mark_non_differentiable(*outs)
         return (results["image"], *outs)
 
@@ -218,7 +226,7 @@ class SynthesisFunction(torch.autograd.Function):
         if ctx.saved_acts is None:
             raise RuntimeError("synthesis was run without saved activations")
         g_wp = synthesis_backward(ctx.mod, ctx.wp, ctx.saved_acts, g_image)
-        return None, g_wp, None
+        return None, g_wp, None, None
 
 
 def synthesis_forward(mod, wp, randomize_noise=False):
@@ -226,18 +234,8 @@ def synthesis_forward(mod, wp, randomize_noise=False):
     wp[:, 2k+1] (reference :511-517).  Returns the reference's result dict."""
     wp = wp if (wp.dtype == torch.float32 and wp.is_contiguous()) else wp.float().contiguous()
     if wp.requires_grad and torch.is_grad_enabled():
-        outs = SynthesisFunction.apply(mod, wp, randomize_noise)
-        keys = [f"style{i:02d}" for i in range(mod.num_layers - 1)]
-        results = {"wp": wp}
-        # keys are produced in the same order as synthesis_run builds them
-        names = []
-        for i in range(mod.num_layers - 1):
-            names.append(f"style{i:02d}")
-            if i % 2 == 0:
-                names.append(f"output_style{i // 2}")
-        for n, t in zip(names, outs[1:]):
-            results[n] = t
-        results["image"] = outs[0]
-        return results
+        keys = []
+        image, *outs = SynthesisFunction.apply(mod, wp, randomize_noise, keys)
+        return {"wp": wp, **dict(zip(keys, outs)), "image": image}
     results, _ = synthesis_run(mod, wp, randomize_noise, save=False)
     return results

@@ -74,14 +74,17 @@ class SlotStats:
         return self.alloc(1)[0]
 
 
+def sum_slots(partial, out, accumulate=True):
+    """out [...] (+)= the sum of partial [n, ...] over its leading axis (dge_sum_slots): the slot copies of a statistics target"""
+    check(lib().dge_sum_slots(_p(partial), _p(out), partial.shape[0], out.numel(), 1 if accumulate else 0, _stream()), "dge_sum_slots")
+    return out
+
+
 def _sum_over_batch(partial, out=None):
     """partial [B, ...] per-sample sums -> [...] (dge_sum_slots); accumulates into `out` when given."""
-    n = partial[0].numel()
-    acc = out is not None
-    if out is None:
-        out = torch.empty(partial.shape[1:], dtype=torch.float32, device=partial.device)
-    check(lib().dge_sum_slots(_p(partial), _p(out), partial.shape[0], n, 1 if acc else 0, _stream()), "dge_sum_slots")
-    return out
+    if out is not None:
+        return sum_slots(partial, out)
+    return sum_slots(partial, torch.empty(partial.shape[1:], dtype=torch.float32, device=partial.device), accumulate=False)
 
 
 # ------------------------------------------------------------------ counter-based noise (dge_randn)
@@ -440,13 +443,30 @@ def _mask_as_dot_src(name, relu_mask, dot_src, prep):
     return dot_src if relu_mask is None else relu_mask
 
 
+def _stats_target(stats, B, H, W, tile_w, device, spread_plain=True):
+    """The statistics-slot protocol of a launch on an H x W grid -> (tensor the kernel adds into, its slot count, finish).  `stats`:
+    None; a SlotStats, allocated here with the launch's slot count (the consuming kernel adds the copies); or a plain zeroed
+    [B,C,2] tensor - the launch then spreads its atomics over partial copies of its own, and `finish()`, called after the launch,
+    adds them into it (dge_sum_slots).  spread_plain=False: a plain tensor takes the atomics itself, as one slot."""
+    nslot = _stats_slots(B, H, W, tile_w)
+    if isinstance(stats, SlotStats):
+        return stats.alloc(nslot), nslot, None
+    if stats is None or nslot == 1 or not spread_plain:
+        return stats, 1, None
+    partial = zeros((nslot,) + tuple(stats.shape), device)
+    return partial, nslot, lambda: sum_slots(partial, stats)
+
+
+def _prep_values(prep, nslot):
+    """the `prep` dict of the data-gradient launches -> (gain, noise, noise strength, batch of the noise, its statistics slots)"""
+    pn = prep.get("noise")
+    return float(prep["gain"]), pn, prep.get("ns") if pn is not None else None, 1 if pn is None else pn.shape[0], prep["stats"].alloc(nslot)
+
+
 def _set_prep(d, prep, nslot):
     """the `prep` dict of conv2d / conv_pp -> the prep_* fields that dge_conv_desc and dge_conv_pp_desc share"""
-    pn = prep.get("noise")
-    d.prep, d.prep_gain = 1, float(prep["gain"])
-    d.prep_noise, d.prep_ns = _f32(pn), _f32(prep.get("ns") if pn is not None else None)
-    d.prep_noise_batch = 1 if pn is None else pn.shape[0]
-    d.prep_stats = _f32(prep["stats"].alloc(nslot))
+    gain, pn, ns, nb, st = _prep_values(prep, nslot)
+    d.prep, d.prep_gain, d.prep_noise, d.prep_ns, d.prep_noise_batch, d.prep_stats = 1, gain, _f32(pn), _f32(ns), nb, _f32(st)
 
 
 def _weight_images(in_scale, out_scale):
@@ -531,15 +551,8 @@ def conv2d(x, w_packed, cout, ksize=3, up=False, in_scale=None, in_shift=None, o
     d.x, d.w_packed, d.y, d.addend, d.dot_src = _p(x), _p(w_packed), _p(out), _p(addend), _p(dot_src)
     d.in_scale, d.in_shift, d.out_scale = _f32(in_scale), _f32(in_shift), _f32(out_scale)
     # statistics atomics of large grids are spread over several copies (same-address contention), then combined
-    partial, nslot = None, 1
-    lazy = isinstance(stats, SlotStats)
-    if stats is not None:
-        nslot = _stats_slots(B, H, W, 16)
-        if lazy:
-            partial = stats.alloc(nslot)
-        elif nslot > 1:
-            partial = zeros((nslot,) + tuple(stats.shape), x.device)
-    d.bias, d.noise, d.noise_w, d.stats = _f32(bias), _f32(noise), _f32(noise_w), _f32(partial if partial is not None else stats)
+    st, nslot, finish = _stats_target(stats, B, H, W, 16, x.device)
+    d.bias, d.noise, d.noise_w, d.stats = _f32(bias), _f32(noise), _f32(noise_w), _f32(st)
     d.stats_slots = nslot
     d.B, d.H, d.W, d.Cin, d.Cout = B, H, W, Cin, cout
     d.ksize, d.up, d.in_s2d, d.in_up2 = ksize, 1 if up else 0, 1 if in_s2d else 0, 1 if in_up2 else 0
@@ -584,8 +597,8 @@ def conv2d(x, w_packed, cout, ksize=3, up=False, in_scale=None, in_shift=None, o
     skip_y = rgb is not None and rgb.get("skip_y")
     _launch(lib().dge_conv2d, (C.byref(d), _stream()), "dge_conv2d", taps_cin * cout * H * W * B, (B, H, W, Cin, cout, ksize, up, in_s2d),
             (x, None if skip_y else out, addend, dot_src, w_packed, rgb["out"] if rgb is not None else None))
-    if partial is not None and not lazy:
-        check(lib().dge_sum_slots(_p(partial), _p(stats), nslot, stats.numel(), 1, _stream()), "dge_sum_slots")
+    if finish is not None:
+        finish()
     if skip_y:
         return None
     if pool_out and pool_mask:
@@ -703,12 +716,10 @@ def conv_pp(x, w_pp, cout, out_scale=None, bias=None, bias_scale=1.0, noise=None
         dot_src = _mask_as_dot_src("conv_pp", relu_mask, dot_src, prep)
         d.dgrad, d.in_s2d, d.in_t2d, d.mask_relu = 1, 1 if in_s2d else 0, 1 if in_t2d else 0, 0 if relu_mask is None else 1
         d.dot_src, d.addend, d.add_scale = _p(dot_src), _p(addend), float(add_scale)
-        nslot = _stats_slots(B, H, W, 32)
-        if stats is not None:
-            d.stats = _f32(stats.alloc(nslot) if isinstance(stats, SlotStats) else stats)
-            if not isinstance(stats, SlotStats):
-                nslot = 1
-        d.stats_slots = nslot
+        st, nslot, _ = _stats_target(stats, B, H, W, 32, x.device, spread_plain=False)
+        if stats is None:
+            nslot = _stats_slots(B, H, W, 32)         # (the sums of a `prep` without stats are spread all the same)
+        d.stats, d.stats_slots = _f32(st), nslot
         if prep is not None:
             if dot_src is None:
                 raise DgeError("conv_pp: prep needs dot_src")
@@ -1446,23 +1457,15 @@ def up_dgrad_stream(g_z, w_packed, d_in, out_scale, addend, stats, dot_src, prep
     if not up_dgrad_stream_supported(B, H, W, cin, cout, dt):
         raise DgeError(f"up_dgrad_stream: unsupported launch {cin} <- {cout} channels, dtype {dt}")
     out = torch.empty((B, H, W, cin), dtype=g_z.dtype, device=g_z.device)
-    nslot = _stats_slots(B, H, W, 32)
-    lazy = isinstance(stats, SlotStats)
-    partial = stats.alloc(nslot) if lazy else (zeros((nslot,) + tuple(stats.shape), g_z.device) if nslot > 1 else stats)
-    pn = pns = pst = None
-    pgain, pbs = 1.0, 0
-    if prep is not None:
-        pn = prep.get("noise")
-        pns = prep.get("ns") if pn is not None else None
-        pbs = 0 if (pn is None or pn.shape[0] == 1) else H * W
-        pgain, pst = float(prep["gain"]), prep["stats"].alloc(nslot)
+    st, nslot, finish = _stats_target(stats, B, H, W, 32, g_z.device)
+    pgain, pn, pns, pnb, pst = (1.0, None, None, 1, None) if prep is None else _prep_values(prep, nslot)
     _launch(lib().dge_up_dgrad_stream,
-            (_p(g_z), _p(w_packed), _p(out), _f32(d_in), _f32(out_scale), _p(addend), _p(dot_src), _f32(partial), nslot,
-             0 if prep is None else 1, pgain, _f32(pn), pbs, _f32(pns), _f32(pst), B, H, W, cin, cout, dt, _stream()),
+            (_p(g_z), _p(w_packed), _p(out), _f32(d_in), _f32(out_scale), _p(addend), _p(dot_src), _f32(st), nslot,
+             0 if prep is None else 1, pgain, _f32(pn), 0 if pnb == 1 else H * W, _f32(pns), _f32(pst), B, H, W, cin, cout, dt, _stream()),
             "dge_up_dgrad_stream", 9.0 * cin * cout * H * W * B, (B, H, W, 4 * cout, cin, 3, False, True),
             (g_z, out, addend, dot_src, w_packed))
-    if not lazy and partial is not stats:
-        check(lib().dge_sum_slots(_p(partial), _p(stats), nslot, stats.numel(), 1, _stream()), "dge_sum_slots")
+    if finish is not None:
+        finish()
     return out
 
 
@@ -1504,12 +1507,8 @@ def up_dgrad_small(z_t2d, w_packed, out_scale, addend, stats, dot_src, prep=None
     d.in_t2d, d.w_layout, d.ksize = 1, 1, 3
     d.x, d.w_packed, d.y, d.addend, d.dot_src = _p(z_t2d), _p(w_packed), _p(out), _p(addend), _p(dot_src)
     d.out_scale = _f32(out_scale)
-    partial, nslot = None, 1
-    lazy = isinstance(stats, SlotStats)
-    if stats is not None:
-        nslot = _stats_slots(B, H, W, 16)
-        partial = stats.alloc(nslot) if lazy else (zeros((nslot,) + tuple(stats.shape), z_t2d.device) if nslot > 1 else stats)
-    d.stats, d.stats_slots = _f32(partial), nslot
+    st, nslot, finish = _stats_target(stats, B, H, W, 16, z_t2d.device)
+    d.stats, d.stats_slots = _f32(st), nslot
     d.B, d.H, d.W, d.Cin, d.Cout = B, H, W, C4, cin
     nxt = _PREFETCH.link(_stream().value or 0, w_packed)
     if nxt is not None:
@@ -1521,8 +1520,8 @@ def up_dgrad_small(z_t2d, w_packed, out_scale, addend, stats, dot_src, prep=None
     d.noise_batch, d.act, d.bias_scale, d.gain, d.add_scale, d.dtype = 1, ACT_NONE, 1.0, 1.0, 1.0, dt
     _launch(lib().dge_up_dgrad_small, (C.byref(d), _stream()), "dge_up_dgrad_small", 9.0 * cin * cout * H * W * B,
             (B, H, W, C4, cin, 3, False, True), (z_t2d, out, addend, dot_src, w_packed), log=True)
-    if partial is not None and not lazy and partial is not stats:
-        check(lib().dge_sum_slots(_p(partial), _p(stats), nslot, stats.numel(), 1, _stream()), "dge_sum_slots")
+    if finish is not None:
+        finish()
     return out
 
 

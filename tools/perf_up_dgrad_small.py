@@ -8,7 +8,7 @@ import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import dge_amd
-from dge_amd import ops
+from dge_amd import ops, s2_conv
 from dge_amd._lib import last_kernel
 
 
@@ -42,6 +42,7 @@ def timeit_cold(f, n=20):
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 C = 512
+s2_conv.UP_DG_SMALL = False                          # "old" is the route this launch replaced: conv2d in phase form or folded
 g = torch.Generator(device="cuda").manual_seed(0)
 gain = math.sqrt(2.0)
 wscale = 1 / math.sqrt(9 * C)
@@ -54,7 +55,7 @@ for R in (4, 8, 16, 32):
     s = 1 + 0.3 * torch.randn(B, C, device="cuda", generator=g)
     noise = torch.randn(1, R, R, device="cuda", generator=g); ns = torch.tensor([0.3], device="cuda")
     w = torch.randn(C, C, 3, 3, device="cuda", generator=g)
-    t2d = R >= 32                                    # s2_conv._up_phase_form
+    t2d = s2_conv.dgrad_route(s2_conv.LayerShape(True, 2 * R, C, C), B, ops.BF16, True, True).kind.endswith("t2d")
     pk = ops.pack_conv_weight(w, ops.PACK_UPT2D_DGRAD if t2d else ops.pack_mode_for(w, ops.PACK_UPFOLD_DGRAD, R, R, ops.BF16), ops.BF16, wscale)
     pu = ops.pack_up_dgrad_small(w, ops.BF16, wscale)
     names = {}
