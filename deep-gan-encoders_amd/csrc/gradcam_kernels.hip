@@ -32,45 +32,46 @@ __device__ __forceinline__ int win_hi(int i, int n) { return ((i + 1) * n + 6) /
 template <typename T>
 __global__ void adaptive_pool7_kernel(const T* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C) {
     const long n = (long)B * 49 * C;
-    const long idx = blockIdx.x * 256L + threadIdx.x;
-    if (idx >= n) return;
-    const int c = idx % C; long r = idx / C; const int j = r % 7; r /= 7; const int i = r % 7; const int b = r / 7;
-    const int y0 = win_lo(i, H), y1 = win_hi(i, H), x0 = win_lo(j, W), x1 = win_hi(j, W);
-    float s = 0.f;
-    for (int yy = y0; yy < y1; yy++)
-        for (int xx = x0; xx < x1; xx++) s += Elem<T>::ld(x + (((size_t)b * H + yy) * W + xx) * C + c);
-    y[(size_t)b * C * 49 + (size_t)c * 49 + i * 7 + j] = s / (float)((y1 - y0) * (x1 - x0));
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
+        const int c = idx % C; long r = idx / C; const int j = r % 7; r /= 7; const int i = r % 7; const int b = r / 7;
+        const int y0 = win_lo(i, H), y1 = win_hi(i, H), x0 = win_lo(j, W), x1 = win_hi(j, W);
+        float s = 0.f;
+        for (int yy = y0; yy < y1; yy++)
+            for (int xx = x0; xx < x1; xx++) s += Elem<T>::ld(x + (((size_t)b * H + yy) * W + xx) * C + c);
+        y[(size_t)b * C * 49 + (size_t)c * 49 + i * 7 + j] = s / (float)((y1 - y0) * (x1 - x0));
+    }
 }
 // adjoint: gx[b,yy,xx,c] = sum over the windows (i,j) that contain (yy,xx) of gy[b, c*49+i*7+j] / |window|
 template <typename T>
 __global__ void adaptive_pool7_bwd_kernel(const float* __restrict__ gy, T* __restrict__ gx, int B, int H, int W, int C) {
     const long n = (long)B * H * W * C;
-    const long idx = blockIdx.x * 256L + threadIdx.x;
-    if (idx >= n) return;
-    const int c = idx % C; long r = idx / C; const int xx = r % W; r /= W; const int yy = r % H; const int b = r / H;
-    float s = 0.f;
-    for (int i = 0; i < 7; i++) {
-        const int y0 = win_lo(i, H), y1 = win_hi(i, H);
-        if (yy < y0 || yy >= y1) continue;
-        for (int j = 0; j < 7; j++) {
-            const int x0 = win_lo(j, W), x1 = win_hi(j, W);
-            if (xx < x0 || xx >= x1) continue;
-            s += gy[(size_t)b * C * 49 + (size_t)c * 49 + i * 7 + j] / (float)((y1 - y0) * (x1 - x0));
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
+        const int c = idx % C; long r = idx / C; const int xx = r % W; r /= W; const int yy = r % H; const int b = r / H;
+        float s = 0.f;
+        for (int i = 0; i < 7; i++) {
+            const int y0 = win_lo(i, H), y1 = win_hi(i, H);
+            if (yy < y0 || yy >= y1) continue;
+            for (int j = 0; j < 7; j++) {
+                const int x0 = win_lo(j, W), x1 = win_hi(j, W);
+                if (xx < x0 || xx >= x1) continue;
+                s += gy[(size_t)b * C * 49 + (size_t)c * 49 + i * 7 + j] / (float)((y1 - y0) * (x1 - x0));
+            }
         }
+        Elem<T>::st(gx + idx, s);
     }
-    Elem<T>::st(gx + idx, s);
 }
 
 // grad_cam.py:166-170 on the device (no host round trip): per-row arg-max of the logits (first maximum, like np.argmax),
 // the most frequent of those indices (smallest index among ties: np.argmax(np.bincount(index))), and the gradient of
-// target = mean_n logits[n, index_max]: glogits[n, k] = (k == index_max) / B.  One workgroup.
+// target = mean_n logits[n, index_max]: glogits[n, k] = (k == index_max) / B.  One workgroup.  Given indices are clamped to [0, K)
+// like the rows form's: index_max addresses a row of the classifier weight in gather_row_kernel.
 __global__ void class_target_kernel(const float* __restrict__ logits, const int* __restrict__ index_in, int* __restrict__ index_out,
                                     float* __restrict__ glogits, int B, int K) {
     __shared__ int row_idx[1024];
     __shared__ int best;
     const int tid = threadIdx.x;
     for (int b = tid; b < B; b += 256) {
-        if (index_in) { row_idx[b] = index_in[b]; continue; }
+        if (index_in) { const int q = index_in[b]; row_idx[b] = q < 0 ? 0 : (q >= K ? K - 1 : q); continue; }
         int am = 0; float mv = logits[(size_t)b * K];
         for (int k = 1; k < K; k++) { const float v = logits[(size_t)b * K + k]; if (v > mv) { mv = v; am = k; } }
         row_idx[b] = am;
@@ -150,7 +151,7 @@ __global__ void class_target_groups_kernel(const float* __restrict__ logits, con
     if (index_in) index_in += r0;
     index_out += (size_t)blockIdx.x * (1 + N);
     for (int b = tid; b < N; b += 256) {
-        if (index_in) { row_idx[b] = index_in[b]; continue; }
+        if (index_in) { const int q = index_in[b]; row_idx[b] = q < 0 ? 0 : (q >= K ? K - 1 : q); continue; }
         int am = 0; float mv = logits[(size_t)b * K];
         for (int k = 1; k < K; k++) { const float v = logits[(size_t)b * K + k]; if (v > mv) { mv = v; am = k; } }
         row_idx[b] = am;
@@ -256,18 +257,18 @@ __device__ __forceinline__ void lin_tap(int d, int dn, int sn, int& i0, int& i1,
 __global__ void cam_resize_kernel(const float* __restrict__ cam, const float* __restrict__ mm, float* __restrict__ mask, int B, int h,
                                   int w, int H, int W) {
     const long n = (long)B * H * W;
-    const long idx = blockIdx.x * 256L + threadIdx.x;
-    if (idx >= n) return;
-    const int X = idx % W; long r = idx / W; const int Y = r % H; const int b = r / H;
-    int y0, y1, x0, x1; float ay, ax;
-    lin_tap(Y, H, h, y0, y1, ay);
-    lin_tap(X, W, w, x0, x1, ax);
-    const float lo = mm[2 * b], span = mm[2 * b + 1] - lo;
-    const float* c = cam + (size_t)b * h * w;
-    const float v00 = (c[y0 * w + x0] - lo) / span, v01 = (c[y0 * w + x1] - lo) / span;
-    const float v10 = (c[y1 * w + x0] - lo) / span, v11 = (c[y1 * w + x1] - lo) / span;
-    const float top = v00 * (1.f - ax) + v01 * ax, bot = v10 * (1.f - ax) + v11 * ax;
-    mask[idx] = top * (1.f - ay) + bot * ay;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
+        const int X = idx % W; long r = idx / W; const int Y = r % H; const int b = r / H;
+        int y0, y1, x0, x1; float ay, ax;
+        lin_tap(Y, H, h, y0, y1, ay);
+        lin_tap(X, W, w, x0, x1, ax);
+        const float lo = mm[2 * b], span = mm[2 * b + 1] - lo;
+        const float* c = cam + (size_t)b * h * w;
+        const float v00 = (c[y0 * w + x0] - lo) / span, v01 = (c[y0 * w + x1] - lo) / span;
+        const float v10 = (c[y1 * w + x0] - lo) / span, v11 = (c[y1 * w + x1] - lo) / span;
+        const float top = v00 * (1.f - ax) + v01 * ax, bot = v10 * (1.f - ax) + v11 * ax;
+        mask[idx] = top * (1.f - ay) + bot * ay;
+    }
 }
 
 // mask2cam part 1 (grad_cam.py:241-248): heat = JET[uint8(255 * mask)] / 255 in RGB order; cam = heat + img; per-block

@@ -152,15 +152,18 @@ class VGG16(nn.Module):
         N, K = logits.shape
         idx_in = None
         if index is not None:
-            idx_in = torch.as_tensor(index, dtype=torch.int32).reshape(-1).to(logits.device)
+            idx_in = torch.as_tensor(index).reshape(-1)
             if idx_in.numel() != N:
                 raise ValueError("index must hold one class id per input")
+            # the winning id addresses a row of the last layer's weight: a host-side index is refused here, before any launch; a
+            # device-side one is clamped to [0, K) by the kernels (checking it would cost a host round trip)
+            if not idx_in.is_cuda and (int(idx_in.min()) < 0 or int(idx_in.max()) >= K):
+                raise ValueError(f"index must lie in [0, {K})")
+            idx_in = idx_in.to(logits.device, torch.int32).contiguous()
         g = torch.empty_like(logits)
         if groups != 1:
             if groups < 1 or N % groups:
                 raise ValueError(f"groups={groups} must divide the {N} rows")
-            if index is not None and not torch.is_tensor(index) and (min(index) < 0 or max(index) >= K):
-                raise ValueError(f"index must lie in [0, {K})")          # (the winning id addresses a row of the last layer's weight)
             out = torch.empty((groups, 1 + N // groups), dtype=torch.int32, device=logits.device)
             check(lib().dge_class_target_groups(_f32(logits), _p(idx_in), _p(out), _f32(g), groups, N // groups, K, _stream()),
                   "dge_class_target_groups")

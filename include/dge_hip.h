@@ -663,7 +663,7 @@ int dge_maxpool2_relu_bwd(const void* gy, const void* x, void* gx, int B, int H,
 /* vgg16.avgpool + torch.flatten: x NHWC [B,H,W,C] -> y [B, C*49] f32 in (c, i, j) order; and its adjoint */
 int dge_adaptive_pool7(const void* x, float* y, int B, int H, int W, int C, int dtype, dge_stream_t stream);
 int dge_adaptive_pool7_bwd(const float* gy, void* gx, int B, int H, int W, int C, int dtype, dge_stream_t stream);
-/* grad_cam.py:166-170: index = per-row argmax of logits [B,K] (or index_in [B] when given), index_max = its most frequent
+/* grad_cam.py:166-170: index = per-row argmax of logits [B,K] (or index_in [B] when given, clamped to [0, K)), index_max = its most frequent
  * value (smallest on ties) -> index_out[0] (index_out[1..B] = the per-row indices); glogits [B,K] = d mean_n logits[n,index_max] */
 int dge_class_target(const float* logits, const int* index_in, int* index_out, float* glogits, int B, int K, dge_stream_t stream);
 /* y[b,:] = scale * w[index[0], :]  (w [O,I] f32, index on the device) */
