@@ -55,6 +55,12 @@ class SumPlanarEntry(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("out", C.c_void_p), ("nslot", C.c_int), ("C", C.c_int), ("NS", C.c_int), ("pad", C.c_int)]
 
 
+class NoisePlan(C.Structure):
+    _fields_ = [("maps", C.c_void_p), ("jobs", C.c_void_p), ("nmaps", C.c_int), ("Bn", C.c_int), ("n_pool0", C.c_int), ("n_pool1", C.c_int),
+                ("n_mom", C.c_int), ("npairs", C.c_int), ("n_chunk", C.c_int), ("pad", C.c_int), ("n_total", C.c_longlong),
+                ("lev_total", C.c_longlong)]
+
+
 _P, _I, _F = C.c_void_p, C.c_int, C.c_float
 # name -> argtypes; every symbol declared in include/dge_hip.h must be listed here
 SIGNATURES = {
@@ -216,6 +222,13 @@ SIGNATURES = {
     "dge_image_metrics_u8": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "dge_minmax_unit_slots": [C.c_long],
     "dge_minmax_unit": [_P, _P, C.c_long, _P, _P],
+    "dge_s2_noise_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _I, _P],
+    "dge_noise_map_size": [],
+    "dge_noise_job_size": [],
+    "dge_noise_reg_work_bytes": [C.POINTER(NoisePlan)],
+    "dge_noise_reg": [C.POINTER(NoisePlan), _P, _P, _P, _F, _I, _P, C.c_longlong, _P],
+    "dge_noise_normalize_work_bytes": [C.POINTER(NoisePlan)],
+    "dge_noise_normalize": [C.POINTER(NoisePlan), _P, _P, C.c_longlong, _P],
 }
 
 _lib = None

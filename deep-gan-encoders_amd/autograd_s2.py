@@ -57,7 +57,22 @@ def _style_tables(mod, B, dt):
     return tab
 
 
-def synthesis_run(mod, wp, randomize_noise=False, save=False):
+def check_noises(mod, noises, B, device):
+    """`noises` of synthesis(): one f32 map [1,res,res] (shared by the batch) or [B,res,res] (a map per row) per conv layer, in layer
+    order, contiguous, on the device - what the kernels' noise operand (batch stride 0 or res^2) takes as it is."""
+    noises = list(noises)
+    if len(noises) != mod.num_layers - 1:
+        raise ValueError(f"synthesis: `noises` takes one map per conv layer ({mod.num_layers - 1}), got {len(noises)}")
+    for i, n in enumerate(noises):
+        res = getattr(mod, f"layer{i}").res
+        if not torch.is_tensor(n) or n.dtype != torch.float32 or n.dim() != 3 or tuple(n.shape[1:]) != (res, res) or n.shape[0] not in (1, B):
+            raise ValueError(f"synthesis: noises[{i}] must be a float32 tensor [1,{res},{res}] or [{B},{res},{res}]")
+        if not n.is_contiguous() or n.device != device:
+            raise ValueError(f"synthesis: noises[{i}] must be contiguous and on {device}")
+    return noises
+
+
+def synthesis_run(mod, wp, randomize_noise=False, save=False, noises=None):
     dt = _dt(mod.compute_dtype)
     B = wp.shape[0]
     results = {"wp": wp}
@@ -78,7 +93,9 @@ def synthesis_run(mod, wp, randomize_noise=False, save=False):
         L = getattr(mod, f"layer{i}")
         s = s_of(i, L.in_c)
         d = d_all[tab["d_off"][i]:tab["d_off"][i] + B * L.out_c].view(B, L.out_c)
-        if randomize_noise:
+        if noises is not None:
+            noise = noises[i].detach()
+        elif randomize_noise:
             noise = ops.randn((x.shape[0], L.res, L.res), x.device)
         else:
             noise = L.noise.reshape(1, L.res, L.res)
@@ -136,7 +153,14 @@ def _style_grads(L, rec, dt, R, st, g_wp_row):
     ops.linear_t(gs_view, L.style.weight.detach(), g_wp_row, scale=L.style.wscale, accumulate=True, incx=2, ldx=2 * L.in_c, O=L.in_c)
 
 
-def _backward_fused(mod, saved, g_img, g_wp, dt):
+def _noise_grad(ng, i, L, rec, g, z_form):
+    """g_noise of layer i where asked for (ng: {layer: out [Bn, res^2] f32}, None: nowhere): from g_z as it is (`z_form`, form A),
+    else from the gradient w.r.t. the layer output, the kernel applying gain * lrelu'(x) (form B)."""
+    if ng and i in ng:
+        ops.s2_noise_grad(g, None if z_form else rec["y"], L.gain, L.noise_strength.detach().reshape(1), ng[i])
+
+
+def _backward_fused(mod, saved, g_img, g_wp, dt, ng=None):
     """Atomics mode.  The gradient travels down the chain as g_z, w.r.t. the pre-activation of each layer: the data-gradient launch
     of layer i + 1 differentiates layer i's noise / bias / lrelu tail in its own epilogue (`prep`: it streams layer i's stored
     output as dot_src anyway) and leaves the two per-(b,c) sums of the demodulation gradient in P; the demodulation factor d
@@ -155,6 +179,7 @@ def _backward_fused(mod, saved, g_img, g_wp, dt):
         g_img = ops.up2_bwd(g_img)
     for i in range(top, -1, -1):
         L, rec = getattr(mod, f"layer{i}"), layers[i]
+        _noise_grad(ng, i, L, rec, g_x, P is not None)
         if P is not None:
             g_y, d_in = g_x, rec["d"]                  # g_x is g_z already (with its sums in P); d joins in the launch
         else:
@@ -179,7 +204,7 @@ def _backward_fused(mod, saved, g_img, g_wp, dt):
     ops.s2_style_grads(blocks, g_wp, getattr(mod, "layer0").style.wscale)
 
 
-def _backward_det(mod, saved, g_img, g_wp, dt):
+def _backward_det(mod, saved, g_img, g_wp, dt, ng=None):
     """Deterministic mode: the same math with no atomics.  The gradient travels as g_x, w.r.t. each layer's output; the tail backward
     is a pass of its own per layer (dge_modconv_bwd_prep, which applies d), and each layer's style gradient is finished on the spot."""
     B, dev, layers, top = g_wp.shape[0], g_wp.device, saved["layers"], mod.num_layers - 2
@@ -192,6 +217,7 @@ def _backward_det(mod, saved, g_img, g_wp, dt):
         g_img = ops.up2_bwd(g_img)
     for i in range(top, -1, -1):
         L, rec = getattr(mod, f"layer{i}"), layers[i]
+        _noise_grad(ng, i, L, rec, g_x, False)
         R = ops.zeros((B, L.out_c, 3), dev)
         g_y = ops.modconv_bwd_prep(g_x, rec["y"], rec["d"], rec["noise"], L.gain, R)
         x_in = saved["const"] if i == 0 else layers[i - 1]["y"]
@@ -201,21 +227,28 @@ def _backward_det(mod, saved, g_img, g_wp, dt):
         _style_grads(L, rec, dt, R, st, g_wp[:, i])
 
 
-def synthesis_backward(mod, wp, saved, g_image):
+def synthesis_backward(mod, wp, saved, g_image, noise_grads=None):
     """d(image)/d(wp) contracted with g_image [B,3,R,R] -> g_wp [B,num_layers,512], layer by layer from the top (the pre-activation
-    of a layer is z = yraw*d + noise*ns + bias, stylegan2_generator.py:908-921), in the form of the library's mode."""
+    of a layer is z = yraw*d + noise*ns + bias, stylegan2_generator.py:908-921), in the form of the library's mode.
+    `noise_grads`: {conv layer: f32 [Bn, res^2]} to receive the gradient w.r.t. that layer's noise map (Bn 1: the map is shared by
+    the batch) - a pass of its own per entry beside the chain (dge_s2_noise_grad), which runs exactly as it does without."""
     g_wp = ops.zeros((wp.shape[0], mod.num_layers, mod.w_space_dim), wp.device)
     chain = _backward_det if ops.is_deterministic() else _backward_fused
-    chain(mod, saved, g_image.float().contiguous(), g_wp, ops.dtype_of(saved["const"]))
+    chain(mod, saved, g_image.float().contiguous(), g_wp, ops.dtype_of(saved["const"]), noise_grads)
     return g_wp
 
 
 class SynthesisFunction(torch.autograd.Function):
+    """Inputs behind `keys`: `grad_out` (None, or per conv layer None or an f32 buffer of the map's shape: the backward writes that
+    layer's noise gradient THERE instead of returning it to autograd - static storage for a captured iteration, no accumulation
+    pass) and the noise maps, if any."""
+
     @staticmethod
-    def forward(ctx, mod, wp, randomize_noise, keys):
-        need = ctx.needs_input_grad[1]
-        results, saved = synthesis_run(mod, wp.detach(), randomize_noise, save=need)
+    def forward(ctx, mod, wp, randomize_noise, keys, grad_out, *noises):
+        need = any(ctx.needs_input_grad)
+        results, saved = synthesis_run(mod, wp.detach(), randomize_noise, save=need, noises=noises or None)
         ctx.mod, ctx.saved_acts, ctx.wp = mod, saved, wp.detach()
+        ctx.grad_out, ctx.noise_shapes = grad_out, [tuple(n.shape) for n in noises]
         keys += [k for k in results if k not in ("wp", "image")]          # (the caller's list: the order synthesis_run produced)
         outs = [results[k] for k in keys]
         ctx.mark_non_differentiable(*outs)
@@ -225,17 +258,35 @@ class SynthesisFunction(torch.autograd.Function):
     def backward(ctx, g_image, *unused):
         if ctx.saved_acts is None:
             raise RuntimeError("synthesis was run without saved activations")
-        g_wp = synthesis_backward(ctx.mod, ctx.wp, ctx.saved_acts, g_image)
-        return None, g_wp, None, None
+        ng, ret = {}, [None] * len(ctx.noise_shapes)
+        if ctx.mod.noise_grad_enabled:          # (read here: a second backward through the same graph may switch the passes off)
+            for i, shape in enumerate(ctx.noise_shapes):
+                if ctx.needs_input_grad[5 + i]:
+                    out = ctx.grad_out[i] if ctx.grad_out is not None else None
+                    if out is None:
+                        ng[i] = ret[i] = torch.empty(shape, dtype=torch.float32, device=g_image.device)
+                    elif tuple(out.shape) != shape or out.dtype != torch.float32:
+                        raise ValueError(f"synthesis: noise_grad_out[{i}] must be float32 {shape}")
+                    else:
+                        ng[i] = out
+        g_wp = synthesis_backward(ctx.mod, ctx.wp, ctx.saved_acts, g_image, ng)
+        return (None, g_wp, None, None, None, *ret)
 
 
-def synthesis_forward(mod, wp, randomize_noise=False):
+def synthesis_forward(mod, wp, randomize_noise=False, noises=None, noise_grad_out=None):
     """SynthesisModule.forward: conv layer i is driven by wp[:, i]; the toRGB of block k by
-    wp[:, 2k+1] (reference :511-517).  Returns the reference's result dict."""
+    wp[:, 2k+1] (reference :511-517).  Returns the reference's result dict.  `noises`: the conv layers' noise maps in place of the
+    `layer{i}.noise` buffers (check_noises); the image is differentiable w.r.t. every map that requires grad."""
     wp = wp if (wp.dtype == torch.float32 and wp.is_contiguous()) else wp.float().contiguous()
-    if wp.requires_grad and torch.is_grad_enabled():
+    if noises is not None:
+        if randomize_noise:
+            raise ValueError("synthesis: `noises` fixes every noise map; randomize_noise=True contradicts it")
+        noises = check_noises(mod, noises, wp.shape[0], wp.device)
+    if noise_grad_out is not None and (noises is None or len(noise_grad_out) != len(noises)):
+        raise ValueError("synthesis: noise_grad_out takes one buffer (or None) per map of `noises`")
+    if torch.is_grad_enabled() and (wp.requires_grad or any(n.requires_grad for n in noises or ())):
         keys = []
-        image, *outs = SynthesisFunction.apply(mod, wp, randomize_noise, keys)
+        image, *outs = SynthesisFunction.apply(mod, wp, randomize_noise, keys, noise_grad_out, *(noises or ()))
         return {"wp": wp, **dict(zip(keys, outs)), "image": image}
-    results, _ = synthesis_run(mod, wp, randomize_noise, save=False)
+    results, _ = synthesis_run(mod, wp, randomize_noise, save=False, noises=noises)
     return results

@@ -98,11 +98,15 @@ class TwoPhaseEmbedStep(GraphReplay):
         warm = {}
 
         def keep_last():    # results of the last executed iteration (the captured one is only recorded)
+            self._after_warmup()
             if warmup:
                 warm.update({k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.last.items()})
         out = self._capture(lambda: self.step(self._g_imgs1, noises), warmup, after_warmup=keep_last)
         self.last = warm
         return out
+
+    def _after_warmup(self):
+        """Behind the last real iteration of capture(), before the recorded one: host-side counters a subclass rolls back itself."""
 
     def _graph_inputs(self, iteration):
         self.opt.graph_advance()

@@ -77,6 +77,23 @@ embedding_v2_pggan is for PGGAN.  Per iteration:
   * the tracker follows z; `independent` works as in W mode (the mapping is per-sample already); files are the W-mode set with the
     z row in models/id*-i*-z*.pt and models/z_all_*.pt [N, 512].
 
+Noise optimisation (`optimize_noise`, --optimize_noise true; StyleGAN2, mode "W", one process): the per-layer noise maps of the
+synthesis network become free variables beside the W+ code, as in StyleGAN2's own projector.
+  * the maps start at the generator's `layer{i}.noise` buffers - one shared set [1,res,res] per layer, or a copy per row
+    [B,res,res] with `independent` - and live in one flat f32 buffer (ops.NoiseTable) with one LREQAdam of its own (lr `noise_lr`
+    or lr, its own step count); begin_image resets the maps and that Adam state in place.
+  * phase 1 back-propagates loss_msiv + noise_reg * sum reg(map) (the projector's regulariser, dge_noise_reg): the synthesis
+    backward writes each map's image-loss gradient (dge_s2_noise_grad) into the flat gradient buffer and the regulariser's
+    gradient is added to it.  loss_msiv, the tracker and every logged loss stay the image loss alone; reg is logged as `noise_reg`
+    ([B] in rows form).
+  * the maps take one Adam step per iteration from that phase-1 gradient and are renormalised to zero mean and unit mean square
+    (dge_noise_normalize).  Phase 2 launches no noise pass (SynthesisModule.noise_grad_enabled is off for its backward) and moves
+    no map.  The step and the renormalisation are ISSUED behind the phase-2 backward: the retained synthesis graph reads its
+    noise operand by reference (the demodulation sums reconstruct yraw*d + bias as z - ns*noise), so a map may not move under
+    it.  Nothing in phase 2 depends on the updated maps, so the results are those of stepping between the phases.
+  * finish_group also writes models/id{n}-noise.pt, the list of maps of that image (each [1,res,res]); they reload into
+    StyleGAN2Generator.synthesis(wp, noises=...).
+
 The loop over the iterations of a group (invert_group), its file side (dump_group, loss_txt_block, finish_group), the group walk
 of main() (invert_folder, rows_plan) and the common part of the command lines (add_inversion_args, open_run, run_inversion) serve
 embedding_v2_pggan and embedding_v2_biggan too: their dumps differ in the file-name patterns and in the Loss.txt block, BigGAN's
@@ -90,6 +107,7 @@ import os
 import torch
 
 from . import losses, ops
+from .custom_adam import LREQAdam
 from .embed_step import TwoPhaseEmbedStep, several_processes
 from .embed_track import EVENT_LOSS, EVENT_NORM, tracker_rules, write_tracker_files  # noqa: F401 (re-exported)
 from .embedding import select_launch
@@ -158,6 +176,8 @@ def _generate_sg1(st, w, noises, truncate):
 def _generate_sg2(st, w, noises, truncate):
     # (the synthesis backward reads its saved activations only, never wp: w itself may be the input when psi == 1)
     wt = w if st.psi == 1.0 or not truncate else _WplusLerp.apply(w, st.G.truncation.w_avg, st.psi)
+    if st.optimize_noise:
+        return st.G.synthesis(wt, randomize_noise=False, noises=st.noise_maps, noise_grad_out=st.noise_grads)["image"]
     return st.G.synthesis(wt, randomize_noise=False)["image"]
 
 
@@ -189,7 +209,12 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
     fused_backward = True          # "pg": the generator backward with ops.pixelnorm_act_bwd (False: the composed launches, for timing)
 
     def __init__(self, G, E, lpips_model, mode="E", generator="sg2", lr=0.005, beta_1=0.0, beta=None, norm_p=2, truncation=None,
-                 iterations=None, arm_iter=None, events_cap=256, seed=0, independent=False, Gm=None, mapping_bwd="auto"):
+                 iterations=None, arm_iter=None, events_cap=256, seed=0, independent=False, Gm=None, mapping_bwd="auto",
+                 optimize_noise=False, noise_reg=1e5, noise_lr=None):
+        if optimize_noise:
+            why = noise_refusal(generator == "sg2", mode == "E", mode == "Z", several_processes())
+            if why:
+                raise ValueError("LatentEmbedStep: " + why)
         if independent and mode == "E":
             raise ValueError("independent=True needs mode 'W' or 'Z': in mode 'E' one encoder is shared by the rows of a group")
         if generator not in KINDS:
@@ -210,6 +235,8 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
         self.norm_p = int(norm_p)
         self.psi = None if d["truncation"] is None else (d["truncation"] if truncation is None else float(truncation))
         self._const2 = None
+        self.optimize_noise, self.noise_reg, self.noise_lr = bool(optimize_noise), float(noise_reg), noise_lr
+        self.noise_table = self.noise_flat = self.noise_maps = self.noise_grads = self.nopt = None
         if mode == "Z" and self.kind.own_mapping:
             # the scripts' coefficients (embedding_v2_styleGAN1.py: 0.7 on the first half of the rows); without a centre Mapping
             # takes the plain broadcast whatever they are
@@ -247,6 +274,65 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
             self.G.mapping.wide_bwd = wide
         return w0 if encoded or not needed else seeded_start(shape, self.seed, self.group, self.independent)
 
+    # ------------------------------------------------------------------ the noise maps (optimize_noise)
+    def begin_image(self, imgs1, w_init=None, noises=None, **group_kw):
+        super().begin_image(imgs1, w_init=w_init, noises=noises, **group_kw)
+        if self.optimize_noise:
+            self._noise_begin(imgs1.shape[0], imgs1.device)
+
+    def _noise_begin(self, B, dev):
+        """The maps of a new group: the generator's buffers, copied per row in independent mode, into the flat leaf (allocated once
+        per shape and device with its table, gradient buffer and LREQAdam); the Adam state is cleared in place."""
+        S, Bn = self.G.synthesis, B if self.independent else 1
+        layers = [getattr(S, f"layer{i}") for i in range(S.num_layers - 1)]
+        tab = self.noise_table
+        if tab is None or tab.Bn != Bn or tab.device != self.w1.device:
+            if self.captured:
+                raise ValueError("LatentEmbedStep.begin_image: the captured iteration works on other noise maps")
+            tab = self.noise_table = ops.NoiseTable([L.res for L in layers], Bn, dev)
+            self.noise_flat = torch.zeros(tab.numel, dtype=torch.float32, device=dev, requires_grad=True)
+            self._noise_gflat = torch.zeros(tab.numel, dtype=torch.float32, device=dev)
+            self._noise_regv = torch.zeros(Bn, dtype=torch.float32, device=dev)
+            # the maps the generator sees: leaves of their own on the flat storage (their gradients go to the views of _noise_gflat)
+            self.noise_maps = [tab.view(self.noise_flat.detach(), m).requires_grad_(True) for m in range(len(layers))]
+            self.noise_grads = [tab.view(self._noise_gflat, m) for m in range(len(layers))]
+            self.nopt = LREQAdam([{"params": [self.noise_flat]}], lr=self.lr if self.noise_lr is None else self.noise_lr,
+                                 betas=(self.beta_1, 0.99), weight_decay=0)
+        with torch.no_grad():
+            for m, L in zip(self.noise_maps, layers):
+                m.copy_(L.noise.reshape(1, L.res, L.res).expand_as(m))
+        self.nopt.graph_reset()
+
+    def _noise_step(self):
+        """One LREQAdam step of the maps from the phase-1 gradient, then the renormalisation."""
+        self.noise_flat.grad = self._noise_gflat
+        self.nopt.step()
+        self.noise_flat.grad = None
+        ops.noise_normalize(self.noise_table, self.noise_flat.detach())
+
+    def capture(self, imgs1, noises=(None, None, None), warmup=TwoPhaseEmbedStep.WARMUP):
+        if not self.optimize_noise:
+            return super().capture(imgs1, noises, warmup)
+        self.nopt.graph_begin(1, imgs1.device)          # one call per iteration, with its own step count
+        out = super().capture(imgs1, noises, warmup)
+        self.nopt.graph_restore(self._noise_snap)       # (the recorded iteration advanced the host counters, not the device)
+        return out
+
+    def _after_warmup(self):
+        if self.optimize_noise:
+            self._noise_snap = self.nopt.graph_snapshot()
+
+    def _graph_inputs(self, iteration):
+        super()._graph_inputs(iteration)
+        if self.optimize_noise:
+            self.nopt.graph_advance()
+
+    def replay(self):
+        r = super().replay()
+        if self.optimize_noise:
+            self.nopt.graph_count_replay()
+        return r
+
     # ------------------------------------------------------------------ one iteration
     def _generate(self, w1, noises):
         return self.kind.generate(self, w1, noises, truncate=True)
@@ -282,6 +368,9 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
         image_loss, latent_loss = (losses.image_loss_tsa_rows, losses.space_loss_rows) if rows else (losses.image_loss_tsa, losses.space_loss)
         loss_msiv, info_img = image_loss(imgs1, imgs2, self.lpips, weights=IMG_WEIGHTS, grad_windows=(True, True, True))
         self._opt_phase(loss_msiv, retain_graph=True)
+        if self.optimize_noise:          # phase 1's loss is loss_msiv + noise_reg * sum reg: the regulariser's gradient joins the image loss's
+            ops.noise_reg(self.noise_table, self.noise_flat.detach(), grad=self._noise_gflat, scale=self.noise_reg, accumulate=True,
+                          out=self._noise_regv)
         if not kind.encode_first:
             const3, w2 = kind.encode(self, imgs2, noises[2])
         wp_new = self._wp_of(w1) if zmode else None          # the direct term of phase 2 sees the updated code
@@ -293,7 +382,15 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
             lat = lat + loss_c1
         nrm = _PNorm.apply(w1, self.norm_p, rows)
         loss_mslv = lat * 0.01 + (nrm.sum() if rows else nrm) * self.beta
-        self._opt_phase(loss_mslv)
+        if self.optimize_noise:
+            self.G.synthesis.noise_grad_enabled = False          # phase 2 through the retained graph: d/dw1 alone
+            try:
+                self._opt_phase(loss_mslv)
+            finally:
+                self.G.synthesis.noise_grad_enabled = True
+            self._noise_step()
+        else:
+            self._opt_phase(loss_mslv)
         w1d = w1.detach()
         if rows:      # the values of every row: the [B] columns of the info tensors (the scalars above are their sums over the rows)
             loss_msiv = info_img[:, 0, 0] * IMG_WEIGHTS[0] + info_img[:, 1, 0] * IMG_WEIGHTS[1] + info_img[:, 2, 0] * IMG_WEIGHTS[2]
@@ -310,7 +407,22 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
                          w_norm=self._tracker.l2)
         if zmode:
             self.last.update(wp=wp.detach(), wp_new=wp_new.detach())
+        if self.optimize_noise:          # the maps behind this iteration's step, its phase-1 gradients (valid until the next backward), reg
+            self.last.update(noises=[m.detach() for m in self.noise_maps], noise_grads=self.noise_grads, noise_reg=self._noise_regv)
         return self.last
+
+
+def noise_refusal(sg2, mode_e, mode_z, several):
+    """Why noise optimisation is not offered for a configuration (None: it is): the step's and the command line's one rule."""
+    if not sg2:
+        return "noise optimisation is for StyleGAN2 (--mtype 2): the other generators' noise inputs have no gradient pass"
+    if mode_e:
+        return "noise optimisation needs --optimizeE false: the maps are optimised beside the W+ code, not beside the encoder"
+    if mode_z:
+        return "noise optimisation is not offered with --space z: it runs beside the W+ code (mode W)"
+    if several:
+        return "noise optimisation runs in one process (WORLD_SIZE > 1 is not supported)"
+    return None
 
 
 def group_plan(n_images, batch_size):
@@ -395,6 +507,10 @@ def finish_group(st, r, B, out_dir, group, keep=None):
                 write_tracker_files(tr[b], group * B + b, models, out_dir)
         else:
             write_tracker_files(tr, group, models, out_dir)
+        if getattr(st, "optimize_noise", False):          # the maps of every image, as synthesis(noises=...) takes them
+            maps = [m.cpu() for m in r["noises"]]
+            for num, b in ([(group * B + b, b) for b in range(B if keep is None else keep)] if st.independent else [(group, 0)]):
+                torch.save([m[b:b + 1].clone() for m in maps], os.path.join(models, "id%d-noise.pt" % num))
     return dict(r, tracker=tr)
 
 
@@ -574,6 +690,10 @@ def make_parser():
     p.add_argument("--beta", type=float, default=None, help="weight of ||w1||_p: default 1e-3 (mtype 1), 3e-4 (mtype 2)")
     p.add_argument("--norm_p", type=int, default=None, help="p of ||w1||_p (default 2)")
     p.add_argument("--truncation", type=float, default=None, help="StyleGAN2: psi of avg + psi*(w1 - avg) (default 0.7; 1: none)")
+    p.add_argument("--optimize_noise", type=strict_bool, default=False,
+                   help="true (--mtype 2, --optimizeE false): optimise the synthesis network's noise maps beside the W+ code")
+    p.add_argument("--noise_reg", type=float, default=1e5, help="weight of the noise regulariser in phase 1 (default 1e5)")
+    p.add_argument("--noise_lr", type=float, default=None, help="learning rate of the noise maps (default: --lr)")
     return p
 
 
@@ -589,6 +709,10 @@ def parse_args(argv=None):
             raise SystemExit("embedding_v2: --space z runs in one process (WORLD_SIZE > 1 is not supported)")
     if args.mtype not in DEFAULTS:
         raise SystemExit("embedding_v2: --mtype must be 1 (StyleGAN1) or 2 (StyleGAN2)")
+    if args.optimize_noise:
+        why = noise_refusal(args.mtype == 2, args.optimizeE, args.space == "z", several_processes(env=True))
+        if why:
+            raise SystemExit("embedding_v2: --optimize_noise true: " + why)
     if args.independent and args.optimizeE:
         raise SystemExit("embedding_v2: --independent true needs --optimizeE false (the fine-tuned encoder is shared by a group)")
     for k, v in DEFAULTS[args.mtype].items():
@@ -632,9 +756,10 @@ def main(argv=None):
     Gm = build_mapping_sg1(G, dev, args.seed) if zspace and args.mtype == 1 else None
     load_checkpoints(G, E, args.mtype, args.checkpoint_dir_GAN, args.checkpoint_dir_E, Gm=Gm)
     out, imgs = open_run(args, LP, "./realimg_embedding_result/7", dev)
+    noise_kw = dict(optimize_noise=True, noise_reg=args.noise_reg, noise_lr=args.noise_lr) if args.optimize_noise else {}
     st = LatentEmbedStep(G, E, LP, mode="E" if args.optimizeE else ("Z" if zspace else "W"), Gm=Gm, generator="sg1" if args.mtype == 1 else "sg2", lr=args.lr,
                          beta_1=args.beta_1, beta=args.beta, norm_p=args.norm_p, truncation=args.truncation,
-                         iterations=args.iterations, seed=args.seed, independent=args.independent)
+                         iterations=args.iterations, seed=args.seed, independent=args.independent, **noise_kw)
     return run_inversion(args, st, invert_v2, imgs, out, all_name="z_all_%d.pt" if zspace else "w_all_%d.pt")
 
 

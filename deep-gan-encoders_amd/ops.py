@@ -1680,3 +1680,119 @@ def image_metrics_u8(a, b, work=None, isums=None, ssim=None, out=None):
     check(lib().dge_image_metrics_u8(_p(a), _p(b), B, H, W, _p(work), _p(isums), _p(ssim), _p(out), _stream()), "dge_image_metrics_u8")
     log_kernel()
     return isums, ssim, out
+
+
+# ---- StyleGAN2 noise maps as free variables (include/dge_hip.h dge_s2_noise_grad / dge_noise_reg / dge_noise_normalize)
+def s2_noise_grad(g, x=None, gain=1.0, ns=None, out=None, accumulate=False):
+    """out [Bn, HW] f32 (Bn 1: a map shared by the batch, or B) (+)= ns * sum_c g_z[b, p, c] (shared: and over b, ascending).
+    g NHWC [B,H,W,C] in the compute dtype: g_z when `x` is None (form A), else the gradient w.r.t. the layer output x, and the
+    kernel applies gain * lrelu'(x) (form B).  ns: the layer's noise strength, a device f32 scalar."""
+    B, H, W, Cc = g.shape
+    if x is not None and (x.shape != g.shape or x.dtype != g.dtype):
+        raise DgeError(f"s2_noise_grad: x {tuple(x.shape)} {x.dtype} does not match g {tuple(g.shape)} {g.dtype}")
+    if ns is None or ns.numel() != 1:
+        raise DgeError("s2_noise_grad: ns must be a device scalar")
+    if out is None:
+        if accumulate:
+            raise DgeError("s2_noise_grad: accumulate needs out")
+        out = torch.empty((1, H * W), dtype=torch.float32, device=g.device)
+    Bn = out.numel() // (H * W)
+    if out.numel() != Bn * H * W or Bn not in (1, B):
+        raise DgeError(f"s2_noise_grad: out holds {out.numel()} floats, {H * W} (shared map) or {B * H * W} (a map per row) expected")
+    check(lib().dge_s2_noise_grad(_p(g), _p(x), _f32(ns), _f32(out), B, Bn, H * W, Cc, float(gain), 1 if accumulate else 0, dtype_of(g),
+                                  _stream()), "dge_s2_noise_grad")
+    _log_dense("dge_s2_noise_grad")
+    return out
+
+
+NOISE_CHUNK = 1024          # elements of a chunk job (csrc/s2_noise_kernels.hip kChunk)
+
+
+def noise_levels(R):
+    """Levels of the regulariser's pyramid for a map of side R: the last one is the first of side <= 8."""
+    n = 1
+    while (R >> (n - 1)) > 8:
+        n += 1
+    return n
+
+
+class NoiseTable:
+    """The static layout of a set of square noise maps for dge_noise_reg / dge_noise_normalize, built once: the maps live in one
+    flat f32 buffer, map m as [Bn, R_m, R_m] from float `offsets[m]` on (`view(flat, m)`); the device tables (map and job records)
+    and the workspace belong to the table, so a captured iteration keeps their addresses."""
+
+    def __init__(self, res, Bn, device):
+        import numpy as np
+        from ._lib import NoisePlan
+        res = [int(r) for r in res]
+        if not 1 <= len(res) <= 32 or Bn < 1:
+            raise DgeError("NoiseTable: 1..32 maps, at least one row")
+        for R in res:
+            if R < 4 or R > 1024 or R & (R - 1):
+                raise DgeError(f"NoiseTable: map side {R} (a power of two, 4..1024)")
+        self.res, self.Bn, self.device = res, int(Bn), torch.device(device)
+        map_dt = np.dtype([("off", "<i8"), ("work_off", "<i8"), ("R", "<i4"), ("nlev", "<i4"), ("pair0", "<i4"), ("cslot0", "<i4")])
+        assert map_dt.itemsize == lib().dge_noise_map_size() and lib().dge_noise_job_size() == 16
+        maps = np.zeros(len(res), dtype=map_dt)
+        pool0, pool1, mom, pairs, chunks = [], [], [], [], []
+        off = lev = 0
+        self.offsets = []
+        for m, R in enumerate(res):
+            nlev = noise_levels(R)
+            maps[m] = (off, lev, R, nlev, len(pairs), len(chunks))
+            self.offsets.append(off)
+            off += Bn * R * R
+            lev += Bn * sum((R >> l) ** 2 for l in range(1, nlev))
+            for src, jobs in ((0, pool0), (5, pool1)):
+                if nlev - 1 > src:
+                    t = max(1, (R >> src) // 32)
+                    jobs += [(m, src, ty, tx) for ty in range(t) for tx in range(t)]
+            for l in range(nlev):
+                nch = -(-((R >> l) ** 2) // NOISE_CHUNK)
+                pairs.append((m, l, len(mom), nch))
+                mom += [(m, l, c, len(mom) + c) for c in range(nch)]
+            nch = -(-(R * R) // NOISE_CHUNK)
+            chunks += [(m, 0, c, len(chunks) + c) for c in range(nch)]
+        if len(pairs) > 256:
+            raise DgeError("NoiseTable: more than 256 (map, level) pairs")
+        jobs = np.array(pool0 + pool1 + mom + pairs + chunks, dtype=np.int32).reshape(-1, 4)
+        self.numel = off
+        self._maps = torch.from_numpy(maps.view(np.uint8).copy()).to(self.device)
+        self._jobs = torch.from_numpy(jobs.copy()).to(self.device)
+        self.device = self._maps.device          # (with its index: what a tensor on it reports)
+        self.plan = NoisePlan(self._maps.data_ptr(), self._jobs.data_ptr(), len(res), self.Bn, len(pool0), len(pool1), len(mom), len(pairs),
+                              len(chunks), 0, off, lev)
+        nb = max(lib().dge_noise_reg_work_bytes(C.byref(self.plan)), lib().dge_noise_normalize_work_bytes(C.byref(self.plan)))
+        if nb < 0:
+            check(nb, "dge_noise_reg_work_bytes")
+        self.work = torch.empty((nb + 3) // 4, dtype=torch.float32, device=self.device)
+
+    def view(self, flat, m):
+        R = self.res[m]
+        return flat[self.offsets[m]:self.offsets[m] + self.Bn * R * R].view(self.Bn, R, R)
+
+    def _flat(self, t, what):
+        if t.dtype != torch.float32 or t.numel() != self.numel or t.device != self.device:
+            raise DgeError(f"{what}: expected the table's flat f32 buffer of {self.numel} floats on {self.device}")
+        return _f32(t)
+
+
+def noise_reg(table, flat, grad=None, scale=1.0, accumulate=False, out=None):
+    """reg [Bn] of the maps in `flat` (NoiseTable layout); with `grad` (same layout): grad (+)= scale * d reg[b] / d flat."""
+    if out is None:
+        out = torch.empty(table.Bn, dtype=torch.float32, device=table.device)
+    if out.numel() != table.Bn:
+        raise DgeError("noise_reg: out holds one value per row")
+    check(lib().dge_noise_reg(C.byref(table.plan), table._flat(flat, "noise_reg"), _f32(out),
+                              None if grad is None else table._flat(grad, "noise_reg"), float(scale), 1 if accumulate else 0,
+                              _p(table.work), table.work.numel() * 4, _stream()), "dge_noise_reg")
+    _log_dense("dge_noise_reg")
+    return out
+
+
+def noise_normalize(table, flat):
+    """Every row of every map of `flat` to zero mean and unit mean square, in place."""
+    check(lib().dge_noise_normalize(C.byref(table.plan), table._flat(flat, "noise_normalize"), _p(table.work), table.work.numel() * 4,
+                                    _stream()), "dge_noise_normalize")
+    _log_dense("dge_noise_normalize")
+    return flat

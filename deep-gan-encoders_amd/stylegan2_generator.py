@@ -266,7 +266,9 @@ class ModulateConvBlock(nn.Module):
 
 
 class SynthesisModule(nn.Module):
-    """wp -> image (reference :336-539, architecture 'skip')."""
+    """wp -> image (reference :336-539, architecture 'skip').  `noise_grad_enabled`: read by the backward - False skips the
+    noise-gradient passes of maps given through `noises` (a second backward through a retained graph that needs d/dwp only)."""
+    noise_grad_enabled = True
 
     def __init__(self, resolution=1024, init_resolution=4, w_space_dim=512, image_channels=3,
                  fmaps_base=32 << 10, fmaps_max=512, compute_dtype="bf16"):
@@ -295,13 +297,17 @@ class SynthesisModule(nn.Module):
     def get_nf(self, res):
         return min(self.fmaps_base // res, self.fmaps_max)
 
-    def forward(self, wp, randomize_noise=False):
+    def forward(self, wp, randomize_noise=False, noises=None, noise_grad_out=None):
+        """Extra keywords: `noises`, one f32 map [1,res,res] (shared by the batch) or [B,res,res] per conv layer in layer order,
+        replacing the `layer{i}.noise` buffers; a map that requires grad receives its gradient (dge_s2_noise_grad).  Where the
+        list `noise_grad_out` names a buffer of the map's shape, the gradient is written there INSTEAD of reaching the map's
+        .grad (static storage for a captured iteration, no accumulation pass)."""
         if wp.ndim != 3 or tuple(wp.shape[1:]) != (self.num_layers, self.w_space_dim):
             raise ValueError(f"Input tensor should be with shape [batch_size, num_layers, w_space_dim], where "
                              f"`num_layers` equals to {self.num_layers}, and `w_space_dim` equals to "
                              f"{self.w_space_dim}!\nBut `{wp.shape}` is received!")
         from .autograd_s2 import synthesis_forward
-        return synthesis_forward(self, wp, randomize_noise)
+        return synthesis_forward(self, wp, randomize_noise, noises, noise_grad_out)
 
 
 def mixing_mask(num_layers, style_mixing_prob=0.9):

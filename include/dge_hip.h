@@ -789,6 +789,54 @@ int dge_image_metrics_u8(const unsigned char* a, const unsigned char* b, int B, 
 int dge_minmax_unit_slots(long n);
 int dge_minmax_unit(const float* x, float* y, long n, float* slots, dge_stream_t stream);
 
+/* ---- StyleGAN2 inversion: the per-layer noise maps as free variables (embedding_v2 --optimize_noise) ------------------------- */
+/* Gradient w.r.t. a layer's noise input (forward z = yraw*d + noise*ns + bias, x = lrelu(z)*gain):
+ *   out[n, p] (+)= ns[0] * sum_{b reads map n} sum_c g_z[b, p, c],   out f32 [Bn, HW], Bn = 1 (one map shared by the batch: the
+ *   rows are added in ascending b) or Bn = B (a map per row).  g, x NHWC [B, HW, C] in `dtype`.  x == NULL: g is g_z, the
+ *   gradient w.r.t. the pre-activation; else g is the gradient w.r.t. the layer output x and g_z = g * gain * lrelu'(x) is formed
+ *   here (slope 0.2, at x == 0 too).  The 16-byte chunks of a pixel combine by a butterfly inside the wave, a pixel wider than a
+ *   wave through LDS in wave order; plain stores (accumulate != 0: out += by its one writer), no atomics, nothing pre-zeroed: the
+ *   same bits in both reduction modes, and row b of a per-row call equals the call on row b alone.  Channel counts: those of
+ *   dge_modconv_bwd_prep.  dge_last_kernel: "s2_noise_grad<bf16|f32,A|B>". */
+int dge_s2_noise_grad(const void* g, const void* x, const float* ns, float* out, int B, int Bn, int HW, int C, float gain, int accumulate,
+                      int dtype, dge_stream_t stream);
+/* The noise regulariser of StyleGAN2's projector and the renormalisation, over a table of square maps of side R (a power of two,
+ * 4 .. 1024) that live in one f32 buffer `n` of n_total floats: map m holds its Bn rows R*R apart from float offset `off`.
+ *   reg(n) = sum over levels l of mean(n_l * roll(n_l, 1, w))^2 + mean(n_l * roll(n_l, 1, h))^2, n_0 = n, n_{l+1} = avgpool2(n_l),
+ *   the last level the first of side <= 8 (nlev levels); rolls wrap around.
+ * The tables are device memory, written once by the caller:
+ *   maps [nmaps]: work_off = float offset of the map's pooled levels (rows lev = sum_{l>=1} (R>>l)^2 apart, level 1 first) in the
+ *     level area of lev_total floats; pair0 = index of (map, level 0) among the npairs (map, level) pairs; cslot0 = index of the
+ *     map's first 1024-element chunk among the n_chunk chunks of all maps.
+ *   jobs, five sections in this order: n_pool0 x (map, 0, tile y, tile x), the 32 x 32 tiles (the whole map below 32) of every map
+ *     of more than one level; n_pool1 x (map, 5, tile y, tile x) for every map of more than six levels; n_mom x (map, level,
+ *     chunk, slot) with the slots numbered 0 .. n_mom - 1 and the chunks of a pair adjacent; npairs x (map, level, first slot,
+ *     slots); n_chunk x (map, 0, chunk, slot), slots 0 .. n_chunk - 1.
+ * A job whose map does not fit n_total / lev_total touches nothing. */
+typedef struct dge_noise_map { long long off, work_off; int R, nlev, pair0, cslot0; } dge_noise_map;
+typedef struct dge_noise_job { int map, level, a, b; } dge_noise_job;
+typedef struct dge_noise_plan {
+    const dge_noise_map* maps;
+    const dge_noise_job* jobs;
+    int nmaps, Bn, n_pool0, n_pool1, n_mom, npairs, n_chunk, pad;
+    long long n_total, lev_total;
+} dge_noise_plan;
+int dge_noise_map_size(void);
+int dge_noise_job_size(void);
+/* reg [Bn] = sum over the maps of reg(row b of the map); grad (may be NULL; the layout of n) (+)= scale * d reg[b] / d n.
+ * Launches: two pooling passes (levels through LDS, to `work`), the roll products per 1024-element chunk to a slot each, a
+ * finaliser (one workgroup per row: a pair's slots in slot order, the pairs in pair order), the gradient - five, however many
+ * maps.  work: dge_noise_reg_work_bytes(plan) bytes, 16-byte aligned, nothing pre-zeroed (-1: a plan it refuses, or 2 GiB or more).
+ * dge_last_kernel: "noise_reg". */
+int dge_noise_reg_work_bytes(const dge_noise_plan* plan);
+int dge_noise_reg(const dge_noise_plan* plan, const float* n, float* reg, float* grad, float scale, int accumulate, void* work,
+                  long long work_bytes, dge_stream_t stream);
+/* n <- (n - mean(n)) * rsqrt(mean((n - mean(n))^2)) for every row of every map, in place: three launches over the chunk jobs (sums
+ * to slots; squared deviations from the mean every workgroup re-adds in slot order, to slots; the update).
+ * dge_last_kernel: "noise_normalize". */
+int dge_noise_normalize_work_bytes(const dge_noise_plan* plan);
+int dge_noise_normalize(const dge_noise_plan* plan, float* n, void* work, long long work_bytes, dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,11 @@ trained encoder, alternating, medians over --rounds rounds.
 --space z: the Z-space loop (mode "Z") under hipGraph replay at batch 1 (coupled) and --batches independent rows, with each
 route of the mapping adjoint (dge_mapping_bwd / dge_mapping_bwd_wide), beside mode W on the same box, one process, the
 configurations alternating, medians over --rounds rounds with the round spread.
+--optimize_noise: mode W under hipGraph replay with the noise maps optimised beside the W+ code against the same step without
+them, at batch 1 (coupled) and the other --batches as independent rows, one process, flag on and off alternating round by round,
+medians over --rounds rounds with the round spread; then the noise-gradient passes of one synthesis backward alone (device time
+of the per-layer dge_s2_noise_grad launches on operands of the layers' shapes) and the regulariser and renormalisation launches.
+    python tools/bench_embed_v2.py --optimize_noise --batches 1,8
     python tools/bench_embed_v2.py --space z --batches 8
     python tools/bench_embed_v2.py --compare-encoders --batches 8
     python tools/bench_embed_v2.py --last-stage --batches 1,8"""
@@ -29,6 +34,7 @@ ap.add_argument("--iters", type=int, default=20); ap.add_argument("--dtype", def
 ap.add_argument("--encoder", choices=("blur", "be"), default="blur"); ap.add_argument("--compare-encoders", action="store_true")
 ap.add_argument("--last-stage", action="store_true")
 ap.add_argument("--space", choices=("w", "z"), default="w")
+ap.add_argument("--optimize_noise", action="store_true")
 ap.add_argument("--independent", action="store_true"); ap.add_argument("--batches", default="2,4,8"); ap.add_argument("--rounds", type=int, default=5)
 a = ap.parse_args()
 res = {}
@@ -117,6 +123,65 @@ def bench_space_z():
     print(json.dumps(res))
 
 
+def bench_noise():
+    from dge_amd import ops
+    batches = [int(v) for v in a.batches.split(",")]
+    G, E, LP = build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0, encoder=a.encoder)
+    with torch.no_grad():
+        imgs = G.synthesis(torch.randn(max(batches), G.synthesis.num_layers, 512, device="cuda"))["image"].detach().clamp(-1, 1).contiguous()
+    runs = {}
+    for B in batches:
+        for flag in (False, True):
+            st = LatentEmbedStep(G, E, LP, mode="W", generator="sg2", independent=B > 1, optimize_noise=flag)
+            st.begin_image(imgs[:B].contiguous())
+            st.capture(imgs[:B].contiguous(), warmup=1)
+            for _ in range(3):
+                st.replay()
+            runs[f"B{B}_{'independent' if B > 1 else 'coupled'}_{'noise' if flag else 'plain'}"] = (st, B)
+    ms = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for name, (st, B) in runs.items():
+            ms[name].append(timed(st.replay, a.iters))
+    for name, (st, B) in runs.items():
+        m = median(ms[name])
+        res[name] = dict(ms_per_iteration=round(m, 3), spread=round(max(ms[name]) - min(ms[name]), 3), rounds=[round(v, 3) for v in ms[name]])
+        print(f"embedding_v2 W replay, StyleGAN2-{a.img_size} + {ENC_NAME[a.encoder]}, {a.dtype}, {name}: {m:.3f} ms/iteration "
+              f"(spread {max(ms[name]) - min(ms[name]):.3f}), {m / B:.3f} ms/image-iteration", flush=True)
+    # the passes alone, device time between two events around `iters` repetitions
+    S = G.synthesis
+    layers = [getattr(S, f"layer{i}") for i in range(S.num_layers - 1)]
+    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+
+    def device_ms(f):
+        for _ in range(3):
+            f()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            f()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    for B in batches:
+        Bn = B if B > 1 else 1
+        gz = [torch.randn(B, L.res, L.res, L.out_c, device="cuda").to(dt) for L in layers]
+        outs = [torch.empty(Bn, L.res * L.res, device="cuda") for L in layers]
+        ns = [L.noise_strength.detach().reshape(1) for L in layers]
+        tab = ops.NoiseTable([L.res for L in layers], Bn, "cuda")
+        flat, grad = torch.randn(tab.numel, device="cuda"), torch.empty(tab.numel, device="cuda")
+        nbytes = sum(g.numel() * g.element_size() for g in gz)
+        t = dict(noise_grad_form_A=[], noise_grad_form_B=[], noise_reg=[], noise_normalize=[])
+        for _ in range(a.rounds):
+            t["noise_grad_form_A"].append(device_ms(lambda: [ops.s2_noise_grad(g, None, L.gain, n, o) for g, L, n, o in zip(gz, layers, ns, outs)]))
+            t["noise_grad_form_B"].append(device_ms(lambda: [ops.s2_noise_grad(g, g, L.gain, n, o) for g, L, n, o in zip(gz, layers, ns, outs)]))
+            t["noise_reg"].append(device_ms(lambda: ops.noise_reg(tab, flat, grad=grad, scale=1e5, accumulate=True)))
+            t["noise_normalize"].append(device_ms(lambda: ops.noise_normalize(tab, flat)))
+        res[f"passes_B{B}"] = dict(gz_bytes=nbytes, **{k: dict(ms=round(median(v), 4), rounds=[round(q, 4) for q in v]) for k, v in t.items()})
+        print(f"noise passes alone, B = {B} ({'a map per row' if B > 1 else 'shared maps'}), g_z of all layers {nbytes / 1e9:.3f} GB: "
+              + ", ".join(f"{k} {median(v):.4f} ms" for k, v in t.items()), flush=True)
+    print(json.dumps(res))
+
+
 def bench_compare_encoders():
     batches = [int(v) for v in a.batches.split(",")]
     models = {enc: build_models_v2(2, a.img_size, a.start_features, a.dtype, seed=0, encoder=enc) for enc in ("blur", "be")}
@@ -176,6 +241,9 @@ def bench_last_stage():
     print(json.dumps(res))
 
 
+if a.optimize_noise:
+    bench_noise()
+    sys.exit(0)
 if a.space == "z":
     bench_space_z()
     sys.exit(0)
