@@ -229,6 +229,12 @@ SIGNATURES = {
     "dge_noise_reg": [C.POINTER(NoisePlan), _P, _P, _P, _F, _I, _P, C.c_longlong, _P],
     "dge_noise_normalize_work_bytes": [C.POINTER(NoisePlan)],
     "dge_noise_normalize": [C.POINTER(NoisePlan), _P, _P, C.c_longlong, _P],
+    "dge_adam_multi": [_I, _P, _P, _P, _P, _P, C.c_double, C.c_double, _F, _F, _F, _P, _P],
+    "dge_w_broadcast": [_P, _P, _F, _P, _P, _I, _I, _I, _P],
+    "dge_w_broadcast_bwd": [_P, _P, _I, _I, _I, _P],
+    "dge_rows_mean_std_work_bytes": [C.c_longlong, _I],
+    "dge_rows_mean_std": [_P, C.c_longlong, _I, _P, _P, _P, C.c_longlong, _P],
+    "dge_area_pool_bwd": [_P, _P, _I, _I, _I, _I, _P],
 }
 
 _lib = None

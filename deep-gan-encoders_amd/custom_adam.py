@@ -1,12 +1,13 @@
 """LREQAdam (reference model/utils/custom_adam.py:6-76): Adam with beta1 == 0 and a per-parameter
-`lr_equalization_coef`, executed as one multi-tensor HIP launch per step."""
+`lr_equalization_coef`, executed as one multi-tensor HIP launch per step; and Adam, torch.optim.Adam's update with a first
+moment (StyleGAN2's projector), one launch of its own kernel."""
 import ctypes as C
 import math
 
 import torch
 from torch.optim.optimizer import Optimizer
 
-from . import weight_cache
+from . import ops, weight_cache
 from ._lib import lib, check
 from .ops import _stream
 
@@ -156,4 +157,116 @@ class LREQAdam(Optimizer):
                 self._graph_call += 1
             check(lib().dge_lreq_adam_multi(n, PA, GA, VA, NA, SA, group["beta_2"], group["eps"], gsc, smul, _stream()),
                   "dge_lreq_adam_multi")
+        return loss
+
+
+class Adam(Optimizer):
+    """torch.optim.Adam (no amsgrad, no weight decay) as one multi-tensor HIP launch per step (dge_adam_multi): StyleGAN2's projector
+    runs it with beta1 = 0.9 and a learning rate that follows a schedule, so `step(lr=...)` / `group["lr"]` may change per call.
+    Every parameter with a gradient takes part in every step: the parameters share one step count, and the two scalars of a step,
+    lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t), are computed by the host - or, between graph_begin and the end of the process,
+    read from device floats that graph_advance uploads before every capture / replay (the LREQAdam interface GraphReplay drives)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        if not 0.0 <= lr:
+            raise ValueError("Invalid learning rate: {}".format(lr))
+        if not 0.0 < eps:
+            raise ValueError("Invalid epsilon value: {}".format(eps))
+        for i, b in enumerate(betas):
+            if not 0.0 <= b < 1.0:
+                raise ValueError("Invalid beta parameter at index {}: {}".format(i, b))
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps))
+        if len(self.param_groups) != 1:
+            raise ValueError("Adam: one parameter group (one launch, one pair of step scalars)")
+        self.t = 0                      # steps taken (shared by the parameters)
+        self._graph_sc = None           # [calls per replay, 2] device floats: (lr / bc1, 1 / sqrt(bc2)) of each call
+        self._graph_call = 0
+        self._graph_t = None
+
+    def scalars(self, t, lr=None):
+        """(lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t)) of step number t >= 1, as host doubles"""
+        group = self.param_groups[0]
+        b1, b2 = group["betas"]
+        return (group["lr"] if lr is None else lr) / (1.0 - b1 ** t), 1.0 / math.sqrt(1.0 - b2 ** t)
+
+    # ---- hipGraph mode: the interface of LREQAdam
+    def graph_begin(self, calls_per_replay, device):
+        self._graph_sc = torch.zeros((calls_per_replay, 2), dtype=torch.float32, device=device)
+        self._graph_call = 0
+        self._graph_t = None
+
+    def graph_advance(self):
+        """Before every capture / replay: the scalars of the region's step() calls, from the step count and the current group["lr"]."""
+        n = self._graph_sc.shape[0]
+        if self._graph_t is None:
+            self._graph_t = self.t
+        vals = [self.scalars(self._graph_t + k + 1) for k in range(n)]
+        self._graph_t += n
+        self._graph_sc.copy_(torch.tensor(vals, dtype=torch.float32))          # (a fresh pageable host tensor: staged before copy_ returns)
+        self._graph_call = 0
+
+    def graph_snapshot(self):
+        return (self._graph_t, self.t)
+
+    def graph_restore(self, snap):
+        """The step() calls of a RECORDED iteration advanced the host's count although no update ran."""
+        self._graph_t, self.t = snap
+        self._sync_state_steps()
+
+    def graph_count_replay(self):
+        self.t += self._graph_sc.shape[0]
+        self._sync_state_steps()
+
+    def graph_reset(self):
+        """Fresh optimizer state without changing any device address."""
+        for st in self.state.values():
+            if len(st):
+                st["exp_avg"].zero_()
+                st["exp_avg_sq"].zero_()
+        self.t = 0
+        self._graph_t = 0 if self._graph_sc is not None else None
+        self._sync_state_steps()
+
+    def _sync_state_steps(self):
+        for st in self.state.values():
+            if len(st):
+                st["step"] = self.t
+
+    @torch.no_grad()
+    def step(self, closure=None, lr=None):
+        """lr: the learning rate of this call (default group["lr"]); ignored where the scalars come from the device."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        group = self.param_groups[0]
+        ps, gs, ms, vs = [], [], [], []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if p.grad.is_sparse:
+                raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
+            if not p.is_cuda or p.dtype != torch.float32:
+                raise RuntimeError("Adam runs on float32 parameters on the HIP device only")
+            state = self.state[p]
+            if len(state) == 0:
+                state["step"] = self.t
+                state["exp_avg"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
+                state["exp_avg_sq"] = torch.zeros_like(p.data, memory_format=torch.contiguous_format)
+            ps.append(p.data)
+            gs.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
+            ms.append(state["exp_avg"])
+            vs.append(state["exp_avg_sq"])
+        if not ps:
+            return loss
+        self.t += 1
+        self._sync_state_steps()
+        weight_cache.written(p for p in group["params"] if p.grad is not None)
+        b1, b2 = group["betas"]
+        if self._graph_sc is None:
+            step, isb = self.scalars(self.t, lr)
+            ops.adam_multi(ps, gs, ms, vs, b1, b2, group["eps"], step, isb)
+        else:
+            ops.adam_multi(ps, gs, ms, vs, b1, b2, group["eps"], scalars=self._graph_sc[self._graph_call])
+            self._graph_call += 1
         return loss

@@ -1796,3 +1796,104 @@ def noise_normalize(table, flat):
                                     _stream()), "dge_noise_normalize")
     _log_dense("dge_noise_normalize")
     return flat
+
+
+# ---- StyleGAN2's projector (include/dge_hip.h dge_adam_multi / dge_w_broadcast / dge_rows_mean_std / dge_area_pool_bwd)
+def _host_or_dev(v, what):
+    """(host float, device pointer or None) of a scalar given as a Python number or as a one-element f32 device tensor"""
+    if torch.is_tensor(v):
+        if v.numel() != 1:
+            raise DgeError(f"{what}: a device scalar holds one float")
+        return 0.0, _f32(v)
+    return float(v), None
+
+
+def adam_multi(params, grads, exp_avg, exp_avg_sq, beta1, beta2, eps, step=0.0, inv_sqrt_bc2=1.0, scalars=None):
+    """One torch.optim.Adam update of every tensor of the lists, in one launch (in place on params, exp_avg, exp_avg_sq).
+    step = lr / (1 - beta1^t), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t); `scalars`: a [2] f32 device tensor holding the two instead."""
+    n = len(params)
+    if not (len(grads) == len(exp_avg) == len(exp_avg_sq) == n):
+        raise DgeError("adam_multi: the four lists hold one tensor per parameter")
+    for quad in zip(params, grads, exp_avg, exp_avg_sq):
+        if len({t.numel() for t in quad}) != 1:
+            raise DgeError("adam_multi: a parameter, its gradient and its moments have one size")
+    if scalars is not None and scalars.numel() != 2:
+        raise DgeError("adam_multi: scalars holds two floats (step, 1/sqrt(bc2))")
+    VP = C.c_void_p * n
+    ptrs = [VP(*[_f32(t).value for t in ts]) for ts in (params, grads, exp_avg, exp_avg_sq)]
+    check(lib().dge_adam_multi(n, *ptrs, (C.c_long * n)(*[p.numel() for p in params]), float(beta1), float(beta2), float(eps), float(step),
+                               float(inv_sqrt_bc2), _f32(scalars), _stream()), "dge_adam_multi")
+    log_kernel()
+
+
+def w_broadcast(w, L, noise=None, scale=0.0, out=None):
+    """w [B,D], noise [B,D] or None -> ws [B,L,D] = (w + noise * scale) in every row l; `scale`: a number or a device scalar."""
+    B, D = w.shape
+    if noise is not None and tuple(noise.shape) != (B, D):
+        raise DgeError(f"w_broadcast: noise must have w's shape {(B, D)}, got {tuple(noise.shape)}")
+    if out is None:
+        out = torch.empty((B, L, D), dtype=torch.float32, device=w.device)
+    elif tuple(out.shape) != (B, L, D):
+        raise DgeError(f"w_broadcast: out must be {(B, L, D)}")
+    sc, sd = _host_or_dev(scale, "w_broadcast")
+    check(lib().dge_w_broadcast(_f32(w), _f32(noise), sc, sd, _f32(out), B, int(L), D, _stream()), "dge_w_broadcast")
+    log_kernel()
+    return out
+
+
+def w_broadcast_bwd(g_ws, out=None):
+    """g_ws [B,L,D] -> g_w [B,D], the sum over l in ascending order."""
+    B, L, D = g_ws.shape
+    if out is None:
+        out = torch.empty((B, D), dtype=torch.float32, device=g_ws.device)
+    check(lib().dge_w_broadcast_bwd(_f32(g_ws), _f32(out), B, L, D, _stream()), "dge_w_broadcast_bwd")
+    log_kernel()
+    return out
+
+
+def rows_mean_std(x):
+    """x [N,D] f32 -> (mean [D] over the rows, std [1] = sqrt(sum (x - mean)^2 / N)): the projector's w_avg and w_std."""
+    N, D = x.shape
+    nb = lib().dge_rows_mean_std_work_bytes(N, D)
+    if nb < 0:
+        check(nb, "dge_rows_mean_std_work_bytes")
+    work = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+    mean = torch.empty(D, dtype=torch.float32, device=x.device)
+    std = torch.empty(1, dtype=torch.float32, device=x.device)
+    check(lib().dge_rows_mean_std(_f32(x), N, D, _p(mean), _p(std), _p(work), work.numel() * 4, _stream()), "dge_rows_mean_std")
+    log_kernel()
+    return mean, std
+
+
+def area_pool_bwd(g_pooled, k, out=None):
+    """g_pooled [B,C,h,w] f32 -> [B,C,h*k,w*k]: the adjoint of the k x k area pooling (each value / k^2 to its k x k pixels)."""
+    B, Cc, h, w = g_pooled.shape
+    if out is None:
+        out = torch.empty((B, Cc, h * k, w * k), dtype=torch.float32, device=g_pooled.device)
+    check(lib().dge_area_pool_bwd(_f32(g_pooled), _f32(out), B * Cc, h * k, w * k, int(k), _stream()), "dge_area_pool_bwd")
+    log_kernel()
+    return out
+
+
+def area_pool(x, k):
+    """x [B,C,H,W] f32 -> the k x k area means [B,C,H/k,W/k] (dge_crop_pool_multi on the whole image)."""
+    B, Cc, H, W = x.shape
+    out = torch.empty((B, Cc, H // k, W // k), dtype=torch.float32, device=x.device)
+    check(lib().dge_crop_pool_multi((C.c_void_p * 1)(_f32(x).value), (C.c_void_p * 1)(_p(out).value), (C.c_int * 4)(0, 0, H, W),
+                                    (C.c_int * 1)(int(k)), 1, B * Cc, H, W, _stream()), "dge_crop_pool_multi")
+    _log_dense("dge_crop_pool_multi")
+    return out
+
+
+def randn_seeded(out, seeds, seeds_dev=None):
+    """Row r of out [R,D] <- the first D normals of draw 0 under seed seeds[r] (dge_randn, a launch per row: the Philox key is the
+    seed).  seeds_dev: an int64 device tensor [R] read in place of `seeds` (a captured iteration is replayed with new seeds).
+    Every launch is named in KERNEL_LOG (the entry point's name: it selects no kernel instantiation)."""
+    R, D = out.shape
+    LL, ULL, UI = C.c_longlong * 1, C.c_ulonglong * 1, C.c_uint * 1
+    for r in range(R):
+        sd = C.c_void_p(seeds_dev.data_ptr() + 8 * r) if seeds_dev is not None else None
+        check(lib().dge_randn(C.c_void_p(_f32(out).value + 4 * r * D), 1, LL(0), LL(D), ULL(0), UI(0),
+                              C.c_ulonglong(int(seeds[r]) & 0xFFFFFFFFFFFFFFFF), sd, _stream()), "dge_randn")
+        _log_dense("dge_randn")
+    return out

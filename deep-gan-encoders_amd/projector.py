@@ -1,0 +1,371 @@
+"""StyleGAN2's projector on the HIP path (Karras et al., "Analyzing and Improving the Image Quality of StyleGAN", appendix D; the
+stylegan2 / stylegan2-ada `projector.py`): the encoder-free inversion every encoder-based loop of this package is compared with
+(`python -m dge_amd.compare`).  One W code [B,512], shared by all rows of W+, and the synthesis network's noise maps are optimised
+with Adam (beta1 = 0.9) against LPIPS alone.  Per iteration (ProjectorStep.step):
+
+    lr_t, noise_scale_t = projector_schedule(i, steps)                 host doubles
+    ws = w + randn * noise_scale_t, in every row of W+                 dge_randn, dge_w_broadcast
+    imgs = G.synthesis(ws, noises=maps)                                noise fixed to the optimised maps
+    dist = LPIPS(target, imgs) per row, both area-pooled to 256^2 where the image is larger        dge_crop_pool_multi
+    loss = sum_b dist_b + noise_reg * sum_b reg_b                      dge_noise_reg
+    one backward: dge_area_pool_bwd, the synthesis backward with dge_s2_noise_grad, dge_w_broadcast_bwd
+    one Adam step over [w, maps] with lr_t                             dge_adam_multi
+    maps to zero mean and unit mean square                             dge_noise_normalize
+
+The loss is a sum over the rows and every stage is per sample, so the B rows of a group are B independent projections; a row equals
+the batch-1 run of its image.  No step makes a host synchronisation.
+
+Decisions:
+  * w_avg (also the start code) and w_std come from `w_avg_samples` z drawn from a seeded CPU generator and mapped without
+    truncation, through dge_rows_mean_std; w_std = sqrt(sum (w - w_avg)^2 / samples), the projector's formula.
+  * the maps start at the generator's `layer{i}.noise` buffers, a copy per row, not at fresh randn as the original does: the
+    run then starts from the image G shows for w_avg, and a reloaded `id*-noise.pt` with `id*-wp.pt` reproduces `rec/*.png`.
+  * the w noise of row b is a pure function of (seed, image number, iteration): the first 512 normals of dge_randn under a seed
+    mixed from the three (w_noise_seed), one launch per row because the seed is the generator's key.  A captured iteration reads
+    the seeds from device scalars that _graph_inputs refreshes, through dge_randn's `seed_dev`.
+  * a captured iteration reads Adam's two step scalars and noise_scale from device floats (custom_adam.Adam.graph_advance,
+    _graph_inputs), so the schedule moves under replay.
+  * the target's VGG features are recomputed every iteration (LPIPS.value_and_grad evaluates both halves).
+  * one process: WORLD_SIZE > 1 is refused.
+  * ProjectorStep freezes the generator it is given (requires_grad_(False) on every parameter) and does not undo it.
+
+Files of `project` / the CLI: real/{n:05d}.png and rec/{n:05d}.png (the bytes of infer.quantize_u8: `compare --dir1 real --dir2
+rec` works on the output), models/id{n}-w.pt [1,512], models/id{n}-wp.pt [1,L,512], models/id{n}-noise.pt (the list of maps, each
+[1,res,res], as embedding_v2 writes it) and Loss.txt.  Images are numbered across the folder; a short last group repeats its last
+image and discards the padded rows, as `embedding_v2 --independent true` does."""
+import argparse
+import math
+import os
+
+import torch
+
+from . import ops
+from .custom_adam import Adam
+from .embed_step import several_processes
+from .graph_step import GraphReplay
+
+
+def projector_schedule(step, steps, lr=0.1, w_std=1.0, initial_noise_factor=0.05, noise_ramp=0.75, lr_rampdown=0.25, lr_rampup=0.05):
+    """(lr_t, noise_scale_t) of iteration `step` of `steps`, host doubles: the learning rate ramps up over the first `lr_rampup` of
+    the run and decays by a cosine over the last `lr_rampdown`; the w noise decays quadratically to 0 at `noise_ramp`."""
+    t = step / steps
+    noise_scale = w_std * initial_noise_factor * max(0.0, 1.0 - t / noise_ramp) ** 2
+    r = min(1.0, (1.0 - t) / lr_rampdown)
+    r = 0.5 - 0.5 * math.cos(r * math.pi)
+    r = r * min(1.0, t / lr_rampup)
+    return lr * r, noise_scale
+
+
+def w_noise_seed(seed, number, iteration):
+    """The dge_randn seed of image `number`'s w noise in iteration `iteration`: splitmix64 over the three, so neighbouring
+    images and iterations get unrelated Philox keys."""
+    M = 0xFFFFFFFFFFFFFFFF
+    x = (int(seed) * 0x9E3779B97F4A7C15 + int(number) * 0xBF58476D1CE4E5B9 + int(iteration) * 0x94D049BB133111EB + 0x2545F4914F6CDD1D) & M
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M
+    return x ^ (x >> 31)
+
+
+class _WBroadcast(torch.autograd.Function):
+    """ws[b,l,:] = w[b,:] + noise[b,:] * scale (dge_w_broadcast); the gradient of w is the sum over l (dge_w_broadcast_bwd)."""
+
+    @staticmethod
+    def forward(ctx, w, noise, scale, L):
+        return ops.w_broadcast(w.detach(), L, noise, scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.w_broadcast_bwd(g.float().contiguous()), None, None, None
+
+
+class ProjectorStep(GraphReplay):
+    """One projection step (module docstring).  G is a StyleGAN2Generator in eval mode.  The constructor FREEZES G: every parameter
+    gets requires_grad_(False) and keeps it (the synthesis backward then computes the data gradient only); a caller that trains
+    the same G afterwards switches the flags back on itself."""
+    POOL_TO = 256          # LPIPS runs on images of at most this side (the projector's area pooling)
+
+    def __init__(self, G, lpips_model, steps=1000, lr=0.1, initial_noise_factor=0.05, noise_ramp=0.75, lr_rampdown=0.25, lr_rampup=0.05,
+                 noise_reg=1e5, w_avg_samples=10000, seed=0):
+        if several_processes():
+            raise ValueError("ProjectorStep: the projector runs in one process (WORLD_SIZE > 1 is not supported)")
+        if G.training:
+            raise ValueError("ProjectorStep: G must be in eval mode (G.eval()): the projection runs on fixed noise and a fixed w_avg")
+        if steps < 1 or w_avg_samples < 1:
+            raise ValueError("ProjectorStep: steps and w_avg_samples must be positive")
+        self.G, self.lpips = G, lpips_model
+        self.E = torch.nn.Module()          # no encoder: GraphReplay primes the pack tables of `E`, and an empty module has none
+        for p in G.parameters():
+            p.requires_grad_(False)
+        self.steps, self.lr, self.noise_reg, self.w_avg_samples, self.seed = int(steps), float(lr), float(noise_reg), int(w_avg_samples), int(seed)
+        self._sched = dict(initial_noise_factor=initial_noise_factor, noise_ramp=noise_ramp, lr_rampdown=lr_rampdown, lr_rampup=lr_rampup)
+        self.w_avg = self.w_std = None
+        self.w = self.opt = self.noise_table = self.noise_flat = self.noise_maps = self.noise_grads = None
+        self._ns_dev = self._seeds_dev = None
+        self._inputs_fresh = False          # graph mode: _graph_inputs has uploaded the inputs of the iteration step() is about to issue
+        self.group, self.it, self.numbers, self.last = -1, 0, [], {}
+
+    # ------------------------------------------------------------------ statistics of W
+    def w_stats(self, z=None, chunk=1000):
+        """(w_avg [512] device tensor, w_std host float), computed once and cached on the step.  z: the samples [N,512] (parity
+        runs); default: `w_avg_samples` draws of torch.randn from a CPU generator seeded with `seed`."""
+        if self.w_avg is None:
+            dev = next(self.G.parameters()).device
+            if z is None:
+                z = torch.randn(self.w_avg_samples, self.G.z_space_dim, generator=torch.Generator().manual_seed(self.seed))
+            with torch.no_grad():
+                ws = torch.cat([self.G.mapping(z[i:i + chunk].to(dev))["w"] for i in range(0, z.shape[0], chunk)])
+                self.w_avg, std = ops.rows_mean_std(ws.float().contiguous())
+            self.w_std = float(std)          # (the one host read: the schedule is a host function)
+        return self.w_avg, self.w_std
+
+    def schedule(self, iteration):
+        return projector_schedule(iteration, self.steps, self.lr, self.w_stats()[1], **self._sched)
+
+    # ------------------------------------------------------------------ per image group
+    def begin_image(self, target, numbers=None):
+        """Start the group of `target` [B,3,H,W]: w = w_avg in every row, the maps = the generator's buffers in every row, Adam's
+        state cleared, the iteration count at 0 - all in place (a captured iteration stays valid).  The maps are initialised from
+        the generator's buffers and not from fresh randn (the original's choice): the written id*-noise.pt then reproduces the
+        image with id*-wp.pt, and the run starts from the image G shows for w_avg.  numbers: the image number of every row
+        (default group * B + b), which seeds its w noise."""
+        B, dev = target.shape[0], target.device
+        w_avg, _ = self.w_stats()
+        S = self.G.synthesis
+        layers = [getattr(S, f"layer{i}") for i in range(S.num_layers - 1)]
+        if self.w is None or self.w.shape[0] != B or self.w.device != dev:
+            if self.captured:
+                raise ValueError("ProjectorStep.begin_image: the captured iteration works on a different batch")
+            D = self.G.w_space_dim
+            self.w = torch.zeros((B, D), dtype=torch.float32, device=dev, requires_grad=True)
+            self._wn = torch.empty((B, D), dtype=torch.float32, device=dev)
+            tab = self.noise_table = ops.NoiseTable([L.res for L in layers], B, dev)
+            self.noise_flat = torch.zeros(tab.numel, dtype=torch.float32, device=dev, requires_grad=True)
+            self._noise_gflat = torch.zeros(tab.numel, dtype=torch.float32, device=dev)
+            self._regv = torch.zeros(B, dtype=torch.float32, device=dev)
+            # the maps the generator sees: leaves of their own on the flat storage (their gradients go to the views of _noise_gflat)
+            self.noise_maps = [tab.view(self.noise_flat.detach(), m).requires_grad_(True) for m in range(len(layers))]
+            self.noise_grads = [tab.view(self._noise_gflat, m) for m in range(len(layers))]
+            self.opt = Adam([self.w, self.noise_flat], lr=self.lr, betas=(0.9, 0.999), eps=1e-8)
+        self.group += 1
+        self.numbers = [self.group * B + b for b in range(B)] if numbers is None else [int(n) for n in numbers]
+        if len(self.numbers) != B:
+            raise ValueError("ProjectorStep.begin_image: one image number per row")
+        with torch.no_grad():
+            self.w.copy_(w_avg.reshape(1, -1).expand_as(self.w))
+            for m, L in zip(self.noise_maps, layers):
+                m.copy_(L.noise.reshape(1, L.res, L.res).expand_as(m))
+        self.opt.graph_reset()
+        self.it = 0
+
+    def _seeds(self):
+        return [w_noise_seed(self.seed, n, self.it) for n in self.numbers]
+
+    # ------------------------------------------------------------------ one iteration
+    def step(self, target, w_noise=None):
+        """One iteration on target [B,3,H,W] in [-1,1]; `w_noise` [B,512] replaces the draws (parity runs).  Returns w [B,512], ws
+        [B,L,512] (with this iteration's noise), imgs, dist [B], reg [B], w_grad, noise_grads, noises (the maps behind the step), lr
+        and noise_scale (host floats); no host synchronisation."""
+        if self.group < 0:
+            raise RuntimeError("ProjectorStep.step: call begin_image() first")
+        B, H = target.shape[0], target.shape[2]
+        graph = self._ns_dev is not None
+        if graph and not self._inputs_fresh:          # an eager iteration behind capture(): it reads the device scalars too
+            self._graph_inputs(self.it)
+        self._inputs_fresh = False
+        lr_t, ns_t = self.schedule(self.it)
+        if w_noise is None:
+            w_noise = ops.randn_seeded(self._wn, self._seeds(), self._seeds_dev)
+        ws = _WBroadcast.apply(self.w, w_noise, self._ns_dev if graph else ns_t, self.G.num_layers)
+        imgs = self.G.synthesis(ws, randomize_noise=False, noises=self.noise_maps, noise_grad_out=self.noise_grads)["image"]
+        k = 1
+        while H // k > self.POOL_TO:
+            k *= 2
+        with torch.no_grad():
+            a, b = target.float().contiguous(), imgs.detach().float().contiguous()
+            if k > 1:
+                a, b = ops.area_pool(a, k), ops.area_pool(b, k)
+            dist, gb = self.lpips.value_and_grad(a, b, per_sample=True)
+            if B > 1:
+                ops.scale_(gb, B)          # value_and_grad returns d mean / d b; the loss is the sum over the rows
+            g_img = gb if k == 1 else ops.area_pool_bwd(gb, k)
+        self.w.grad = None
+        imgs.backward(g_img)
+        flat = self.noise_flat.detach()
+        ops.noise_reg(self.noise_table, flat, grad=self._noise_gflat, scale=self.noise_reg, accumulate=True, out=self._regv)
+        self.noise_flat.grad = self._noise_gflat
+        self.opt.step(lr=lr_t)
+        ops.noise_normalize(self.noise_table, flat)
+        self.it += 1
+        self.last = dict(w=self.w.detach(), ws=ws.detach(), imgs=imgs.detach(), dist=dist, reg=self._regv, w_grad=self.w.grad,
+                         noise_grads=self.noise_grads, noises=[m.detach() for m in self.noise_maps], lr=lr_t, noise_scale=ns_t)
+        return self.last
+
+    # ------------------------------------------------------------------ hipGraph replay of the iteration
+    def capture(self, target, warmup=GraphReplay.WARMUP):
+        """`warmup` real iterations, then one recorded (not executed) iteration (GraphReplay._capture); begin_image() must have run
+        for the group.  From here on step() reads Adam's scalars, noise_scale and the noise seeds from the device."""
+        if warmup < 1:
+            raise ValueError("ProjectorStep.capture: warmup must be at least 1: the first real iteration allocates Adam's state, which "
+                             "a recorded iteration must find in place, and its results are what the loop reads before the first replay")
+        dev = target.device
+        self._g_target = target.detach().clone()
+        self.opt.graph_begin(1, dev)
+        self._ns_dev = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._seeds_dev = torch.zeros(target.shape[0], dtype=torch.int64, device=dev)
+        self.graph_iteration = 0
+        warm = {}
+
+        def keep_last():          # the count and the results of the last executed iteration (the captured one is only recorded)
+            self._it_snap = self.it
+            warm.update({k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.last.items()})
+        out = self._capture(lambda: self.step(self._g_target), warmup, after_warmup=keep_last)
+        self.it = self._it_snap
+        self.last = warm
+        return out
+
+    def _graph_inputs(self, iteration):
+        """What the host decides for iteration `self.it` of the group (GraphReplay's own count runs across groups), uploaded from
+        fresh pageable host tensors: staged before copy_ returns, so the host may run ahead of the device."""
+        lr_t, ns_t = self.schedule(self.it)
+        self.opt.param_groups[0]["lr"] = lr_t
+        self.opt.graph_advance()
+        self._ns_dev.copy_(torch.tensor([ns_t], dtype=torch.float32))
+        self._seeds_dev.copy_(torch.tensor([s - (1 << 64) if s >= (1 << 63) else s for s in self._seeds()], dtype=torch.int64))
+        self._inputs_fresh = True
+
+    def set_image(self, target):
+        """Copies a new group's images into the static input of the captured iteration (call begin_image() for the group too)."""
+        self._set_static("_g_target", target)
+
+    def replay(self):
+        lr_t, ns_t = self.schedule(self.it)
+        out = super().replay()
+        self._inputs_fresh = False
+        self.it += 1
+        self.last = dict(out, lr=lr_t, noise_scale=ns_t)
+        return self.last
+
+    # ------------------------------------------------------------------ the result of a group
+    @torch.no_grad()
+    def result(self):
+        """(w [B,512], wp [B,L,512] = w in every row, maps, image): the projection as it stands, synthesised without w noise."""
+        w = self.w.detach()
+        wp = ops.w_broadcast(w, self.G.num_layers)
+        maps = [m.detach() for m in self.noise_maps]
+        return w, wp, maps, self.G.synthesis(wp, randomize_noise=False, noises=maps)["image"]
+
+
+def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=None, keep=None):
+    """`st.steps` iterations on the group `target` [B,3,H,W]; launch="graph" captures the iteration once (its warm-up iteration is a
+    real one) and replays it, later groups go through set_image.  With `out_dir`: a Loss.txt line per kept row at every
+    `save_every`-th iteration and at the end (one host read each), and the files of the module docstring for the first `keep` rows
+    (default: all), numbered by `numbers`.  Returns the last result dict with `w`, `wp`, `noises` and `rec` of ProjectorStep.result()."""
+    from .embedding import select_launch
+    from .infer import quantize_u8, save_u8
+    if launch not in ("graph", "eager"):
+        raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
+    B = target.shape[0]
+    keep = B if keep is None else keep
+    st.begin_image(target, numbers=numbers)
+    nums = st.numbers
+    run, done = select_launch(st, target, launch)
+    r = st.last
+
+    def log(i):
+        vals = torch.stack((r["dist"], r["reg"])).cpu()
+        with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
+            for b in range(keep):
+                print("id_%d_____i_%d  dist: %s  noise_reg: %s  lr: %s  noise_scale: %s" % (nums[b], i, float(vals[0, b]), float(vals[1, b]),
+                                                                                       r["lr"], r["noise_scale"]), file=f)
+    for i in range(max(st.steps, done)):
+        if i >= done:          # (with done == 1, iteration 0 ran as capture()'s warm-up)
+            r = run()
+        if out_dir is not None and save_every and (i % save_every == 0 or i == st.steps - 1):
+            log(i)
+    w, wp, maps, rec = st.result()
+    if out_dir is not None:
+        for sub in ("real", "rec", "models"):
+            os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
+        q_real, q_rec = quantize_u8(target.float()), quantize_u8(rec)
+        wc, wpc, mc = w.cpu(), wp.cpu(), [m.cpu() for m in maps]
+        for b in range(keep):
+            n = nums[b]
+            save_u8(q_real[b], os.path.join(out_dir, "real", "%05d.png" % n))
+            save_u8(q_rec[b], os.path.join(out_dir, "rec", "%05d.png" % n))
+            torch.save(wc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-w.pt" % n))
+            torch.save(wpc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-wp.pt" % n))
+            torch.save([m[b:b + 1].clone() for m in mc], os.path.join(out_dir, "models", "id%d-noise.pt" % n))
+    return dict(r, w=w, wp=wp, noises=maps, rec=rec)
+
+
+# ------------------------------------------------------------------ CLI
+def make_parser():
+    from .embedding_v2 import strict_bool
+    from .infer import add_lpips_args
+    from .models import add_model_args
+    p = argparse.ArgumentParser(prog="dge_amd.projector", description="StyleGAN2's projector: W and noise-map optimisation against LPIPS")
+    add_model_args(p)
+    p.set_defaults(mtype=2)
+    p.add_argument("--img_dir", default="./real_imgs/", help="a directory of images or a .pt tensor in [0,1]")
+    p.add_argument("--experiment_dir", default="./projector_result")
+    p.add_argument("--steps", type=int, default=1000)
+    p.add_argument("--batch_size", type=int, default=1, help="images projected side by side, each as in its batch-1 run")
+    p.add_argument("--lr", type=float, default=0.1)
+    p.add_argument("--initial_noise_factor", type=float, default=0.05)
+    p.add_argument("--noise_ramp", type=float, default=0.75)
+    p.add_argument("--lr_rampdown", type=float, default=0.25)
+    p.add_argument("--lr_rampup", type=float, default=0.05)
+    p.add_argument("--noise_reg", type=float, default=1e5, help="weight of the noise regulariser")
+    p.add_argument("--w_avg_samples", type=int, default=10000)
+    p.add_argument("--launch", choices=("eager", "graph"), default="graph")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--save_every", type=int, default=100)
+    p.add_argument("--deterministic", type=strict_bool, default=False, help="true: bit-reproducible reductions (ops.set_deterministic)")
+    add_lpips_args(p)
+    return p
+
+
+def parse_args(argv=None):
+    args = make_parser().parse_args(argv)
+    if args.mtype != 2:
+        raise SystemExit("projector: --mtype must be 2 (StyleGAN2): StyleGAN1, PGGAN and BigGAN are not offered")
+    if several_processes(env=True):
+        raise SystemExit("projector: runs in one process (WORLD_SIZE > 1 is not supported)")
+    if args.steps < 1 or args.batch_size < 1:
+        raise SystemExit("projector: --steps and --batch_size must be positive")
+    return args
+
+
+def main(argv=None):
+    from .embedding_v2 import _load_imgs, load_generator_smooth, rows_plan
+    from .lpips import LPIPS
+    from .models import load_lpips_weights
+    from .stylegan2_generator import StyleGAN2Generator
+    args = parse_args(argv)
+    if args.deterministic:
+        ops.set_deterministic(True)
+    dev = "cuda"
+    torch.manual_seed(args.seed)
+    kw = {k: getattr(args, k) for k in ("fmaps_base", "fmaps_max") if getattr(args, k) is not None}
+    G = StyleGAN2Generator(args.img_size, compute_dtype=args.compute_dtype, **kw).to(dev)
+    G.eval()
+    if args.checkpoint_dir_GAN:
+        load_generator_smooth(G, args.checkpoint_dir_GAN)
+    LP = load_lpips_weights(LPIPS(compute_dtype=args.compute_dtype).to(dev), args.vgg_weights, args.lpips_weights,
+                            allow_standin=args.allow_standin_lpips)
+    out = args.experiment_dir
+    os.makedirs(out, exist_ok=True)
+    imgs = _load_imgs(args.img_dir, args.img_size, dev)
+    st = ProjectorStep(G, LP, steps=args.steps, lr=args.lr, initial_noise_factor=args.initial_noise_factor, noise_ramp=args.noise_ramp,
+                       lr_rampdown=args.lr_rampdown, lr_rampup=args.lr_rampup, noise_reg=args.noise_reg, w_avg_samples=args.w_avg_samples,
+                       seed=args.seed)
+    for first, keep, idx, _ in rows_plan(imgs.shape[0], args.batch_size):
+        r = project(st, imgs[idx].contiguous(), out, args.save_every, args.launch, numbers=idx, keep=keep)
+        vals = torch.stack((r["dist"], r["reg"])).cpu()
+        for b in range(keep):
+            print("image %d: dist %.5f  noise_reg %.3e" % (first + b, float(vals[0, b]), float(vals[1, b])))
+    return st
+
+
+if __name__ == "__main__":
+    main()

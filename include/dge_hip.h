@@ -837,6 +837,37 @@ int dge_noise_reg(const dge_noise_plan* plan, const float* n, float* reg, float*
 int dge_noise_normalize_work_bytes(const dge_noise_plan* plan);
 int dge_noise_normalize(const dge_noise_plan* plan, float* n, void* work, long long work_bytes, dge_stream_t stream);
 
+/* ---- StyleGAN2's projector (dge_amd.projector): one W code, Adam with a first moment, the W statistics ----------------------- */
+/* All f32; no atomics, nothing pre-zeroed, every sum in a fixed order: the same bits from run to run and in both reduction modes,
+ * and row b of a batch call equals the call on row b alone.
+ * Multi-tensor Adam with torch.optim.Adam's update (no amsgrad, no weight decay), one launch for all tensors:
+ *   m = beta1*m + (1-beta1)*g ;  v = beta2*v + (1-beta2)*g^2 ;  p -= step * m / (sqrt(v) * inv_sqrt_bc2 + eps)
+ * with step = lr_t / (1 - beta1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t) computed by the host.  scalars_dev (optional): two
+ * DEVICE floats (step, inv_sqrt_bc2) that replace the host values (a captured hipGraph of the step is replayed with new ones).
+ * Tensors whose four pointers are 16-byte aligned go four elements at a time with a scalar tail.  host_*: HOST arrays of device
+ * pointers / element counts, as in dge_lreq_adam_multi.  The betas are doubles: 1 - beta is formed in double and rounded once, as
+ * torch does (1 - 0.999f is off by 1.3e-5 of its value).  step == 0 leaves the bits of p.  dge_last_kernel: "adam_multi". */
+int dge_adam_multi(int ntensors, float* const* host_p, const float* const* host_g, float* const* host_m, float* const* host_v,
+                   const long* host_n, double beta1, double beta2, float eps, float step, float inv_sqrt_bc2, const float* scalars_dev,
+                   dge_stream_t stream);
+/* ws[b,l,:] = w[b,:] + noise[b,:] * scale for l < L (w, noise [B,D]; ws [B,L,D]).  The product is rounded before the add (no fma):
+ * the bits of torch's `w + noise * scale`.  noise == NULL: ws[b,l,:] = w[b,:].  scale_dev (optional): a DEVICE float that replaces
+ * `scale`.  dge_last_kernel: "w_broadcast". */
+int dge_w_broadcast(const float* w, const float* noise, float scale, const float* scale_dev, float* ws, int B, int L, int D,
+                    dge_stream_t stream);
+/* g_w[b,:] = sum_l g_ws[b,l,:], l ascending in one accumulator per element.  dge_last_kernel: "w_broadcast_bwd". */
+int dge_w_broadcast_bwd(const float* g_ws, float* g_w, int B, int L, int D, dge_stream_t stream);
+/* x [N,D] (D a multiple of 4) -> mean [D] over the rows and the scalar std[0] = sqrt(sum_{n,d} (x[n,d] - mean[d])^2 / N), the
+ * projector's w_std.  Two passes over chunks of 64 rows: column sums of a chunk to its slot, the slots added in slot order; then
+ * the squared deviations of a chunk's (up to) 1024 columns to a slot, those added by one workgroup in a fixed order.
+ * work: dge_rows_mean_std_work_bytes(N, D) bytes (-1: sizes it refuses).  dge_last_kernel: "rows_mean_std". */
+int dge_rows_mean_std_work_bytes(long long N, int D);
+int dge_rows_mean_std(const float* x, long long N, int D, float* mean, float* std, void* work, long long work_bytes,
+                      dge_stream_t stream);
+/* Adjoint of the k x k area pooling (dge_crop_pool_multi on the whole image): g [BC,H,W] = g_pooled [BC,H/k,W/k] at (y/k, x/k),
+ * divided by k*k (a correctly rounded division).  g is written, not accumulated.  dge_last_kernel: "area_pool_bwd". */
+int dge_area_pool_bwd(const float* g_pooled, float* g, int BC, int H, int W, int k, dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
