@@ -235,6 +235,14 @@ SIGNATURES = {
     "dge_rows_mean_std_work_bytes": [C.c_longlong, _I],
     "dge_rows_mean_std": [_P, C.c_longlong, _I, _P, _P, _P, C.c_longlong, _P],
     "dge_area_pool_bwd": [_P, _P, _I, _I, _I, _I, _P],
+    "dge_mask_pyramid_work_bytes": [_I, _I, _I],
+    "dge_mask_pyramid": [_P, _P, _P, _P, _I, _I, _I, _P, C.c_longlong, _P],
+    "dge_lpips_prep_masked": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P],
+    "dge_lpips_prep_bwd_masked": [_P, _P, _P, _I, _I, _I, _P, _F, _I, _I, _P],
+    "dge_lpips_head_w_slots": [_I, _I, _I],
+    "dge_lpips_head_w": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _F, _I, _P],
+    "dge_lpips_head_w_finalize": [_P, _P, _P, _P, _P, _I, _P],
+    "dge_mask_blend": [_P, _P, _P, _P, _I, _I, _P],
 }
 
 _lib = None

@@ -5,35 +5,10 @@
 // called at training_utils.py:93 / E_align_s2.py:98 - structure restated from the published
 // method; see oracle/lpips_ref.py for the CPU restatement and DESIGN.md for the parity caveat.
 #include "common.h"
+#include "lpips_prep.h"
 #include "../../include/dge_hip.h"
 
-// img [B,3,h,w] f32 -> x [B,h,w,CP] T (CP >= 3, extra channels zero): (img - shift[c]) / scale[c]
-template <typename T>
-__global__ void lpips_prep_kernel(const float* __restrict__ img, T* __restrict__ x, int B, int HW, int CP,
-                                  float s0, float s1, float s2, float i0, float i1, float i2) {
-    const long idx = blockIdx.x * 256L + threadIdx.x;
-    if (idx >= (long)B * HW) return;
-    const int b = idx / HW, p = idx % HW;
-    const float* ib = img + (size_t)b * 3 * HW;
-    T* xp = x + (size_t)idx * CP;
-    Elem<T>::st(xp + 0, (ib[p] - s0) * i0);
-    Elem<T>::st(xp + 1, (ib[HW + p] - s1) * i1);
-    Elem<T>::st(xp + 2, (ib[2 * HW + p] - s2) * i2);
-    for (int c = 3; c < CP; c++) Elem<T>::st(xp + c, 0.f);
-}
-// adjoint: gimg[b,c,p] (+)= factor * gx[b,p,c] * inv_scale[c]
-template <typename T>
-__global__ void lpips_prep_bwd_kernel(const T* __restrict__ gx, float* __restrict__ gimg, int B, int HW, int CP,
-                                      float i0, float i1, float i2, float factor, int accumulate) {
-    const long idx = blockIdx.x * 256L + threadIdx.x;
-    if (idx >= (long)B * HW) return;
-    const int b = idx / HW, p = idx % HW;
-    const T* xp = gx + (size_t)idx * CP;
-    float* gb = gimg + (size_t)b * 3 * HW;
-    const float v0 = Elem<T>::ld(xp) * i0 * factor, v1 = Elem<T>::ld(xp + 1) * i1 * factor, v2 = Elem<T>::ld(xp + 2) * i2 * factor;
-    if (accumulate) { gb[p] += v0; gb[HW + p] += v1; gb[2 * HW + p] += v2; }
-    else { gb[p] = v0; gb[HW + p] = v1; gb[2 * HW + p] = v2; }
-}
+// input scaling + NHWC packing and its adjoint: lpips_prep.h (one body with the masked entry points of lpips_mask_kernels.hip)
 
 // 2x2 max pooling, stride 2, floor (nn.MaxPool2d(2,2)); NHWC
 template <typename T>
@@ -197,8 +172,8 @@ extern "C" int dge_lpips_prep(const float* img, void* x, int B, int HW, int cpad
     DGE_CHECK(cpad >= 3, "lpips_prep: cpad < 3");
     const long n = (long)B * HW;
     const float i0 = 1.f / host_scale3[0], i1 = 1.f / host_scale3[1], i2 = 1.f / host_scale3[2];
-    if (dtype == DGE_BF16) hipLaunchKernelGGL(lpips_prep_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, (bf16_t*)x, B, HW, cpad, host_shift3[0], host_shift3[1], host_shift3[2], i0, i1, i2);
-    else hipLaunchKernelGGL(lpips_prep_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, (float*)x, B, HW, cpad, host_shift3[0], host_shift3[1], host_shift3[2], i0, i1, i2);
+    if (dtype == DGE_BF16) hipLaunchKernelGGL((lpips_prep_kernel<bf16_t, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, (const float*)nullptr, (bf16_t*)x, B, HW, cpad, host_shift3[0], host_shift3[1], host_shift3[2], i0, i1, i2);
+    else hipLaunchKernelGGL((lpips_prep_kernel<float, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, (const float*)nullptr, (float*)x, B, HW, cpad, host_shift3[0], host_shift3[1], host_shift3[2], i0, i1, i2);
     DGE_LAUNCH_CHECK("lpips_prep");
     return 0;
 }
@@ -207,8 +182,8 @@ extern "C" int dge_lpips_prep_bwd(const void* gx, float* gimg, int B, int HW, in
                                   int accumulate, int dtype, hipStream_t s) {
     const long n = (long)B * HW;
     const float i0 = 1.f / host_scale3[0], i1 = 1.f / host_scale3[1], i2 = 1.f / host_scale3[2];
-    if (dtype == DGE_BF16) hipLaunchKernelGGL(lpips_prep_bwd_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)gx, gimg, B, HW, cpad, i0, i1, i2, factor, accumulate);
-    else hipLaunchKernelGGL(lpips_prep_bwd_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)gx, gimg, B, HW, cpad, i0, i1, i2, factor, accumulate);
+    if (dtype == DGE_BF16) hipLaunchKernelGGL((lpips_prep_bwd_kernel<bf16_t, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16_t*)gx, (const float*)nullptr, gimg, B, HW, cpad, i0, i1, i2, factor, accumulate);
+    else hipLaunchKernelGGL((lpips_prep_bwd_kernel<float, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)gx, (const float*)nullptr, gimg, B, HW, cpad, i0, i1, i2, factor, accumulate);
     DGE_LAUNCH_CHECK("lpips_prep_bwd");
     return 0;
 }

@@ -144,11 +144,31 @@ class LPIPS(nn.Module):
         return hit[1], hit[2]
 
     # ---------------------------------------------------------------- forward (+ gradient w.r.t. b)
-    def value_and_grad(self, a, b, need_grad=True, per_sample=False):
+    def mask_state(self, mask):
+        """The pyramid of `mask` [B,1,h,w] (f32 in [0,1], 1 = fit the pixel) with the workspaces of the weighted heads, as one object
+        for value_and_grad(mask_state=...); MaskState.set(mask) refills it in place."""
+        return MaskState(mask, _dt(self.compute_dtype))
+
+    def value_and_grad(self, a, b, need_grad=True, per_sample=False, mask=None, mask_state=None):
         """a, b: [B,3,h,w] f32 in [-1,1].  Returns (mean over the batch of LPIPS(a,b) as a [1]
         device tensor, d mean / d b  [B,3,h,w] f32 or None).  per_sample: the first result is LPIPS(a[i], b[i]) as a [B] device
-        tensor instead of its mean (the gradient is still d mean / d b: B times it is the gradient of the sum)."""
+        tensor instead of its mean (the gradient is still d mean / d b: B times it is the gradient of the sum).
+        mask [B,1,h,w] f32 in [0,1] (or mask_state, the prepared form of one: self.mask_state(mask)): the masked distance.  Both
+        images are multiplied by the mask before VGG (a hole reads as mid-grey in both), tap k is averaged with the weights m_k /
+        sum m_k of the mask's level k (m_k = avg_pool2d(m_{k-1}, 2), floor sizes), a level of sum 0 contributes 0, and the gradient
+        that leaves VGG is multiplied by the mask.  Without either the launches are the unmasked ones."""
         dt = _dt(self.compute_dtype)
+        if mask is not None or mask_state is not None:
+            if a.shape[1] == 1:
+                raise ValueError("LPIPS: a mask together with a single-channel image is not provided")
+            if mask_state is None:
+                mask_state = MaskState(mask, dt)
+            elif mask is not None:
+                raise ValueError("LPIPS: pass mask or mask_state, not both")
+            if mask_state.shape != (a.shape[0], a.shape[2], a.shape[3]) or mask_state.dt != dt:
+                raise ValueError(f"LPIPS: the mask state was made for [B,h,w] = {mask_state.shape}, compute dtype {mask_state.dt}; "
+                                 f"the images are {tuple(a.shape)}, compute dtype {dt}")
+        ms = mask_state
         if a.shape[1] == 1:
             # single-channel maps (the Grad-CAM masks of E_mis_align_cropping_s1.py:182): lpips' ScalingLayer broadcasts
             # them against its [1,3,1,1] constants, i.e. the map is fed as three identical channels
@@ -161,8 +181,12 @@ class LPIPS(nn.Module):
         L = lib()
         shift, scale = self._scaling_host()
         x = torch.empty((2 * B, h, w, _CPAD), dtype=ops.tdtype(dt), device=dev)
-        check(L.dge_lpips_prep(_f32(a.contiguous()), _p(x[:B]), B, h * w, _CPAD, shift, scale, dt, _stream()), "dge_lpips_prep")
-        check(L.dge_lpips_prep(_f32(b.contiguous()), _p(x[B:]), B, h * w, _CPAD, shift, scale, dt, _stream()), "dge_lpips_prep")
+        if ms is not None:
+            ops.lpips_prep_masked(a.contiguous(), ms.levels[0], x[:B], shift, scale, _CPAD)
+            ops.lpips_prep_masked(b.contiguous(), ms.levels[0], x[B:], shift, scale, _CPAD)
+        else:
+            check(L.dge_lpips_prep(_f32(a.contiguous()), _p(x[:B]), B, h * w, _CPAD, shift, scale, dt, _stream()), "dge_lpips_prep")
+            check(L.dge_lpips_prep(_f32(b.contiguous()), _p(x[B:]), B, h * w, _CPAD, shift, scale, dt, _stream()), "dge_lpips_prep")
         acts, pools = [], {}        # acts[ci] = output of conv ci (post relu); pools[ci] = pooled input of conv ci
         ci = 0
         cur = x
@@ -183,15 +207,20 @@ class LPIPS(nn.Module):
                 cur = ops.conv2d(cur, self._packed(ci, dt, ops.PACK_FWD, cur.shape[1:3]), item[1], 3, bias=conv.bias.detach(), act=ops.ACT_RELU)
             acts.append(cur)
             ci += 1
-        val = torch.zeros(B, dtype=torch.float32, device=dev)
+        val = torch.zeros(B, dtype=torch.float32, device=dev) if ms is None else torch.empty(B, dtype=torch.float32, device=dev)
         heads = []
         for k, cidx in enumerate(_TAP_AFTER):
             f = acts[cidx]
             _, fh, fw, fc = f.shape
             g1 = torch.empty((B, fh, fw, fc), dtype=f.dtype, device=dev) if need_grad else None
             lin = getattr(self, f"lin{k}").model._modules["1"].weight.detach().reshape(-1).contiguous()
-            check(L.dge_lpips_head(_p(f), _f32(lin), _p(val), _p(g1), B, fh * fw, fc, 1.0 / B, dt, _stream()), "dge_lpips_head")
+            if ms is not None:
+                ops.lpips_head_w(f, lin, ms.levels[k], ms.inv_sum, k, ms.tap_slots(k), g1, 1.0 / B)
+            else:
+                check(L.dge_lpips_head(_p(f), _f32(lin), _p(val), _p(g1), B, fh * fw, fc, 1.0 / B, dt, _stream()), "dge_lpips_head")
             heads.append(g1)
+        if ms is not None:
+            ops.lpips_head_w_finalize(ms.slots, ms.offsets, ms.nslots, ms.inv_sum, val)
         if per_sample:
             out = val
         else:
@@ -219,7 +248,10 @@ class LPIPS(nn.Module):
             else:
                 g_pre = ops.conv2d(g_pre, wd, cin, 3, addend=head, relu_mask=below)
         gb = torch.empty((B, 3, h, w), dtype=torch.float32, device=dev)
-        check(L.dge_lpips_prep_bwd(_p(g), _p(gb), B, h * w, _CPAD, scale, 1.0, 0, dt, _stream()), "dge_lpips_prep_bwd")
+        if ms is not None:
+            ops.lpips_prep_bwd_masked(g, ms.levels[0], gb, scale, _CPAD)
+        else:
+            check(L.dge_lpips_prep_bwd(_p(g), _p(gb), B, h * w, _CPAD, scale, 1.0, 0, dt, _stream()), "dge_lpips_prep_bwd")
         return out, gb
 
     def forward(self, a, b):
@@ -229,6 +261,56 @@ class LPIPS(nn.Module):
             v, _ = self.value_and_grad(a[i:i + 1], b[i:i + 1], need_grad=False)
             vals.append(v)
         return torch.stack(vals).view(-1, 1, 1, 1)
+
+
+class MaskState:
+    """A mask [B,1,h,w] prepared for LPIPS.value_and_grad: the five levels and inv_sum / sums [B,5] of ops.mask_pyramid, and the slot
+    workspace of the five weighted heads.  All storage is allocated once; set(mask) refills it in place with one dge_mask_pyramid
+    call (no host sync), so a captured iteration that read this state reads the new mask at its next replay."""
+    _TAP_CH = [64, 128, 256, 512, 512]
+
+    def __init__(self, mask, dt):
+        m = self._plane(mask)
+        B, h, w = m.shape
+        if min(h, w) < 16:
+            raise ValueError(f"MaskState: the image side must be at least 16 (tap 4 needs one pixel), got {h} x {w}")
+        self.shape, self.dt, dev = (B, h, w), dt, m.device
+        shapes = ops.mask_level_shapes(h, w)
+        self._flat = torch.empty(B * sum(hk * wk for hk, wk in shapes), dtype=torch.float32, device=dev)
+        self.inv_sum = torch.empty((B, ops.MASK_LEVELS), dtype=torch.float32, device=dev)
+        self.sums = torch.empty((B, ops.MASK_LEVELS), dtype=torch.float32, device=dev)
+        self._work = torch.empty(ops.mask_pyramid_work_bytes(B, h, w) // 4, dtype=torch.float32, device=dev)
+        self.nslots = [ops.lpips_head_w_slots(hk * wk, c, dt) for (hk, wk), c in zip(shapes, self._TAP_CH)]
+        self.offsets, off = [], 0
+        for n in self.nslots:
+            self.offsets.append(off)
+            off += B * n
+        self.slots = torch.empty(off, dtype=torch.float32, device=dev)
+        self.levels = None
+        self.set(m)
+
+    @staticmethod
+    def _plane(mask):
+        if mask.dim() == 4 and mask.shape[1] == 1:
+            mask = mask[:, 0]
+        if mask.dim() != 3 or mask.dtype != torch.float32:
+            raise ValueError(f"LPIPS mask: expected [B,1,h,w] f32 in [0,1], got {tuple(mask.shape)} {mask.dtype}")
+        return mask.contiguous()
+
+    def set(self, mask):
+        """Refill the state from `mask` (same shape) in place."""
+        m = self._plane(mask)
+        if tuple(m.shape) != self.shape:
+            raise ValueError(f"MaskState.set: the state holds a mask of [B,h,w] = {self.shape}, got {tuple(m.shape)}")
+        self.levels, _, _ = ops.mask_pyramid(m, self._flat, self.inv_sum, self.sums, self._work)
+        return self
+
+    def tap_slots(self, k):
+        return self.slots[self.offsets[k]:self.offsets[k] + self.shape[0] * self.nslots[k]]
+
+    def cover(self):
+        """[B] = sum m_0 / (h w): the share of the image the mask keeps (a device tensor)."""
+        return self.sums[:, 0] / float(self.shape[1] * self.shape[2])
 
 
 _VGG_CIN = [item[0] for item in _VGG if item != "M"]

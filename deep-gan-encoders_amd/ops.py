@@ -1897,3 +1897,121 @@ def randn_seeded(out, seeds, seeds_dev=None):
                               C.c_ulonglong(int(seeds[r]) & 0xFFFFFFFFFFFFFFFF), sd, _stream()), "dge_randn")
         _log_dense("dge_randn")
     return out
+
+
+# ---- masked LPIPS (include/dge_hip.h dge_mask_pyramid / dge_lpips_prep_masked / dge_lpips_head_w / dge_mask_blend)
+MASK_LEVELS = 5
+
+
+def mask_level_shapes(H, W):
+    """(h_k, w_k) of the five mask levels: floor halving, the grids of the five LPIPS-VGG taps."""
+    return [(H >> k, W >> k) for k in range(MASK_LEVELS)]
+
+
+def mask_pyramid_work_bytes(B, H, W):
+    n = lib().dge_mask_pyramid_work_bytes(int(B), int(H), int(W))
+    if n < 0:
+        check(n, "dge_mask_pyramid_work_bytes")
+    return n
+
+
+def mask_pyramid(m, levels=None, inv_sum=None, sums=None, work=None):
+    """m [B,H,W] f32 -> (levels: the list of the five levels [B,h_k,w_k], views of one flat buffer; inv_sum [B,5] = 1 / sum of a
+    level, 0 where the sum is 0; sums [B,5]).  `levels` (the flat buffer), inv_sum, sums and work may be passed in to be refilled in
+    place (a captured iteration keeps reading them).  No host sync."""
+    if m.dim() != 3 or m.dtype != torch.float32:
+        raise DgeError(f"mask_pyramid: expected a [B,H,W] f32 mask, got {tuple(m.shape)} {m.dtype}")
+    B, H, W = m.shape
+    shapes = mask_level_shapes(H, W)
+    total = B * sum(h * w for h, w in shapes)
+    dev = m.device
+    flat = torch.empty(total, dtype=torch.float32, device=dev) if levels is None else levels
+    if flat.dtype != torch.float32 or flat.numel() != total:
+        raise DgeError(f"mask_pyramid: levels must be a flat f32 buffer of {total} floats")
+    inv_sum = torch.empty((B, MASK_LEVELS), dtype=torch.float32, device=dev) if inv_sum is None else inv_sum
+    sums = torch.empty((B, MASK_LEVELS), dtype=torch.float32, device=dev) if sums is None else sums
+    if inv_sum.numel() != B * MASK_LEVELS or sums.numel() != B * MASK_LEVELS:
+        raise DgeError("mask_pyramid: inv_sum and sums hold [B,5] floats")
+    nb = mask_pyramid_work_bytes(B, H, W)
+    if work is None:
+        work = torch.empty(nb // 4, dtype=torch.float32, device=dev)
+    check(lib().dge_mask_pyramid(_f32(m.contiguous()), _f32(flat), _f32(inv_sum), _f32(sums), B, H, W, _p(work),
+                                 work.numel() * work.element_size(), _stream()), "dge_mask_pyramid")
+    _log_dense("dge_mask_pyramid")
+    views, off = [], 0
+    for h, w in shapes:
+        views.append(flat[off:off + B * h * w].view(B, h, w))
+        off += B * h * w
+    return views, inv_sum, sums
+
+
+def lpips_prep_masked(img, mask, x, shift3, scale3, cpad):
+    """x [B,h,w,cpad] <- ((mask * img) - shift) / scale, NHWC (dge_lpips_prep with the per-pixel factor mask [B,h,w])."""
+    B, _, h, w = img.shape
+    if mask.dtype != torch.float32 or mask.numel() != B * h * w:
+        raise DgeError(f"lpips_prep_masked: the mask holds {mask.numel()} floats, {B * h * w} expected")
+    check(lib().dge_lpips_prep_masked(_f32(img), _f32(mask), _p(x), B, h * w, int(cpad), shift3, scale3, dtype_of(x), _stream()),
+          "dge_lpips_prep_masked")
+    _log_dense("dge_lpips_prep_masked")
+    return x
+
+
+def lpips_prep_bwd_masked(gx, mask, gimg, scale3, cpad, factor=1.0, accumulate=False):
+    """gimg [B,3,h,w] (+)= (factor * gx[..., :3] / scale) * mask (dge_lpips_prep_bwd with the per-pixel factor mask [B,h,w])."""
+    B, _, h, w = gimg.shape
+    if mask.dtype != torch.float32 or mask.numel() != B * h * w:
+        raise DgeError(f"lpips_prep_bwd_masked: the mask holds {mask.numel()} floats, {B * h * w} expected")
+    check(lib().dge_lpips_prep_bwd_masked(_p(gx), _f32(mask), _f32(gimg), B, h * w, int(cpad), scale3, float(factor), 1 if accumulate else 0,
+                                          dtype_of(gx), _stream()), "dge_lpips_prep_bwd_masked")
+    _log_dense("dge_lpips_prep_bwd_masked")
+    return gimg
+
+
+def lpips_head_w_slots(HW, Cc, dtype):
+    """Slots per row of one tap's weighted head (the workgroups that walk a row's pixels)."""
+    n = lib().dge_lpips_head_w_slots(int(HW), int(Cc), int(dtype))
+    if n < 0:
+        check(n, "dge_lpips_head_w_slots")
+    return n
+
+
+def lpips_head_w(feat, lin, mk, inv_sum, tap, slots, g1=None, gscale=1.0):
+    """The weighted head of tap `tap`: feat [2B,h,w,C], mk [B,h,w], inv_sum [B,5]; slots [B, lpips_head_w_slots] is written, g1
+    (optional, [B,h,w,C]) = gscale * mk * inv_sum[:, tap] * d d / d feat[B:]."""
+    B2, h, w, Cc = feat.shape
+    B = B2 // 2
+    dt = dtype_of(feat)
+    n = lpips_head_w_slots(h * w, Cc, dt)
+    if mk.numel() != B * h * w or inv_sum.numel() != B * MASK_LEVELS or slots.numel() != B * n:
+        raise DgeError(f"lpips_head_w: mk holds {mk.numel()} floats ({B * h * w} expected), slots {slots.numel()} ({B * n} expected)")
+    if g1 is not None and (g1.dtype != feat.dtype or g1.numel() != B * h * w * Cc):
+        raise DgeError("lpips_head_w: g1 must be [B,h,w,C] in the features' dtype")
+    check(lib().dge_lpips_head_w(_p(feat), _f32(lin), _f32(mk), _f32(inv_sum), int(tap), _f32(slots), _p(g1), B, h * w, Cc, float(gscale), dt,
+                                 _stream()), "dge_lpips_head_w")
+    _log_dense("dge_lpips_head_w")
+    return g1
+
+
+def lpips_head_w_finalize(slots, offsets, nslots, inv_sum, dist):
+    """dist [B] <- sum over the five taps of inv_sum[b,k] * (the slots of tap k, row b, in a fixed order).  slots: the flat
+    workspace; offsets[k], nslots[k]: where tap k's [B, nslots[k]] block starts and how many slots a row has."""
+    B = dist.numel()
+    if len(offsets) != MASK_LEVELS or len(nslots) != MASK_LEVELS or offsets[-1] + B * nslots[-1] > slots.numel():
+        raise DgeError("lpips_head_w_finalize: five tap blocks inside the workspace")
+    check(lib().dge_lpips_head_w_finalize(_f32(slots), (C.c_longlong * MASK_LEVELS)(*[int(o) for o in offsets]),
+                                          (C.c_int * MASK_LEVELS)(*[int(n) for n in nslots]), _f32(inv_sum), _f32(dist), B, _stream()),
+          "dge_lpips_head_w_finalize")
+    _log_dense("dge_lpips_head_w_finalize")
+    return dist
+
+
+def mask_blend(m, a, b, out=None):
+    """m [B,1,H,W], a, b [B,3,H,W] f32 -> m * a + (1 - m) * b, the bits of torch's expression (feeds quantize_u8)."""
+    B, Cc, H, W = a.shape
+    if Cc != 3 or a.shape != b.shape or m.numel() != B * H * W or any(t.dtype != torch.float32 for t in (m, a, b)):
+        raise DgeError(f"mask_blend: two [B,3,H,W] f32 images and a [B,1,H,W] f32 mask, got {tuple(a.shape)}, {tuple(b.shape)}, {tuple(m.shape)}")
+    if out is None:
+        out = torch.empty_like(a, memory_format=torch.contiguous_format)
+    check(lib().dge_mask_blend(_f32(m.contiguous()), _f32(a.contiguous()), _f32(b.contiguous()), _f32(out), B, H * W, _stream()), "dge_mask_blend")
+    _log_dense("dge_mask_blend")
+    return out

@@ -32,7 +32,16 @@ Decisions:
 Files of `project` / the CLI: real/{n:05d}.png and rec/{n:05d}.png (the bytes of infer.quantize_u8: `compare --dir1 real --dir2
 rec` works on the output), models/id{n}-w.pt [1,512], models/id{n}-wp.pt [1,L,512], models/id{n}-noise.pt (the list of maps, each
 [1,res,res], as embedding_v2 writes it) and Loss.txt.  Images are numbered across the folder; a short last group repeats its last
-image and discards the padded rows, as `embedding_v2 --independent true` does."""
+image and discards the padded rows, as `embedding_v2 --independent true` does.
+
+Masked projection (`--mask_dir DIR|x.pt`, ProjectorStep.begin_image(mask=...), project(mask=...)): a mask [B,1,H,W] in [0,1] at the
+target's size, 1 = fit the pixel, 0 = ignore it.  The mask is area-pooled with the images; both LPIPS inputs are multiplied by it
+(a hole is mid-grey in both) and tap k is averaged with the weights m_k / sum m_k of the mask's level k (csrc/lpips_mask_kernels.hip,
+LPIPS.value_and_grad(mask_state=...)).  The pyramid is refilled once per group, outside the captured iteration; a step captured
+without a mask refuses a later mask and the other way round.  Extra files with a mask: blend/{n:05d}.png (the target inside the mask,
+the reconstruction outside: the bytes of quantize_u8(ops.mask_blend(mask, real, rec))), mask/{n:05d}.png (8-bit L), and `cover: ...`
+(the kept share of the image) at the end of every Loss.txt line; the result dict gains `mask_cover` [B].  A short last group pads the
+mask as it pads the image.  Without a mask nothing is written or launched that was not before."""
 import argparse
 import math
 import os
@@ -101,6 +110,7 @@ class ProjectorStep(GraphReplay):
         self.w_avg = self.w_std = None
         self.w = self.opt = self.noise_table = self.noise_flat = self.noise_maps = self.noise_grads = None
         self._ns_dev = self._seeds_dev = None
+        self._mask_state = self._mask_cover = self._graph_masked = None
         self._inputs_fresh = False          # graph mode: _graph_inputs has uploaded the inputs of the iteration step() is about to issue
         self.group, self.it, self.numbers, self.last = -1, 0, [], {}
 
@@ -122,13 +132,49 @@ class ProjectorStep(GraphReplay):
         return projector_schedule(iteration, self.steps, self.lr, self.w_stats()[1], **self._sched)
 
     # ------------------------------------------------------------------ per image group
-    def begin_image(self, target, numbers=None):
+    def _pool_k(self, H):
+        k = 1
+        while H // k > self.POOL_TO:
+            k *= 2
+        return k
+
+    def _set_mask(self, target, mask, who):
+        """The group's mask [B,1,H,W] (or None) into the step: pooled by the step's k to the LPIPS resolution, the state refilled in
+        place (one dge_mask_pyramid call outside the captured iteration), mask_cover refreshed in place."""
+        if self.captured and (mask is not None) != self._graph_masked:
+            raise ValueError(f"ProjectorStep.{who}: the iteration was captured " + ("with a mask, and this group has none" if self._graph_masked
+                             else "without a mask, and this group has one") + "; the masked and the unmasked iteration are different "
+                             "launches: use a step of its own for each")
+        if mask is None:
+            self._mask_state = self._mask_cover = None
+            return
+        B, _, H, W = target.shape
+        if mask.dim() == 3:
+            mask = mask[:, None]
+        if tuple(mask.shape) != (B, 1, H, W):
+            raise ValueError(f"ProjectorStep.{who}: the mask must be [B,1,H,W] = {(B, 1, H, W)} at the target's size, got {tuple(mask.shape)}")
+        m = mask.detach().to(device=target.device, dtype=torch.float32).contiguous()
+        k = self._pool_k(H)
+        if k > 1:
+            m = ops.area_pool(m, k)
+        if self._mask_state is None or self._mask_state.shape != (B, m.shape[2], m.shape[3]):
+            if self.captured:
+                raise ValueError(f"ProjectorStep.{who}: the captured iteration works on a different mask geometry")
+            self._mask_state = self.lpips.mask_state(m)
+            self._mask_cover = torch.empty(B, dtype=torch.float32, device=target.device)
+        else:
+            self._mask_state.set(m)
+        self._mask_cover.copy_(self._mask_state.cover())
+
+    def begin_image(self, target, numbers=None, mask=None):
         """Start the group of `target` [B,3,H,W]: w = w_avg in every row, the maps = the generator's buffers in every row, Adam's
         state cleared, the iteration count at 0 - all in place (a captured iteration stays valid).  The maps are initialised from
         the generator's buffers and not from fresh randn (the original's choice): the written id*-noise.pt then reproduces the
         image with id*-wp.pt, and the run starts from the image G shows for w_avg.  numbers: the image number of every row
-        (default group * B + b), which seeds its w noise."""
+        (default group * B + b), which seeds its w noise.  mask [B,1,H,W] f32 in [0,1] at the target's size (1 = fit the pixel,
+        0 = ignore it): the group is fitted under the mask-weighted LPIPS of LPIPS.value_and_grad(mask_state=...)."""
         B, dev = target.shape[0], target.device
+        self._set_mask(target, mask, "begin_image")
         w_avg, _ = self.w_stats()
         S = self.G.synthesis
         layers = [getattr(S, f"layer{i}") for i in range(S.num_layers - 1)]
@@ -177,14 +223,15 @@ class ProjectorStep(GraphReplay):
             w_noise = ops.randn_seeded(self._wn, self._seeds(), self._seeds_dev)
         ws = _WBroadcast.apply(self.w, w_noise, self._ns_dev if graph else ns_t, self.G.num_layers)
         imgs = self.G.synthesis(ws, randomize_noise=False, noises=self.noise_maps, noise_grad_out=self.noise_grads)["image"]
-        k = 1
-        while H // k > self.POOL_TO:
-            k *= 2
+        k = self._pool_k(H)
         with torch.no_grad():
             a, b = target.float().contiguous(), imgs.detach().float().contiguous()
             if k > 1:
                 a, b = ops.area_pool(a, k), ops.area_pool(b, k)
-            dist, gb = self.lpips.value_and_grad(a, b, per_sample=True)
+            if self._mask_state is None:
+                dist, gb = self.lpips.value_and_grad(a, b, per_sample=True)
+            else:
+                dist, gb = self.lpips.value_and_grad(a, b, per_sample=True, mask_state=self._mask_state)
             if B > 1:
                 ops.scale_(gb, B)          # value_and_grad returns d mean / d b; the loss is the sum over the rows
             g_img = gb if k == 1 else ops.area_pool_bwd(gb, k)
@@ -198,6 +245,8 @@ class ProjectorStep(GraphReplay):
         self.it += 1
         self.last = dict(w=self.w.detach(), ws=ws.detach(), imgs=imgs.detach(), dist=dist, reg=self._regv, w_grad=self.w.grad,
                          noise_grads=self.noise_grads, noises=[m.detach() for m in self.noise_maps], lr=lr_t, noise_scale=ns_t)
+        if self._mask_state is not None:
+            self.last["mask_cover"] = self._mask_cover
         return self.last
 
     # ------------------------------------------------------------------ hipGraph replay of the iteration
@@ -208,6 +257,7 @@ class ProjectorStep(GraphReplay):
             raise ValueError("ProjectorStep.capture: warmup must be at least 1: the first real iteration allocates Adam's state, which "
                              "a recorded iteration must find in place, and its results are what the loop reads before the first replay")
         dev = target.device
+        self._graph_masked = self._mask_state is not None
         self._g_target = target.detach().clone()
         self.opt.graph_begin(1, dev)
         self._ns_dev = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -233,9 +283,12 @@ class ProjectorStep(GraphReplay):
         self._seeds_dev.copy_(torch.tensor([s - (1 << 64) if s >= (1 << 63) else s for s in self._seeds()], dtype=torch.int64))
         self._inputs_fresh = True
 
-    def set_image(self, target):
-        """Copies a new group's images into the static input of the captured iteration (call begin_image() for the group too)."""
+    def set_image(self, target, mask=None):
+        """Copies a new group's images into the static input of the captured iteration (call begin_image() for the group too).
+        mask: the group's mask, refilled in place into the state the captured iteration reads; None keeps what begin_image() set."""
         self._set_static("_g_target", target)
+        if mask is not None:
+            self._set_mask(target, mask, "set_image")
 
     def replay(self):
         lr_t, ns_t = self.schedule(self.it)
@@ -255,28 +308,38 @@ class ProjectorStep(GraphReplay):
         return w, wp, maps, self.G.synthesis(wp, randomize_noise=False, noises=maps)["image"]
 
 
-def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=None, keep=None):
+def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=None, keep=None, mask=None):
     """`st.steps` iterations on the group `target` [B,3,H,W]; launch="graph" captures the iteration once (its warm-up iteration is a
     real one) and replays it, later groups go through set_image.  With `out_dir`: a Loss.txt line per kept row at every
     `save_every`-th iteration and at the end (one host read each), and the files of the module docstring for the first `keep` rows
-    (default: all), numbered by `numbers`.  Returns the last result dict with `w`, `wp`, `noises` and `rec` of ProjectorStep.result()."""
+    (default: all), numbered by `numbers`.  Returns the last result dict with `w`, `wp`, `noises` and `rec` of ProjectorStep.result().
+    mask [B,1,H,W] f32 in [0,1] at the target's size: the masked projection (ProjectorStep.begin_image); the Loss.txt lines then end
+    in `cover: ...`, and blend/{n:05d}.png (the target where the mask is 1, the reconstruction where it is 0:
+    quantize_u8(ops.mask_blend(mask, real, rec))) and mask/{n:05d}.png (8-bit L) are written next to real/ and rec/."""
     from .embedding import select_launch
     from .infer import quantize_u8, save_u8
     if launch not in ("graph", "eager"):
         raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
     B = target.shape[0]
     keep = B if keep is None else keep
-    st.begin_image(target, numbers=numbers)
+    if mask is None:
+        st.begin_image(target, numbers=numbers)
+    else:
+        if mask.dim() == 3:
+            mask = mask[:, None]
+        mask = mask.to(device=target.device, dtype=torch.float32).contiguous()
+        st.begin_image(target, numbers=numbers, mask=mask)
     nums = st.numbers
     run, done = select_launch(st, target, launch)
     r = st.last
 
     def log(i):
-        vals = torch.stack((r["dist"], r["reg"])).cpu()
+        vals = torch.stack((r["dist"], r["reg"]) + ((r["mask_cover"],) if mask is not None else ())).cpu()
         with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
             for b in range(keep):
-                print("id_%d_____i_%d  dist: %s  noise_reg: %s  lr: %s  noise_scale: %s" % (nums[b], i, float(vals[0, b]), float(vals[1, b]),
-                                                                                       r["lr"], r["noise_scale"]), file=f)
+                line = "id_%d_____i_%d  dist: %s  noise_reg: %s  lr: %s  noise_scale: %s" % (nums[b], i, float(vals[0, b]), float(vals[1, b]),
+                                                                                        r["lr"], r["noise_scale"])
+                print(line if mask is None else line + "  cover: %s" % float(vals[2, b]), file=f)
     for i in range(max(st.steps, done)):
         if i >= done:          # (with done == 1, iteration 0 ran as capture()'s warm-up)
             r = run()
@@ -284,18 +347,59 @@ def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=No
             log(i)
     w, wp, maps, rec = st.result()
     if out_dir is not None:
-        for sub in ("real", "rec", "models"):
+        for sub in ("real", "rec", "models") + (("blend", "mask") if mask is not None else ()):
             os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
         q_real, q_rec = quantize_u8(target.float()), quantize_u8(rec)
+        if mask is not None:
+            q_blend = quantize_u8(ops.mask_blend(mask, target.float().contiguous(), rec.float().contiguous()))
+            q_mask = mask_u8(mask)
         wc, wpc, mc = w.cpu(), wp.cpu(), [m.cpu() for m in maps]
         for b in range(keep):
             n = nums[b]
             save_u8(q_real[b], os.path.join(out_dir, "real", "%05d.png" % n))
             save_u8(q_rec[b], os.path.join(out_dir, "rec", "%05d.png" % n))
+            if mask is not None:
+                save_u8(q_blend[b], os.path.join(out_dir, "blend", "%05d.png" % n))
+                save_u8(q_mask[b], os.path.join(out_dir, "mask", "%05d.png" % n))
             torch.save(wc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-w.pt" % n))
             torch.save(wpc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-wp.pt" % n))
             torch.save([m[b:b + 1].clone() for m in mc], os.path.join(out_dir, "models", "id%d-noise.pt" % n))
     return dict(r, w=w, wp=wp, noises=maps, rec=rec)
+
+
+def mask_u8(mask):
+    """mask [B,1,H,W] in [0,1] -> [B,H,W] uint8 on the host, round(255 m): what mask/{n:05d}.png holds (a mask read from an 8-bit
+    file comes back with its bytes)."""
+    return (mask.detach().float().cpu()[:, 0] * 255.0).round().clamp(0, 255).to(torch.uint8)
+
+
+MASK_EXT = (".png", ".jpg", ".jpeg", ".bmp")
+
+
+def load_masks(path, size, n_images):
+    """--mask_dir: a folder (files in sorted-name order pair with the images of --img_dir in theirs; decoded as 8-bit L, resized
+    to size x size with PIL's bilinear filter, / 255: white = fit) or a .pt tensor [N,1,H,W] or [N,H,W] in [0,1] -> [N,1,size,size]
+    f32 on the host.  Exits when the count differs from the images'."""
+    if path.endswith(".pt"):
+        m = torch.load(path, map_location="cpu").float()
+        if m.dim() == 3:
+            m = m[:, None]
+        if m.dim() != 4 or m.shape[1] != 1:
+            raise SystemExit(f"projector: --mask_dir {path}: expected [N,1,H,W] or [N,H,W], got {tuple(m.shape)}")
+        if tuple(m.shape[2:]) != (size, size):
+            raise SystemExit(f"projector: --mask_dir {path}: the masks are {tuple(m.shape[2:])}, the images {(size, size)}")
+        if float(m.min()) < 0.0 or float(m.max()) > 1.0:
+            raise SystemExit(f"projector: --mask_dir {path}: values outside [0,1]")
+    else:
+        import numpy as np
+        from PIL import Image
+        names = sorted(n for n in os.listdir(path) if n.lower().endswith(MASK_EXT))
+        planes = [torch.from_numpy(np.asarray(Image.open(os.path.join(path, n)).convert("L").resize((size, size), Image.BILINEAR),
+                                              dtype=np.uint8).copy()).float().div(255.0) for n in names]
+        m = torch.stack(planes)[:, None] if planes else torch.zeros((0, 1, size, size))
+    if m.shape[0] != n_images:
+        raise SystemExit(f"projector: --mask_dir {path} holds {m.shape[0]} masks, --img_dir {n_images} images: one mask per image")
+    return m.contiguous()
 
 
 # ------------------------------------------------------------------ CLI
@@ -307,6 +411,8 @@ def make_parser():
     add_model_args(p)
     p.set_defaults(mtype=2)
     p.add_argument("--img_dir", default="./real_imgs/", help="a directory of images or a .pt tensor in [0,1]")
+    p.add_argument("--mask_dir", default=None, help="masks, one per image: a directory (sorted-name order, white = fit) or a .pt "
+                   "tensor [N,1,H,W] / [N,H,W] in [0,1]; the projection then fits the masked region only")
     p.add_argument("--experiment_dir", default="./projector_result")
     p.add_argument("--steps", type=int, default=1000)
     p.add_argument("--batch_size", type=int, default=1, help="images projected side by side, each as in its batch-1 run")
@@ -356,11 +462,13 @@ def main(argv=None):
     out = args.experiment_dir
     os.makedirs(out, exist_ok=True)
     imgs = _load_imgs(args.img_dir, args.img_size, dev)
+    masks = load_masks(args.mask_dir, args.img_size, imgs.shape[0]).to(dev) if args.mask_dir else None
     st = ProjectorStep(G, LP, steps=args.steps, lr=args.lr, initial_noise_factor=args.initial_noise_factor, noise_ramp=args.noise_ramp,
                        lr_rampdown=args.lr_rampdown, lr_rampup=args.lr_rampup, noise_reg=args.noise_reg, w_avg_samples=args.w_avg_samples,
                        seed=args.seed)
     for first, keep, idx, _ in rows_plan(imgs.shape[0], args.batch_size):
-        r = project(st, imgs[idx].contiguous(), out, args.save_every, args.launch, numbers=idx, keep=keep)
+        r = project(st, imgs[idx].contiguous(), out, args.save_every, args.launch, numbers=idx, keep=keep,
+                    mask=None if masks is None else masks[idx].contiguous())
         vals = torch.stack((r["dist"], r["reg"])).cpu()
         for b in range(keep):
             print("image %d: dist %.5f  noise_reg %.3e" % (first + b, float(vals[0, b]), float(vals[1, b])))

@@ -868,6 +868,44 @@ int dge_rows_mean_std(const float* x, long long N, int D, float* mean, float* st
  * divided by k*k (a correctly rounded division).  g is written, not accumulated.  dge_last_kernel: "area_pool_bwd". */
 int dge_area_pool_bwd(const float* g_pooled, float* g, int BC, int H, int W, int k, dge_stream_t stream);
 
+/* ---- Masked LPIPS (dge_amd.lpips.LPIPS.value_and_grad(mask=...), the projector's --mask_dir) ---------------------------------- */
+/* m [B,H,W] f32 in [0,1] at the LPIPS resolution (1 = fit the pixel, 0 = ignore it).  Levels m_0 = m, m_k = avg_pool2d(m_{k-1}, 2)
+ * for k = 1..4 with floor sizes (an odd trailing row or column is dropped, as the VGG max pooling drops it, so level k has tap k's
+ * grid), and  dist_b = sum_k ( sum_p m_k[b,p] d_k[b,p] ) / ( sum_p m_k[b,p] )  with d_k what dge_lpips_head forms; a level whose sum
+ * is 0 contributes 0 and no gradient.  All of these: no atomics, nothing pre-zeroed, partial sums in slots of a caller-provided
+ * workspace added in a fixed order: the same bits run to run and in both reduction modes, and row b of a batch call has the bits of
+ * the call on row b alone.
+ * dge_mask_pyramid: levels = the five levels back to back, level k as [B, H>>k, W>>k] from float  B * sum_{j<k} (H>>j)*(W>>j)  on
+ * (level 0 is a copy of m: `levels` must not be m); inv_sum [B,5] = 1 / sum_p m_k[b,p], or 0 where the sum is 0; sums (optional)
+ * [B,5] the sums themselves.  One workgroup per 32 x 32 tile of m through LDS, each level pooled from the one below as
+ * ((a + b) + (c + d)) * 0.25.  work: dge_mask_pyramid_work_bytes(B, H, W) bytes (-1: sizes it refuses).  No host synchronisation.
+ * dge_last_kernel: "mask_pyramid". */
+int dge_mask_pyramid_work_bytes(int B, int H, int W);
+int dge_mask_pyramid(const float* m, float* levels, float* inv_sum, float* sums, int B, int H, int W, void* work, long long work_bytes,
+                     dge_stream_t stream);
+/* dge_lpips_prep / dge_lpips_prep_bwd with a per-pixel factor mask [B,HW]: x = (mask * img - shift) / scale (the product rounded
+ * first: a hole reads as mid-grey), and gimg (+)= (factor * gx * inv_scale) * mask (rounded before the add).  The same kernel body as
+ * the plain entry points, which keep their launches and bits.  dge_last_kernel: "lpips_prep_masked" / "lpips_prep_bwd_masked". */
+int dge_lpips_prep_masked(const float* img, const float* mask, void* x, int B, int HW, int cpad, const float* host_shift3,
+                          const float* host_scale3, int dtype, dge_stream_t stream);
+int dge_lpips_prep_bwd_masked(const void* gx, const float* mask, float* gimg, int B, int HW, int cpad, const float* host_scale3,
+                              float factor, int accumulate, int dtype, dge_stream_t stream);
+/* The weighted head of tap `tap` (0..4): feat [2B,h,w,C], lin [C], mk [B,HW] = level `tap` of the pyramid, inv_sum [B,5].  Every
+ * workgroup stores  sum_p m_k[b,p] d_k[b,p]  over its pixels to slots[b][workgroup] (dge_lpips_head_w_slots(HW, C, dtype) slots per
+ * row; -1 for a C it refuses); g1 (optional, [B,h,w,C]) = gscale * m_k[b,p] * inv_sum[b,tap] * d d_k[b,p] / d feat[B+b], exactly 0
+ * where that factor is 0.  dge_lpips_head's lane layout, C in {64,128,256,512} in both dtypes.  dge_last_kernel: "lpips_head_w".
+ * dge_lpips_head_w_finalize: one launch for the five taps; host_off5[k] = the float offset of tap k's [B][host_nslots5[k]] block in
+ * `slots`.  dist[b] = sum_k inv_sum[b,k] * (tap k's slots of row b in a fixed order), taps in tap order; written, not accumulated.
+ * dge_last_kernel: "lpips_head_w_finalize". */
+int dge_lpips_head_w_slots(int HW, int C, int dtype);
+int dge_lpips_head_w(const void* feat, const float* lin, const float* mk, const float* inv_sum, int tap, float* slots, void* g1, int B,
+                     int HW, int C, float gscale, int dtype, dge_stream_t stream);
+int dge_lpips_head_w_finalize(const float* slots, const long long* host_off5, const int* host_nslots5, const float* inv_sum, float* dist,
+                              int B, dge_stream_t stream);
+/* out [B,3,HW] = m * a + (1 - m) * b with m [B,HW] (all f32): the two products and the sum are rounded one by one, the bits of
+ * torch's expression.  dge_last_kernel: "mask_blend". */
+int dge_mask_blend(const float* m, const float* a, const float* b, float* out, int B, int HW, dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,11 @@ seeded stand-in LPIPS, one process.  Configurations alternate round by round; me
   * the optimiser alone: dge_adam_multi over the parameter sets of batch 1 and batch 8 ([w, all noise maps]) against
     torch.optim.Adam on the same tensors (device events around 10 x --iters steps, eager launches: a step of tens of
     microseconds needs the longer window).
-    python tools/bench_projector.py [--img-size 1024] [--dtype bf16] [--batches 1,8] [--iters 20] [--rounds 5]"""
+    python tools/bench_projector.py [--img-size 1024] [--dtype bf16] [--batches 1,8] [--iters 20] [--rounds 5]
+  * --mask: only the masked against the unmasked iteration (README, "Masked projection"): hipGraph replay at every batch of
+    --batches, a soft-edged half-plane mask, the two alternating round by round in one process; the difference of the medians
+    is what the mask costs per iteration (one more f32 plane read in each prep, one m_k read per head, six head launches for
+    five)."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -21,6 +25,7 @@ ap.add_argument("--img-size", type=int, default=1024); ap.add_argument("--dtype"
 ap.add_argument("--fmaps-base", type=int, default=None); ap.add_argument("--fmaps-max", type=int, default=None)
 ap.add_argument("--batches", default="1,8"); ap.add_argument("--iters", type=int, default=20); ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--w-avg-samples", type=int, default=10000)
+ap.add_argument("--mask", action="store_true", help="time the masked against the unmasked replay and nothing else")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "bench_projector needs the GPU"
 res = {}
@@ -66,6 +71,33 @@ LP = LPIPS(compute_dtype=a.dtype).cuda()
 batches = [int(v) for v in a.batches.split(",")]
 with torch.no_grad():
     imgs = G.synthesis(torch.randn(max(batches), G.num_layers, 512, device="cuda"))["image"].detach().float().clamp(-1, 1).contiguous()
+
+# ---- --mask: the masked against the unmasked replay
+if a.mask:
+    runs, per = {}, {}
+    R = a.img_size
+    ramp = ((R * 0.625 - torch.arange(R, dtype=torch.float32, device="cuda")) / (R / 4)).clamp(0, 1)
+    for B in batches:
+        x = imgs[:B].contiguous()
+        m = ramp.view(1, 1, 1, R).expand(B, 1, R, R).contiguous()
+        for name, mask in (("plain", None), ("masked", m)):
+            st = ProjectorStep(G, LP, w_avg_samples=a.w_avg_samples)
+            st.begin_image(x, mask=mask)
+            st.capture(x, warmup=1)
+            for _ in range(3):
+                st.replay()
+            runs[f"B{B}_{name}"], per[f"B{B}_{name}"] = st.replay, B
+    ms = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for name, run in runs.items():
+            ms[name].append(timed(run, a.iters))
+    report(f"projector replay with and without a mask, StyleGAN2-{a.img_size}, {a.dtype}", ms, per)
+    for B in batches:
+        d = res[f"B{B}_masked"]["ms"] - res[f"B{B}_plain"]["ms"]
+        res[f"B{B}_mask_cost_ms"] = round(d, 4)
+        print(f"B{B}: the mask costs {d:+.3f} ms per iteration ({100 * d / res[f'B{B}_plain']['ms']:+.2f} %)", flush=True)
+    print(json.dumps(res))
+    sys.exit(0)
 
 # ---- the iteration
 runs, per = {}, {}
