@@ -2,8 +2,9 @@
 embedding_v2_biggan.BigEmbedStep with its rows form): the constructor tail, the start of an image group, the optimiser phase, the
 tracker read-out and the hipGraph plumbing.  step() itself - the loss composition and the result keys - is each family's own.
 
-A subclass provides `_latent_shape(B)`, `_start_code(imgs1, shape, noises, needed)` and, where a group needs more than its images
-(BigGAN's class conditions), `_begin_group(imgs1, **group_kw)`."""
+A subclass provides `_latent_shape(B)`, `_start_code(imgs1, shape, noises, needed)`, where a group needs more than its images
+(BigGAN's class conditions) `_begin_group(imgs1, **group_kw)`, and where it steps a second optimiser (the noise maps') its own
+`_graph_opts()`."""
 import os
 
 import torch
@@ -92,24 +93,18 @@ class TwoPhaseEmbedStep(GraphReplay):
         through graph_advance, the noise seed is a device scalar; with a leaf w1 the graph updates it in place.  begin_image() must
         have run for the group."""
         self._g_imgs1 = imgs1.detach().clone()
-        self.opt.graph_begin(2, imgs1.device)          # two optimizer calls per iteration
+        for opt, calls in self._graph_opts():
+            opt.graph_begin(calls, imgs1.device)
         ops.noise_graph_begin(imgs1.device)
         self.graph_iteration = 0
-        warm = {}
+        return self._capture_keeping_last(lambda: self.step(self._g_imgs1, noises), warmup)
 
-        def keep_last():    # results of the last executed iteration (the captured one is only recorded)
-            self._after_warmup()
-            if warmup:
-                warm.update({k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.last.items()})
-        out = self._capture(lambda: self.step(self._g_imgs1, noises), warmup, after_warmup=keep_last)
-        self.last = warm
-        return out
-
-    def _after_warmup(self):
-        """Behind the last real iteration of capture(), before the recorded one: host-side counters a subclass rolls back itself."""
+    def _graph_opts(self):
+        return [(self.opt, 2)]          # two optimizer calls per iteration
 
     def _graph_inputs(self, iteration):
-        self.opt.graph_advance()
+        for opt, _ in self._graph_opts():
+            opt.graph_advance()
         ops.noise_graph_seed(iteration)
 
     def set_image(self, imgs1):

@@ -97,15 +97,31 @@ def select_launch(st, imgs1, launch):
     return st.replay, 1
 
 
+def iterate(st, imgs1, iterations, launch):
+    """The iteration loop of every inversion (invert, embedding_v2.invert_group, projector.project): a generator of (i, result dict
+    of iteration i).  `launch` is validated HERE, in the call; select_launch runs when the generator is first advanced, behind the
+    group's begin_image (a caller that validates in front of its begin_image makes the call there and loops afterwards)."""
+    if launch not in ("graph", "eager"):
+        raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
+
+    def loop():
+        run, done = select_launch(st, imgs1, launch)
+        r = st.last
+        for i in range(max(iterations, done)):
+            if i >= done:          # (with done == 1, iteration 0 ran as capture()'s warm-up)
+                r = run()
+            yield i, r
+    return loop()
+
+
 def invert(st, imgs1, iterations=1500, launch="graph"):
     """The inversion loop on one image group (embedding_img.py:74-170: `iterations` two-phase iterations from the encoder
     checkpoint).  launch="graph" (default: the loop runs at batch 1, where the eager iteration is bound by the host's launch rate -
     15-17 ms against 13 ms of GPU work at 1024^2) captures the iteration once and replays it; "eager" runs EmbedStep.step."""
     st.begin_image()
-    run, done = select_launch(st, imgs1, launch)
     r = st.last
-    for _ in range(max(0, iterations - done)):
-        r = run()
+    for _, r in iterate(st, imgs1, iterations, launch):
+        pass
     return r
 
 

@@ -80,8 +80,9 @@ embedding_v2_pggan is for PGGAN.  Per iteration:
 Noise optimisation (`optimize_noise`, --optimize_noise true; StyleGAN2, mode "W", one process): the per-layer noise maps of the
 synthesis network become free variables beside the W+ code, as in StyleGAN2's own projector.
   * the maps start at the generator's `layer{i}.noise` buffers - one shared set [1,res,res] per layer, or a copy per row
-    [B,res,res] with `independent` - and live in one flat f32 buffer (ops.NoiseTable) with one LREQAdam of its own (lr `noise_lr`
-    or lr, its own step count); begin_image resets the maps and that Adam state in place.
+    [B,res,res] with `independent` - and live in one flat f32 buffer (noise_maps.NoiseMaps, the step's `noise`; shared with the
+    projector) with one LREQAdam of its own (`nopt`: lr `noise_lr` or lr, its own step count); begin_image resets the maps and
+    that Adam state in place.
   * phase 1 back-propagates loss_msiv + noise_reg * sum reg(map) (the projector's regulariser, dge_noise_reg): the synthesis
     backward writes each map's image-loss gradient (dge_s2_noise_grad) into the flat gradient buffer and the regulariser's
     gradient is added to it.  loss_msiv, the tracker and every logged loss stay the image loss alone; reg is logged as `noise_reg`
@@ -110,8 +111,9 @@ from . import losses, ops
 from .custom_adam import LREQAdam
 from .embed_step import TwoPhaseEmbedStep, several_processes
 from .embed_track import EVENT_LOSS, EVENT_NORM, tracker_rules, write_tracker_files  # noqa: F401 (re-exported)
-from .embedding import select_launch
+from .embedding import iterate
 from .models import add_model_args, blur_encoder, load_lpips_weights
+from .noise_maps import NoiseMaps, save_noise_rows
 
 # per-generator defaults (embedding_v2_styleGAN1.py:195-209 + :118,128-131; embedding_v2_styleGAN2.py:214-232 + :136,153-166)
 DEFAULTS = {
@@ -177,7 +179,7 @@ def _generate_sg2(st, w, noises, truncate):
     # (the synthesis backward reads its saved activations only, never wp: w itself may be the input when psi == 1)
     wt = w if st.psi == 1.0 or not truncate else _WplusLerp.apply(w, st.G.truncation.w_avg, st.psi)
     if st.optimize_noise:
-        return st.G.synthesis(wt, randomize_noise=False, noises=st.noise_maps, noise_grad_out=st.noise_grads)["image"]
+        return st.G.synthesis(wt, randomize_noise=False, noises=st.noise.maps, noise_grad_out=st.noise.grads)["image"]
     return st.G.synthesis(wt, randomize_noise=False)["image"]
 
 
@@ -236,7 +238,7 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
         self.psi = None if d["truncation"] is None else (d["truncation"] if truncation is None else float(truncation))
         self._const2 = None
         self.optimize_noise, self.noise_reg, self.noise_lr = bool(optimize_noise), float(noise_reg), noise_lr
-        self.noise_table = self.noise_flat = self.noise_maps = self.noise_grads = self.nopt = None
+        self.noise = self.nopt = None          # the NoiseMaps owner and its LREQAdam: from the first group with optimize_noise
         if mode == "Z" and self.kind.own_mapping:
             # the scripts' coefficients (embedding_v2_styleGAN1.py: 0.7 on the first half of the rows); without a centre Mapping
             # takes the plain broadcast whatever they are
@@ -276,62 +278,31 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
 
     # ------------------------------------------------------------------ the noise maps (optimize_noise)
     def begin_image(self, imgs1, w_init=None, noises=None, **group_kw):
+        """With optimize_noise, the maps of the new group too: the generator's buffers, copied per row in independent mode, into the
+        NoiseMaps owner (allocated once per shape and device, with the LREQAdam over its flat leaf); that Adam state is cleared in place."""
         super().begin_image(imgs1, w_init=w_init, noises=noises, **group_kw)
-        if self.optimize_noise:
-            self._noise_begin(imgs1.shape[0], imgs1.device)
-
-    def _noise_begin(self, B, dev):
-        """The maps of a new group: the generator's buffers, copied per row in independent mode, into the flat leaf (allocated once
-        per shape and device with its table, gradient buffer and LREQAdam); the Adam state is cleared in place."""
-        S, Bn = self.G.synthesis, B if self.independent else 1
-        layers = [getattr(S, f"layer{i}") for i in range(S.num_layers - 1)]
-        tab = self.noise_table
-        if tab is None or tab.Bn != Bn or tab.device != self.w1.device:
+        if not self.optimize_noise:
+            return
+        Bn = imgs1.shape[0] if self.independent else 1
+        if self.noise is None or not self.noise.fits(Bn, self.w1.device):
             if self.captured:
                 raise ValueError("LatentEmbedStep.begin_image: the captured iteration works on other noise maps")
-            tab = self.noise_table = ops.NoiseTable([L.res for L in layers], Bn, dev)
-            self.noise_flat = torch.zeros(tab.numel, dtype=torch.float32, device=dev, requires_grad=True)
-            self._noise_gflat = torch.zeros(tab.numel, dtype=torch.float32, device=dev)
-            self._noise_regv = torch.zeros(Bn, dtype=torch.float32, device=dev)
-            # the maps the generator sees: leaves of their own on the flat storage (their gradients go to the views of _noise_gflat)
-            self.noise_maps = [tab.view(self.noise_flat.detach(), m).requires_grad_(True) for m in range(len(layers))]
-            self.noise_grads = [tab.view(self._noise_gflat, m) for m in range(len(layers))]
-            self.nopt = LREQAdam([{"params": [self.noise_flat]}], lr=self.lr if self.noise_lr is None else self.noise_lr,
+            self.noise = NoiseMaps(self.G.synthesis, Bn, imgs1.device)
+            self.nopt = LREQAdam([{"params": [self.noise.flat]}], lr=self.lr if self.noise_lr is None else self.noise_lr,
                                  betas=(self.beta_1, 0.99), weight_decay=0)
-        with torch.no_grad():
-            for m, L in zip(self.noise_maps, layers):
-                m.copy_(L.noise.reshape(1, L.res, L.res).expand_as(m))
+        self.noise.reset()
         self.nopt.graph_reset()
 
     def _noise_step(self):
         """One LREQAdam step of the maps from the phase-1 gradient, then the renormalisation."""
-        self.noise_flat.grad = self._noise_gflat
+        self.noise.hand_grad()
         self.nopt.step()
-        self.noise_flat.grad = None
-        ops.noise_normalize(self.noise_table, self.noise_flat.detach())
+        self.noise.flat.grad = None
+        self.noise.normalize()
 
-    def capture(self, imgs1, noises=(None, None, None), warmup=TwoPhaseEmbedStep.WARMUP):
-        if not self.optimize_noise:
-            return super().capture(imgs1, noises, warmup)
-        self.nopt.graph_begin(1, imgs1.device)          # one call per iteration, with its own step count
-        out = super().capture(imgs1, noises, warmup)
-        self.nopt.graph_restore(self._noise_snap)       # (the recorded iteration advanced the host counters, not the device)
-        return out
-
-    def _after_warmup(self):
-        if self.optimize_noise:
-            self._noise_snap = self.nopt.graph_snapshot()
-
-    def _graph_inputs(self, iteration):
-        super()._graph_inputs(iteration)
-        if self.optimize_noise:
-            self.nopt.graph_advance()
-
-    def replay(self):
-        r = super().replay()
-        if self.optimize_noise:
-            self.nopt.graph_count_replay()
-        return r
+    def _graph_opts(self):
+        """Two calls of `opt` per iteration; the maps' optimiser makes one, with its own step count."""
+        return [(self.opt, 2)] + ([(self.nopt, 1)] if self.optimize_noise else [])
 
     # ------------------------------------------------------------------ one iteration
     def _generate(self, w1, noises):
@@ -369,8 +340,7 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
         loss_msiv, info_img = image_loss(imgs1, imgs2, self.lpips, weights=IMG_WEIGHTS, grad_windows=(True, True, True))
         self._opt_phase(loss_msiv, retain_graph=True)
         if self.optimize_noise:          # phase 1's loss is loss_msiv + noise_reg * sum reg: the regulariser's gradient joins the image loss's
-            ops.noise_reg(self.noise_table, self.noise_flat.detach(), grad=self._noise_gflat, scale=self.noise_reg, accumulate=True,
-                          out=self._noise_regv)
+            self.noise.add_reg(self.noise_reg)
         if not kind.encode_first:
             const3, w2 = kind.encode(self, imgs2, noises[2])
         wp_new = self._wp_of(w1) if zmode else None          # the direct term of phase 2 sees the updated code
@@ -408,7 +378,7 @@ class LatentEmbedStep(TwoPhaseEmbedStep):
         if zmode:
             self.last.update(wp=wp.detach(), wp_new=wp_new.detach())
         if self.optimize_noise:          # the maps behind this iteration's step, its phase-1 gradients (valid until the next backward), reg
-            self.last.update(noises=[m.detach() for m in self.noise_maps], noise_grads=self.noise_grads, noise_reg=self._noise_regv)
+            self.last.update(noises=self.noise.detached(), noise_grads=self.noise.grads, noise_reg=self.noise.reg)
         return self.last
 
 
@@ -508,9 +478,8 @@ def finish_group(st, r, B, out_dir, group, keep=None):
         else:
             write_tracker_files(tr, group, models, out_dir)
         if getattr(st, "optimize_noise", False):          # the maps of every image, as synthesis(noises=...) takes them
-            maps = [m.cpu() for m in r["noises"]]
-            for num, b in ([(group * B + b, b) for b in range(B if keep is None else keep)] if st.independent else [(group, 0)]):
-                torch.save([m[b:b + 1].clone() for m in maps], os.path.join(models, "id%d-noise.pt" % num))
+            rows = range(B if keep is None else keep) if st.independent else [0]          # (coupled form: the one shared set)
+            save_noise_rows([m.cpu() for m in r["noises"]], rows, [group * B + b for b in rows] if st.independent else [group], models)
     return dict(r, tracker=tr)
 
 
@@ -546,13 +515,8 @@ def invert_group(st, imgs1, iterations, launch, save_every, out_dir, group, keep
     `iterations` iterations through `launch`, a dump_group(..., **dump_kw) at every `save_every`-th with `out_dir`, finish_group.
     `infos(r)`: the result dict with the info vectors under the keys loss_txt_block prints."""
     st.begin_image(imgs1, **begin_kw)
-    if launch not in ("graph", "eager"):
-        raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
-    run, done = select_launch(st, imgs1, launch)
     r = st.last
-    for i in range(max(iterations, done)):
-        if i >= done:                                # (with done == 1, iteration 0 ran as capture()'s warm-up)
-            r = run()
+    for i, r in iterate(st, imgs1, iterations, launch):
         if out_dir is not None and save_every and i % save_every == 0:
             dump_group(st, imgs1, r if infos is None else infos(r), i, out_dir, group, keep, **dump_kw)
     return finish_group(st, r, imgs1.shape[0], out_dir, group, keep)
@@ -721,11 +685,14 @@ def parse_args(argv=None):
     return args
 
 
+IMAGE_EXT = (".png", ".jpg", ".jpeg", ".bmp")
+
+
 def _load_imgs(path, size, device):
     if path.endswith(".pt"):
         return (torch.load(path, map_location="cpu").float() * 2 - 1).to(device)
     from .infer import load_images
-    names = sorted(n for n in os.listdir(path) if n.lower().endswith((".png", ".jpg", ".jpeg", ".bmp")))
+    names = sorted(n for n in os.listdir(path) if n.lower().endswith(IMAGE_EXT))
     return load_images([os.path.join(path, n) for n in names], size, bicubic=True, device=device)
 
 

@@ -52,6 +52,7 @@ from . import ops
 from .custom_adam import Adam
 from .embed_step import several_processes
 from .graph_step import GraphReplay
+from .noise_maps import NoiseMaps, save_noise_rows
 
 
 def projector_schedule(step, steps, lr=0.1, w_std=1.0, initial_noise_factor=0.05, noise_ramp=0.75, lr_rampdown=0.25, lr_rampup=0.05):
@@ -102,13 +103,12 @@ class ProjectorStep(GraphReplay):
         if steps < 1 or w_avg_samples < 1:
             raise ValueError("ProjectorStep: steps and w_avg_samples must be positive")
         self.G, self.lpips = G, lpips_model
-        self.E = torch.nn.Module()          # no encoder: GraphReplay primes the pack tables of `E`, and an empty module has none
         for p in G.parameters():
             p.requires_grad_(False)
         self.steps, self.lr, self.noise_reg, self.w_avg_samples, self.seed = int(steps), float(lr), float(noise_reg), int(w_avg_samples), int(seed)
         self._sched = dict(initial_noise_factor=initial_noise_factor, noise_ramp=noise_ramp, lr_rampdown=lr_rampdown, lr_rampup=lr_rampup)
         self.w_avg = self.w_std = None
-        self.w = self.opt = self.noise_table = self.noise_flat = self.noise_maps = self.noise_grads = None
+        self.w = self.opt = self.noise = None          # (noise: the NoiseMaps owner, from the first group)
         self._ns_dev = self._seeds_dev = None
         self._mask_state = self._mask_cover = self._graph_masked = None
         self._inputs_fresh = False          # graph mode: _graph_inputs has uploaded the inputs of the iteration step() is about to issue
@@ -176,30 +176,21 @@ class ProjectorStep(GraphReplay):
         B, dev = target.shape[0], target.device
         self._set_mask(target, mask, "begin_image")
         w_avg, _ = self.w_stats()
-        S = self.G.synthesis
-        layers = [getattr(S, f"layer{i}") for i in range(S.num_layers - 1)]
-        if self.w is None or self.w.shape[0] != B or self.w.device != dev:
+        if self.noise is None or not self.noise.fits(B, dev):          # (w is allocated with the maps: one row each per image)
             if self.captured:
                 raise ValueError("ProjectorStep.begin_image: the captured iteration works on a different batch")
             D = self.G.w_space_dim
             self.w = torch.zeros((B, D), dtype=torch.float32, device=dev, requires_grad=True)
             self._wn = torch.empty((B, D), dtype=torch.float32, device=dev)
-            tab = self.noise_table = ops.NoiseTable([L.res for L in layers], B, dev)
-            self.noise_flat = torch.zeros(tab.numel, dtype=torch.float32, device=dev, requires_grad=True)
-            self._noise_gflat = torch.zeros(tab.numel, dtype=torch.float32, device=dev)
-            self._regv = torch.zeros(B, dtype=torch.float32, device=dev)
-            # the maps the generator sees: leaves of their own on the flat storage (their gradients go to the views of _noise_gflat)
-            self.noise_maps = [tab.view(self.noise_flat.detach(), m).requires_grad_(True) for m in range(len(layers))]
-            self.noise_grads = [tab.view(self._noise_gflat, m) for m in range(len(layers))]
-            self.opt = Adam([self.w, self.noise_flat], lr=self.lr, betas=(0.9, 0.999), eps=1e-8)
+            self.noise = NoiseMaps(self.G.synthesis, B, dev)
+            self.opt = Adam([self.w, self.noise.flat], lr=self.lr, betas=(0.9, 0.999), eps=1e-8)
         self.group += 1
         self.numbers = [self.group * B + b for b in range(B)] if numbers is None else [int(n) for n in numbers]
         if len(self.numbers) != B:
             raise ValueError("ProjectorStep.begin_image: one image number per row")
         with torch.no_grad():
             self.w.copy_(w_avg.reshape(1, -1).expand_as(self.w))
-            for m, L in zip(self.noise_maps, layers):
-                m.copy_(L.noise.reshape(1, L.res, L.res).expand_as(m))
+        self.noise.reset()
         self.opt.graph_reset()
         self.it = 0
 
@@ -222,7 +213,7 @@ class ProjectorStep(GraphReplay):
         if w_noise is None:
             w_noise = ops.randn_seeded(self._wn, self._seeds(), self._seeds_dev)
         ws = _WBroadcast.apply(self.w, w_noise, self._ns_dev if graph else ns_t, self.G.num_layers)
-        imgs = self.G.synthesis(ws, randomize_noise=False, noises=self.noise_maps, noise_grad_out=self.noise_grads)["image"]
+        imgs = self.G.synthesis(ws, randomize_noise=False, noises=self.noise.maps, noise_grad_out=self.noise.grads)["image"]
         k = self._pool_k(H)
         with torch.no_grad():
             a, b = target.float().contiguous(), imgs.detach().float().contiguous()
@@ -237,14 +228,13 @@ class ProjectorStep(GraphReplay):
             g_img = gb if k == 1 else ops.area_pool_bwd(gb, k)
         self.w.grad = None
         imgs.backward(g_img)
-        flat = self.noise_flat.detach()
-        ops.noise_reg(self.noise_table, flat, grad=self._noise_gflat, scale=self.noise_reg, accumulate=True, out=self._regv)
-        self.noise_flat.grad = self._noise_gflat
+        reg = self.noise.add_reg(self.noise_reg)
+        self.noise.hand_grad()
         self.opt.step(lr=lr_t)
-        ops.noise_normalize(self.noise_table, flat)
+        self.noise.normalize()
         self.it += 1
-        self.last = dict(w=self.w.detach(), ws=ws.detach(), imgs=imgs.detach(), dist=dist, reg=self._regv, w_grad=self.w.grad,
-                         noise_grads=self.noise_grads, noises=[m.detach() for m in self.noise_maps], lr=lr_t, noise_scale=ns_t)
+        self.last = dict(w=self.w.detach(), ws=ws.detach(), imgs=imgs.detach(), dist=dist, reg=reg, w_grad=self.w.grad,
+                         noise_grads=self.noise.grads, noises=self.noise.detached(), lr=lr_t, noise_scale=ns_t)
         if self._mask_state is not None:
             self.last["mask_cover"] = self._mask_cover
         return self.last
@@ -259,19 +249,20 @@ class ProjectorStep(GraphReplay):
         dev = target.device
         self._graph_masked = self._mask_state is not None
         self._g_target = target.detach().clone()
-        self.opt.graph_begin(1, dev)
+        for opt, calls in self._graph_opts():
+            opt.graph_begin(calls, dev)
         self._ns_dev = torch.zeros(1, dtype=torch.float32, device=dev)
         self._seeds_dev = torch.zeros(target.shape[0], dtype=torch.int64, device=dev)
         self.graph_iteration = 0
-        warm = {}
 
-        def keep_last():          # the count and the results of the last executed iteration (the captured one is only recorded)
+        def keep_it():          # the count of the last executed iteration (the captured one is only recorded)
             self._it_snap = self.it
-            warm.update({k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.last.items()})
-        out = self._capture(lambda: self.step(self._g_target), warmup, after_warmup=keep_last)
+        out = self._capture_keeping_last(lambda: self.step(self._g_target), warmup, after_warmup=keep_it)
         self.it = self._it_snap
-        self.last = warm
         return out
+
+    def _graph_opts(self):
+        return [(self.opt, 1)]          # one Adam over [w, maps], one call per iteration
 
     def _graph_inputs(self, iteration):
         """What the host decides for iteration `self.it` of the group (GraphReplay's own count runs across groups), uploaded from
@@ -304,7 +295,7 @@ class ProjectorStep(GraphReplay):
         """(w [B,512], wp [B,L,512] = w in every row, maps, image): the projection as it stands, synthesised without w noise."""
         w = self.w.detach()
         wp = ops.w_broadcast(w, self.G.num_layers)
-        maps = [m.detach() for m in self.noise_maps]
+        maps = self.noise.detached()
         return w, wp, maps, self.G.synthesis(wp, randomize_noise=False, noises=maps)["image"]
 
 
@@ -316,10 +307,9 @@ def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=No
     mask [B,1,H,W] f32 in [0,1] at the target's size: the masked projection (ProjectorStep.begin_image); the Loss.txt lines then end
     in `cover: ...`, and blend/{n:05d}.png (the target where the mask is 1, the reconstruction where it is 0:
     quantize_u8(ops.mask_blend(mask, real, rec))) and mask/{n:05d}.png (8-bit L) are written next to real/ and rec/."""
-    from .embedding import select_launch
+    from .embedding import iterate
     from .infer import quantize_u8, save_u8
-    if launch not in ("graph", "eager"):
-        raise ValueError(f"launch must be 'graph' or 'eager', got {launch!r}")
+    iterations = iterate(st, target, st.steps, launch)          # (validates `launch` here; starts behind begin_image, in the loop)
     B = target.shape[0]
     keep = B if keep is None else keep
     if mask is None:
@@ -330,21 +320,17 @@ def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=No
         mask = mask.to(device=target.device, dtype=torch.float32).contiguous()
         st.begin_image(target, numbers=numbers, mask=mask)
     nums = st.numbers
-    run, done = select_launch(st, target, launch)
-    r = st.last
 
-    def log(i):
+    def log(i, r):
         vals = torch.stack((r["dist"], r["reg"]) + ((r["mask_cover"],) if mask is not None else ())).cpu()
         with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
             for b in range(keep):
                 line = "id_%d_____i_%d  dist: %s  noise_reg: %s  lr: %s  noise_scale: %s" % (nums[b], i, float(vals[0, b]), float(vals[1, b]),
                                                                                         r["lr"], r["noise_scale"])
                 print(line if mask is None else line + "  cover: %s" % float(vals[2, b]), file=f)
-    for i in range(max(st.steps, done)):
-        if i >= done:          # (with done == 1, iteration 0 ran as capture()'s warm-up)
-            r = run()
+    for i, r in iterations:          # (st.steps >= 1: the loop runs and leaves the last result in r)
         if out_dir is not None and save_every and (i % save_every == 0 or i == st.steps - 1):
-            log(i)
+            log(i, r)
     w, wp, maps, rec = st.result()
     if out_dir is not None:
         for sub in ("real", "rec", "models") + (("blend", "mask") if mask is not None else ()):
@@ -363,7 +349,7 @@ def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=No
                 save_u8(q_mask[b], os.path.join(out_dir, "mask", "%05d.png" % n))
             torch.save(wc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-w.pt" % n))
             torch.save(wpc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-wp.pt" % n))
-            torch.save([m[b:b + 1].clone() for m in mc], os.path.join(out_dir, "models", "id%d-noise.pt" % n))
+        save_noise_rows(mc, range(keep), nums[:keep], os.path.join(out_dir, "models"))
     return dict(r, w=w, wp=wp, noises=maps, rec=rec)
 
 
@@ -371,9 +357,6 @@ def mask_u8(mask):
     """mask [B,1,H,W] in [0,1] -> [B,H,W] uint8 on the host, round(255 m): what mask/{n:05d}.png holds (a mask read from an 8-bit
     file comes back with its bytes)."""
     return (mask.detach().float().cpu()[:, 0] * 255.0).round().clamp(0, 255).to(torch.uint8)
-
-
-MASK_EXT = (".png", ".jpg", ".jpeg", ".bmp")
 
 
 def load_masks(path, size, n_images):
@@ -393,7 +376,8 @@ def load_masks(path, size, n_images):
     else:
         import numpy as np
         from PIL import Image
-        names = sorted(n for n in os.listdir(path) if n.lower().endswith(MASK_EXT))
+        from .embedding_v2 import IMAGE_EXT
+        names = sorted(n for n in os.listdir(path) if n.lower().endswith(IMAGE_EXT))
         planes = [torch.from_numpy(np.asarray(Image.open(os.path.join(path, n)).convert("L").resize((size, size), Image.BILINEAR),
                                               dtype=np.uint8).copy()).float().div(255.0) for n in names]
         m = torch.stack(planes)[:, None] if planes else torch.zeros((0, 1, size, size))

@@ -59,7 +59,7 @@ def test_noise_loop_matches_reference_run(mode):
     st = make_step(optimize_noise=True)
     imgs1 = torch.as_tensor(g["imgs1"]).cuda()
     st.begin_image(imgs1, w_init=torch.as_tensor(g["w0"]))
-    assert all(tuple(m.shape) == (1, r, r) for m, r in zip(st.noise_maps, S2N_RES))          # coupled form: one shared set
+    assert all(tuple(m.shape) == (1, r, r) for m, r in zip(st.noise.maps, S2N_RES))          # coupled form: one shared set
     lt = 1e-3 if mode == "det" else 3e-3
     worst = dict(noise=0.0, noise_grad=0.0)
     for it in range(2):
@@ -103,7 +103,7 @@ def test_independent_rows_equal_single_row_runs():
     try:
         st = make_step(optimize_noise=True, independent=True)
         st.begin_image(imgs, w_init=w0)
-        assert all(tuple(m.shape) == (nb, r, r) for m, r in zip(st.noise_maps, S2N_RES))
+        assert all(tuple(m.shape) == (nb, r, r) for m, r in zip(st.noise.maps, S2N_RES))
         out = []
         for it in range(2):
             r = st.step(imgs, noises=enc_noises(g, it, "embed_v2_noise.rows", nb=nb))
@@ -137,13 +137,13 @@ def test_phase_two_launches_no_noise_pass_and_moves_no_map():
     imgs1 = torch.as_tensor(g["imgs1"]).cuda()
     st = make_step(optimize_noise=True)
     st.begin_image(imgs1, w_init=torch.as_tensor(g["w0"]))
-    start = st.noise_flat.detach().clone()
+    start = st.noise.flat.detach().clone()
     seen, orig = [], st._opt_phase
 
     def phase(loss, retain_graph=False):
-        before, n0 = st.noise_flat.detach().clone(), sum(1 for n, _ in log if n == "dge_s2_noise_grad")
+        before, n0 = st.noise.flat.detach().clone(), sum(1 for n, _ in log if n == "dge_s2_noise_grad")
         orig(loss, retain_graph=retain_graph)
-        seen.append((torch.equal(before, st.noise_flat.detach()), sum(1 for n, _ in log if n == "dge_s2_noise_grad") - n0))
+        seen.append((torch.equal(before, st.noise.flat.detach()), sum(1 for n, _ in log if n == "dge_s2_noise_grad") - n0))
     st._opt_phase = phase
     ops.KERNEL_LOG = log = []
     try:
@@ -154,14 +154,14 @@ def test_phase_two_launches_no_noise_pass_and_moves_no_map():
     # phase 1: one pass per map; phase 2: none, and the maps have the bits they had when it began
     assert seen == [(True, len(S2N_RES)), (True, 0)], seen
     assert names.count("dge_noise_reg") == 1 and names.count("dge_noise_normalize") == 1
-    assert not torch.equal(start, st.noise_flat.detach())          # one step per iteration
-    assert st.nopt.state[st.noise_flat]["step"] == 1 and st.opt.state[st.w1]["step"] == 2          # a step count of their own
+    assert not torch.equal(start, st.noise.flat.detach())          # one step per iteration
+    assert st.nopt.state[st.noise.flat]["step"] == 1 and st.opt.state[st.w1]["step"] == 2          # a step count of their own
     assert st.G.synthesis.noise_grad_enabled is True
     # begin_image puts the maps back and clears their Adam state, in place
-    ptr = st.noise_flat.data_ptr()
+    ptr = st.noise.flat.data_ptr()
     st.begin_image(imgs1, w_init=torch.as_tensor(g["w0"]))
-    assert torch.equal(start, st.noise_flat.detach()) and st.noise_flat.data_ptr() == ptr
-    assert st.nopt.state[st.noise_flat]["step"] == 0 and float(st.nopt.state[st.noise_flat]["exp_avg_sq"].abs().max()) == 0.0
+    assert torch.equal(start, st.noise.flat.detach()) and st.noise.flat.data_ptr() == ptr
+    assert st.nopt.state[st.noise.flat]["step"] == 0 and float(st.nopt.state[st.noise.flat]["exp_avg_sq"].abs().max()) == 0.0
 
 
 def test_flag_off_is_the_step_without_the_feature():
@@ -238,7 +238,7 @@ def test_noise_replay_equals_eager_bitwise():
             a.opt.graph_advance()
             a.nopt.graph_advance()
             r = a.step(imgs1, noises)
-            ea.append((r["w1"].clone(), a.noise_flat.detach().clone()))
+            ea.append((r["w1"].clone(), a.noise.flat.detach().clone()))
         b = make_step(optimize_noise=True)
         b.begin_image(imgs1, w_init=w0)
         b.capture(imgs1, noises, warmup=1)
@@ -246,7 +246,7 @@ def test_noise_replay_equals_eager_bitwise():
         rb = []
         for _ in range(3):
             r = b.replay()
-            rb.append((r["w1"].clone(), b.noise_flat.detach().clone()))
+            rb.append((r["w1"].clone(), b.noise.flat.detach().clone()))
         torch.cuda.synchronize()
         for i in range(3):
             assert torch.equal(ea[i][0], rb[i][0]) and torch.equal(ea[i][1], rb[i][1]), i

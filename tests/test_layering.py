@@ -6,7 +6,7 @@ import sys
 
 from tests.conftest import ROOT
 
-LOWER = ("losses", "stylegan2_generator", "s2_conv", "collectives", "generators", "models", "embed_step")
+LOWER = ("losses", "stylegan2_generator", "s2_conv", "collectives", "generators", "models", "embed_step", "noise_maps")
 
 
 def test_lower_modules_do_not_load_the_training_script():

@@ -76,7 +76,7 @@ def test_projector_matches_reference_run(mode):
     assert m["w_avg"] < W_AVG_BOUND and m["w_std"] < W_STD_BOUND, m
     target = torch.as_tensor(g["target"]).cuda()
     st.begin_image(target)
-    assert tuple(st.w.shape) == (PROJ_B, 512) and all(tuple(x.shape) == (PROJ_B, r, r) for x, r in zip(st.noise_maps, S2N_RES))
+    assert tuple(st.w.shape) == (PROJ_B, 512) and all(tuple(x.shape) == (PROJ_B, r, r) for x, r in zip(st.noise.maps, S2N_RES))
     assert torch.equal(st.w[0], st.w_avg) and torch.equal(st.w[1], st.w_avg)
     lt = 1e-3 if mode == "det" else 3e-3
     worst = dict(noise=0.0, noise_grad=0.0, exempt=0.0)
@@ -169,7 +169,7 @@ def test_replay_equals_eager_bitwise_and_serves_a_second_group():
             res = []
             for _ in range(PROJ_ITERS):
                 r = st.step(target)
-                res.append((r["w"].clone(), st.noise_flat.detach().clone(), r["lr"], r["noise_scale"]))
+                res.append((r["w"].clone(), st.noise.flat.detach().clone(), r["lr"], r["noise_scale"]))
             return res
         ea, eb = eager(a_img, [0, 1]), eager(b_img, [7, 8])
         st = make_step(seed=3)
@@ -184,7 +184,7 @@ def test_replay_equals_eager_bitwise_and_serves_a_second_group():
             for i in range(PROJ_ITERS):
                 r = st.replay()
                 torch.cuda.synchronize()
-                assert torch.equal(r["w"], want[i][0]) and torch.equal(st.noise_flat.detach(), want[i][1]), (numbers, i)
+                assert torch.equal(r["w"], want[i][0]) and torch.equal(st.noise.flat.detach(), want[i][1]), (numbers, i)
                 assert r["lr"] == want[i][2] and r["noise_scale"] == want[i][3]
             assert st.it == PROJ_ITERS and st.opt.t == PROJ_ITERS
         assert ea[1][2] != ea[0][2] and ea[1][3] != ea[0][3]          # the schedule moved between the iterations

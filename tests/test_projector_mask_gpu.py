@@ -84,7 +84,7 @@ def test_all_ones_mask_against_the_unmasked_step():
             assert "mask_cover" not in ra and torch.equal(rb["mask_cover"].cpu(), torch.ones(PROJ_B))
             m = dict(w_l2=l2rel(rb["w"].cpu().numpy(), ra["w"].cpu().numpy()), w=relerr(rb["w"].cpu().numpy(), ra["w"].cpu().numpy()),
                      w_grad=l2rel(rb["w_grad"].cpu().numpy(), ra["w_grad"].cpu().numpy()), noise=l2rel(flat_maps(rb), flat_maps(ra)))
-            equal = equal and torch.equal(ra["w"], rb["w"]) and torch.equal(a.noise_flat.detach(), b.noise_flat.detach())
+            equal = equal and torch.equal(ra["w"], rb["w"]) and torch.equal(a.noise.flat.detach(), b.noise.flat.detach())
             meas(f"projector_mask.ones.it{it}", bits_equal=str(equal), **m)
             assert m["w_l2"] < 1e-3 and m["w"] < 4e-3 and m["w_grad"] < 1e-3, (it, m)
             assert m["noise"] < ROWS_NOISE_L2_BOUND, (it, m)
@@ -103,7 +103,7 @@ def test_three_iterations_do_not_see_what_lies_under_the_mask():
             st.begin_image(t, mask=mask)
             for _ in range(PROJ_ITERS):
                 r = st.step(t)
-            res.append((r["w"].clone(), st.noise_flat.detach().clone(), r["dist"].clone()))
+            res.append((r["w"].clone(), st.noise.flat.detach().clone(), r["dist"].clone()))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][2], res[1][2])
 
 
@@ -145,7 +145,7 @@ def test_masked_replay_equals_eager_bitwise_with_a_mask_per_group():
             res = []
             for _ in range(PROJ_ITERS):
                 r = st.step(target)
-                res.append((r["w"].clone(), st.noise_flat.detach().clone(), r["dist"].clone()))
+                res.append((r["w"].clone(), st.noise.flat.detach().clone(), r["dist"].clone()))
             return res, r["mask_cover"].clone()
         (ea, ca), (eb, cb) = eager(a_img, a_m, [0, 1]), eager(b_img, b_m, [7, 8])
         st = make_step(seed=3)
@@ -157,7 +157,7 @@ def test_masked_replay_equals_eager_bitwise_with_a_mask_per_group():
             for i in range(PROJ_ITERS):
                 r = st.replay()
                 torch.cuda.synchronize()
-                assert torch.equal(r["w"], want[i][0]) and torch.equal(st.noise_flat.detach(), want[i][1]), (numbers, i)
+                assert torch.equal(r["w"], want[i][0]) and torch.equal(st.noise.flat.detach(), want[i][1]), (numbers, i)
                 assert torch.equal(r["dist"], want[i][2]) and torch.equal(r["mask_cover"], cover), (numbers, i)
         assert not torch.equal(ea[2][0], eb[2][0])
         # a masked capture refuses a group without a mask, and an unmasked capture a group with one
