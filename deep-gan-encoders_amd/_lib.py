@@ -51,6 +51,12 @@ class S2GradEntry(C.Structure):
                 ("nslot_p", C.c_int), ("nslot_s", C.c_int), ("in_c", C.c_int), ("out_c", C.c_int), ("row", C.c_int), ("bscale", C.c_float)]
 
 
+class S2SGradEntry(C.Structure):
+    _fields_ = [("P", C.c_void_p), ("st", C.c_void_p), ("d", C.c_void_p), ("s", C.c_void_p), ("bias", C.c_void_p), ("wsq", C.c_void_p),
+                ("gs", C.c_void_p), ("out", C.c_void_p),
+                ("nslot_p", C.c_int), ("nslot_s", C.c_int), ("in_c", C.c_int), ("out_c", C.c_int), ("bscale", C.c_float), ("pad", C.c_int)]
+
+
 class SumPlanarEntry(C.Structure):
     _fields_ = [("partial", C.c_void_p), ("out", C.c_void_p), ("nslot", C.c_int), ("C", C.c_int), ("NS", C.c_int), ("pad", C.c_int)]
 
@@ -243,6 +249,9 @@ SIGNATURES = {
     "dge_lpips_head_w": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _F, _I, _P],
     "dge_lpips_head_w_finalize": [_P, _P, _P, _P, _P, _I, _P],
     "dge_mask_blend": [_P, _P, _P, _P, _I, _I, _P],
+    "dge_s2_style_grads_s": [C.POINTER(S2SGradEntry), _I, _I, _P],
+    "dge_cols_mean_std_work_bytes": [C.c_longlong, _I],
+    "dge_cols_mean_std": [_P, C.c_longlong, _I, _P, _P, _P, C.c_longlong, _P],
 }
 
 _lib = None

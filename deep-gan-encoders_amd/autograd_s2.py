@@ -9,6 +9,12 @@ from .stylegan2_generator import _dt
 from .weight_cache import version
 
 
+def style_groups(mod):
+    """[(modulated block, its row of wp)] in the order of the flat style buffer: the conv layers, then the toRGB blocks."""
+    nl = mod.num_layers
+    return [(getattr(mod, f"layer{i}"), i) for i in range(nl - 1)] + [(getattr(mod, f"output{k}"), 2 * k + 1) for k in range(nl // 2)]
+
+
 def _style_tables(mod, B, dt):
     """Row-concatenated style weights / demodulation tables of all 17 + 9 modulated blocks (cached; G is frozen in E_align)
     so that every style vector and demodulation factor of a pass comes from two launches (dge_linear_rows, dge_demod_rows).
@@ -16,7 +22,7 @@ def _style_tables(mod, B, dt):
     tables of its batch size, and a step at another batch size on the same generator must not free them under it (the next
     replay of the first graph would index through freed memory)."""
     nl = mod.num_layers
-    groups = [(getattr(mod, f"layer{i}"), i) for i in range(nl - 1)] + [(getattr(mod, f"output{k}"), 2 * k + 1) for k in range(nl // 2)]
+    groups = style_groups(mod)
     key = (B, str(dt)) + tuple(version(p) for L, _ in groups for p in (L.style.weight, L.style.bias, L.weight))
     cache = mod.__dict__.setdefault("_style_tab", {})
     hit = cache.get(key[:2])
@@ -72,17 +78,42 @@ def check_noises(mod, noises, B, device):
     return noises
 
 
-def synthesis_run(mod, wp, randomize_noise=False, save=False, noises=None):
-    dt = _dt(mod.compute_dtype)
+def styles_from_wp(mod, wp, out=None, tab=None):
+    """Every style vector of the pass from wp [B,L,512] in one launch (dge_linear_rows) -> the flat f32 buffer of _style_tables'
+    layout for batch B (block g at B * off_g, viewed [B,C_g]); `out`: written in place."""
     B = wp.shape[0]
-    results = {"wp": wp}
+    tab = _style_tables(mod, B, _dt(mod.compute_dtype)) if tab is None else tab
+    wpc = wp if (wp.dtype == torch.float32 and wp.is_contiguous()) else wp.float().contiguous()
+    s_all = torch.empty(tab["s_total"], dtype=torch.float32, device=wp.device) if out is None else out
+    ops.linear_rows(wpc, mod.num_layers * mod.w_space_dim, tab["xoff"], tab["Wc"], tab["bc"], s_all, tab["ybase"], tab["ybs"], B,
+                    tab["wscale"], tab["bscale"], tab["add"])
+    return s_all
+
+
+def styles_batch(mod, styles):
+    """The batch size a flat style buffer `styles` holds (ValueError where it is no such buffer)."""
+    per_row = sum(L.in_c for L, _ in style_groups(mod))
+    if (not torch.is_tensor(styles) or styles.dtype != torch.float32 or styles.dim() != 1 or styles.numel() == 0 or styles.numel() % per_row
+            or not styles.is_contiguous()):
+        raise ValueError(f"synthesis: `styles` is a StyleCodes or its flat tensor: contiguous float32 [B * {per_row}]")
+    return styles.numel() // per_row
+
+
+def synthesis_run(mod, wp, randomize_noise=False, save=False, noises=None, styles=None):
+    """`styles` (with wp None): the flat style buffer in place of the one dge_linear_rows fills from wp."""
+    dt = _dt(mod.compute_dtype)
     nl = mod.num_layers
     # ---- all styles and demodulation factors of the pass: two launches instead of 2*17 + 9
-    tab = _style_tables(mod, B, dt)
-    wpc = wp if (wp.dtype == torch.float32 and wp.is_contiguous()) else wp.float().contiguous()
-    s_all = torch.empty(tab["s_total"], dtype=torch.float32, device=wp.device)
-    ops.linear_rows(wpc, nl * mod.w_space_dim, tab["xoff"], tab["Wc"], tab["bc"], s_all, tab["ybase"], tab["ybs"], B,
-                    tab["wscale"], tab["bscale"], tab["add"])
+    if styles is None:
+        B = wp.shape[0]
+        results = {"wp": wp}
+        tab = _style_tables(mod, B, dt)
+        s_all = styles_from_wp(mod, wp, tab=tab)
+    else:
+        B = styles_batch(mod, styles)
+        results = {}
+        tab = _style_tables(mod, B, dt)
+        wp = s_all = styles
     d_all = torch.empty(tab["d_total"], dtype=torch.float32, device=wp.device)
     ops.demod_rows(s_all, tab["wsq"], tab["woff"], tab["sbase"], tab["cin"], d_all, tab["dbase"], tab["dbs"], B, tab["eps"])
     s_of = lambda g, C: s_all[tab["s_off"][g]:tab["s_off"][g] + B * C].view(B, C)
@@ -145,12 +176,14 @@ def _torgb_adjoint(mod, saved, i, g_img, x_in, emit):
 
 
 def _style_grads(L, rec, dt, R, st, g_wp_row):
-    """style / demodulation gradients of a layer whose tail backward ran as a pass of its own (sums in R), st [B,in_c,2] -> g_wp[:, i]"""
+    """style / demodulation gradients of a layer whose tail backward ran as a pass of its own (sums in R), st [B,in_c,2] -> g_wp[:, i]
+    (g_wp_row None, the S form: the layer stops at g_s = st[..., 0], which dge_s2_style_grads_s brings to the block's slice)"""
     B = st.shape[0]
     t = ops.demod_bwd(R, rec["d"], L.bias.detach(), L.noise_strength.detach().reshape(1), L.bscale)
     gs_view = st.view(B, -1)      # [B, 2*Cin]: element (b, 2*i) = g_s[b,i]
     ops.linear_t(t, L._prepared(dt)[1], gs_view, mul=rec["s"], accumulate=True, incy=2, ldy=2 * L.in_c)
-    ops.linear_t(gs_view, L.style.weight.detach(), g_wp_row, scale=L.style.wscale, accumulate=True, incx=2, ldx=2 * L.in_c, O=L.in_c)
+    if g_wp_row is not None:
+        ops.linear_t(gs_view, L.style.weight.detach(), g_wp_row, scale=L.style.wscale, accumulate=True, incx=2, ldx=2 * L.in_c, O=L.in_c)
 
 
 def _noise_grad(ng, i, L, rec, g, z_form):
@@ -160,16 +193,23 @@ def _noise_grad(ng, i, L, rec, g, z_form):
         ops.s2_noise_grad(g, None if z_form else rec["y"], L.gain, L.noise_strength.detach().reshape(1), ng[i])
 
 
-def _backward_fused(mod, saved, g_img, g_wp, dt, ng=None):
+def _backward_fused(mod, saved, g_img, g_wp, dt, ng=None, gs=None):
     """Atomics mode.  The gradient travels down the chain as g_z, w.r.t. the pre-activation of each layer: the data-gradient launch
     of layer i + 1 differentiates layer i's noise / bias / lrelu tail in its own epilogue (`prep`: it streams layer i's stored
     output as dot_src anyway) and leaves the two per-(b,c) sums of the demodulation gradient in P; the demodulation factor d
     multiplies g_z in the NEXT launch.  Every style gradient leaves in ONE launch at the end (dge_s2_style_grads): none feeds the
     chain.  Where the route of layer i + 1 does not take prep (s2_conv.dgrad_route), layer i runs its tail as a pass of its own and
-    finishes its style gradient as the deterministic chain does."""
-    B, dev, layers, top = g_wp.shape[0], g_wp.device, saved["layers"], mod.num_layers - 2
+    finishes its style gradient as the deterministic chain does.
+    S form (`gs`: every block's [B,in_c] slice of the style-gradient buffer in the order of style_groups, g_wp None): the same
+    chain and the same `blocks`, each with its slice in place of (wstyle, row), end in dge_s2_style_grads_s."""
+    B, dev, layers, top = g_img.shape[0], g_img.device, saved["layers"], mod.num_layers - 2
     blocks = []
-    emit = lambda g_srgb, O, row: blocks.append(dict(gs=g_srgb, wstyle=O.style.weight.detach(), row=row))
+    if gs is None:
+        emit = lambda g_srgb, O, row: blocks.append(dict(gs=g_srgb, wstyle=O.style.weight.detach(), row=row))
+        dest = lambda L, i: dict(wstyle=L.style.weight.detach(), row=i)
+    else:
+        emit = lambda g_srgb, O, row: blocks.append(dict(gs=g_srgb, out=gs[top + 1 + (row - 1) // 2]))          # (toRGB k: row 2k + 1)
+        dest = lambda L, i: dict(out=gs[i])
     # top layer: its output only feeds the last toRGB (image_k = rgb_k + up(image_{k-1}), :515-522)
     Lt, Ot = getattr(mod, f"layer{top}"), getattr(mod, f"output{top // 2}")
     g_x, g_srgb, P = ops.torgb_bwd_prep(g_img, layers[top]["y"], Ot.weight.detach().reshape(3, -1), saved["rgb"][top // 2]["s"], Ot.wscale,
@@ -197,18 +237,30 @@ def _backward_fused(mod, saved, g_img, g_wp, dt, ng=None):
         g_x = s2_conv.dgrad(L, route, g_y, d_in, dt, prep, rec["s"], addend, st, x_in)
         if P is not None:
             blocks.append(dict(P=P, st=st, d=rec["d"], s=rec["s"], bias=L.bias.detach(), wsq=L._prepared(dt)[1], bscale=L.bscale,
-                               wstyle=L.style.weight.detach(), row=i))
+                               **dest(L, i)))
         else:
-            _style_grads(L, rec, dt, R, ops.sum_slots(st.buf, ops.zeros((B, L.in_c, 2), dev), accumulate=False), g_wp[:, i])
+            st1 = ops.sum_slots(st.buf, ops.zeros((B, L.in_c, 2), dev), accumulate=False)
+            _style_grads(L, rec, dt, R, st1, None if gs is not None else g_wp[:, i])
+            if gs is not None:
+                blocks.append(dict(st=st1, out=gs[i]))
         P = P_next
-    ops.s2_style_grads(blocks, g_wp, getattr(mod, "layer0").style.wscale)
+    if gs is not None:
+        ops.s2_style_grads_s(blocks, B)
+    else:
+        ops.s2_style_grads(blocks, g_wp, getattr(mod, "layer0").style.wscale)
 
 
-def _backward_det(mod, saved, g_img, g_wp, dt, ng=None):
+def _backward_det(mod, saved, g_img, g_wp, dt, ng=None, gs=None):
     """Deterministic mode: the same math with no atomics.  The gradient travels as g_x, w.r.t. each layer's output; the tail backward
-    is a pass of its own per layer (dge_modconv_bwd_prep, which applies d), and each layer's style gradient is finished on the spot."""
-    B, dev, layers, top = g_wp.shape[0], g_wp.device, saved["layers"], mod.num_layers - 2
-    emit = lambda g_srgb, O, row: ops.linear_t(g_srgb, O.style.weight.detach(), g_wp[:, row], scale=O.style.wscale, accumulate=True)
+    is a pass of its own per layer (dge_modconv_bwd_prep, which applies d), and each layer's style gradient is finished on the spot.
+    S form (`gs` as in _backward_fused): every layer stops at g_s, and one dge_s2_style_grads_s launch at the end brings the g_s of
+    all blocks to their slices (plain stores, one writer per element)."""
+    B, dev, layers, top = g_img.shape[0], g_img.device, saved["layers"], mod.num_layers - 2
+    blocks = []
+    if gs is None:
+        emit = lambda g_srgb, O, row: ops.linear_t(g_srgb, O.style.weight.detach(), g_wp[:, row], scale=O.style.wscale, accumulate=True)
+    else:
+        emit = lambda g_srgb, O, row: blocks.append(dict(gs=g_srgb, out=gs[top + 1 + (row - 1) // 2]))
     # top layer: its output only feeds the last toRGB (image_k = rgb_k + up(image_{k-1}), :515-522)
     Ot = getattr(mod, f"output{top // 2}")
     g_x, g_srgb = ops.torgb_bwd(g_img, layers[top]["y"], Ot.weight.detach().reshape(3, -1), saved["rgb"][top // 2]["s"], Ot.wscale)
@@ -224,29 +276,59 @@ def _backward_det(mod, saved, g_img, g_wp, dt, ng=None):
         addend, g_img = _torgb_adjoint(mod, saved, i, g_img, x_in, emit)
         st = ops.zeros((B, L.in_c, 2), dev)
         g_x = s2_conv.dgrad(L, s2_conv.dgrad_route(L, B, dt, False, False), g_y, None, dt, None, rec["s"], addend, st, x_in)
-        _style_grads(L, rec, dt, R, st, g_wp[:, i])
+        _style_grads(L, rec, dt, R, st, None if gs is not None else g_wp[:, i])
+        if gs is not None:
+            blocks.append(dict(st=st, out=gs[i]))
+    if gs is not None:
+        ops.s2_style_grads_s(blocks, B)
 
 
-def synthesis_backward(mod, wp, saved, g_image, noise_grads=None):
+def synthesis_backward(mod, wp, saved, g_image, noise_grads=None, style_grads=None):
     """d(image)/d(wp) contracted with g_image [B,3,R,R] -> g_wp [B,num_layers,512], layer by layer from the top (the pre-activation
     of a layer is z = yraw*d + noise*ns + bias, stylegan2_generator.py:908-921), in the form of the library's mode.
     `noise_grads`: {conv layer: f32 [Bn, res^2]} to receive the gradient w.r.t. that layer's noise map (Bn 1: the map is shared by
-    the batch) - a pass of its own per entry beside the chain (dge_s2_noise_grad), which runs exactly as it does without."""
-    g_wp = ops.zeros((wp.shape[0], mod.num_layers, mod.w_space_dim), wp.device)
+    the batch) - a pass of its own per entry beside the chain (dge_s2_noise_grad), which runs exactly as it does without.
+    `style_grads` (the S form, for a pass that ran on `styles`; wp is ignored): the flat f32 buffer of the styles' layout that
+    receives d(image)/d(styles) contracted with g_image, every element written once; no g_wp is allocated, and it is what returns."""
     chain = _backward_det if ops.is_deterministic() else _backward_fused
+    if style_grads is not None:
+        B, off, gs = g_image.shape[0], 0, []
+        for L, _ in style_groups(mod):
+            gs.append(style_grads[B * off:B * (off + L.in_c)].view(B, L.in_c))
+            off += L.in_c
+        if style_grads.numel() != B * off or style_grads.dtype != torch.float32 or not style_grads.is_contiguous():
+            raise ValueError(f"synthesis: the style-gradient buffer must be contiguous float32 [{B * off}]")
+        chain(mod, saved, g_image.float().contiguous(), None, ops.dtype_of(saved["const"]), noise_grads, gs)
+        return style_grads
+    g_wp = ops.zeros((wp.shape[0], mod.num_layers, mod.w_space_dim), wp.device)
     chain(mod, saved, g_image.float().contiguous(), g_wp, ops.dtype_of(saved["const"]), noise_grads)
     return g_wp
+
+
+class StyleGradOut:
+    """grad_out of SynthesisFunction in S form: `noises` = noise_grad_out, `styles` = style_grad_out (either may be None)."""
+    __slots__ = ("noises", "styles")
+
+    def __init__(self, noises, styles):
+        self.noises, self.styles = noises, styles
 
 
 class SynthesisFunction(torch.autograd.Function):
     """Inputs behind `keys`: `grad_out` (None, or per conv layer None or an f32 buffer of the map's shape: the backward writes that
     layer's noise gradient THERE instead of returning it to autograd - static storage for a captured iteration, no accumulation
-    pass) and the noise maps, if any."""
+    pass) and the noise maps, if any.  S form: `wp` is the flat style buffer and `grad_out` a StyleGradOut around the two
+    destinations, the noise maps' list and the flat buffer for the style gradient (None: it returns to autograd)."""
 
     @staticmethod
     def forward(ctx, mod, wp, randomize_noise, keys, grad_out, *noises):
         need = any(ctx.needs_input_grad)
-        results, saved = synthesis_run(mod, wp.detach(), randomize_noise, save=need, noises=noises or None)
+        ctx.s_form = isinstance(grad_out, StyleGradOut)
+        ctx.style_out = grad_out.styles if ctx.s_form else None
+        if ctx.s_form:
+            grad_out = grad_out.noises
+            results, saved = synthesis_run(mod, None, randomize_noise, save=need, noises=noises or None, styles=wp.detach())
+        else:
+            results, saved = synthesis_run(mod, wp.detach(), randomize_noise, save=need, noises=noises or None)
         ctx.mod, ctx.saved_acts, ctx.wp = mod, saved, wp.detach()
         ctx.grad_out, ctx.noise_shapes = grad_out, [tuple(n.shape) for n in noises]
         keys += [k for k in results if k not in ("wp", "image")]          # (the caller's list: the order synthesis_run produced)
@@ -269,14 +351,21 @@ class SynthesisFunction(torch.autograd.Function):
                         raise ValueError(f"synthesis: noise_grad_out[{i}] must be float32 {shape}")
                     else:
                         ng[i] = out
+        if ctx.s_form:
+            out = ctx.style_out if ctx.style_out is not None else torch.empty_like(ctx.wp)
+            synthesis_backward(ctx.mod, None, ctx.saved_acts, g_image, ng, style_grads=out)
+            return (None, None if ctx.style_out is not None else out, None, None, None, *ret)
         g_wp = synthesis_backward(ctx.mod, ctx.wp, ctx.saved_acts, g_image, ng)
         return (None, g_wp, None, None, None, *ret)
 
 
-def synthesis_forward(mod, wp, randomize_noise=False, noises=None, noise_grad_out=None):
+def synthesis_forward(mod, wp, randomize_noise=False, noises=None, noise_grad_out=None, styles=None, style_grad_out=None):
     """SynthesisModule.forward: conv layer i is driven by wp[:, i]; the toRGB of block k by
     wp[:, 2k+1] (reference :511-517).  Returns the reference's result dict.  `noises`: the conv layers' noise maps in place of the
-    `layer{i}.noise` buffers (check_noises); the image is differentiable w.r.t. every map that requires grad."""
+    `layer{i}.noise` buffers (check_noises); the image is differentiable w.r.t. every map that requires grad.
+    `styles` (a StyleCodes or its flat tensor, with wp None): the pass starts from the style vectors themselves (_synthesis_styles)."""
+    if styles is not None or style_grad_out is not None:
+        return _synthesis_styles(mod, wp, randomize_noise, noises, noise_grad_out, styles, style_grad_out)
     wp = wp if (wp.dtype == torch.float32 and wp.is_contiguous()) else wp.float().contiguous()
     if noises is not None:
         if randomize_noise:
@@ -289,4 +378,35 @@ def synthesis_forward(mod, wp, randomize_noise=False, noises=None, noise_grad_ou
         image, *outs = SynthesisFunction.apply(mod, wp, randomize_noise, keys, noise_grad_out, *(noises or ()))
         return {"wp": wp, **dict(zip(keys, outs)), "image": image}
     results, _ = synthesis_run(mod, wp, randomize_noise, save=False, noises=noises)
+    return results
+
+
+def _synthesis_styles(mod, wp, randomize_noise, noises, noise_grad_out, styles, style_grad_out):
+    """synthesis(styles=...): the S code as the input of the pass.  No dge_linear_rows: the flat buffer feeds dge_demod_rows and the
+    layers as s_all does.  The result dict holds the image and the style views, and no wp.  Where the flat tensor requires grad the
+    backward ends in S form (synthesis_backward(style_grads=...)); `style_grad_out`: a flat f32 buffer of the styles' layout that
+    the gradient is written to INSTEAD of reaching .grad (noise_grad_out's convention, for a captured iteration)."""
+    if styles is None:
+        raise ValueError("synthesis: style_grad_out needs `styles`: it receives the gradient of the style codes")
+    if wp is not None:
+        raise ValueError("synthesis: `styles` takes the place of wp: pass wp=None with it (the styles are not recomputed from wp)")
+    flat = getattr(styles, "flat", styles)
+    B = styles_batch(mod, flat)
+    if not flat.is_cuda:
+        raise ValueError("synthesis: `styles` must be on the GPU")
+    if noises is not None:
+        if randomize_noise:
+            raise ValueError("synthesis: `noises` fixes every noise map; randomize_noise=True contradicts it")
+        noises = check_noises(mod, noises, B, flat.device)
+    if noise_grad_out is not None and (noises is None or len(noise_grad_out) != len(noises)):
+        raise ValueError("synthesis: noise_grad_out takes one buffer (or None) per map of `noises`")
+    if style_grad_out is not None and (not torch.is_tensor(style_grad_out) or tuple(style_grad_out.shape) != tuple(flat.shape)
+                                       or style_grad_out.dtype != torch.float32 or not style_grad_out.is_contiguous()
+                                       or style_grad_out.device != flat.device):
+        raise ValueError(f"synthesis: style_grad_out must be a contiguous float32 buffer {tuple(flat.shape)} on {flat.device}")
+    if torch.is_grad_enabled() and (flat.requires_grad or any(n.requires_grad for n in noises or ())):
+        keys = []
+        image, *outs = SynthesisFunction.apply(mod, flat, randomize_noise, keys, StyleGradOut(noise_grad_out, style_grad_out), *(noises or ()))
+        return {**dict(zip(keys, outs)), "image": image}
+    results, _ = synthesis_run(mod, None, randomize_noise, save=False, noises=noises, styles=flat.detach())
     return results

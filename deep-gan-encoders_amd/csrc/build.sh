@@ -11,7 +11,7 @@ objs=""
 pids=""
 for f in $SRCS; do
   o="build/${f%.hip}.o"
-  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ conv_params.h -nt "$o" ] || [ conv_epilogue.h -nt "$o" ] || [ conv_igemm_impl.h -nt "$o" ] || [ lpips_prep.h -nt "$o" ] || [ ../../include/dge_hip.h -nt "$o" ]; then
+  if [ ! -f "$o" ] || [ "$f" -nt "$o" ] || [ common.h -nt "$o" ] || [ conv_params.h -nt "$o" ] || [ conv_epilogue.h -nt "$o" ] || [ conv_igemm_impl.h -nt "$o" ] || [ lpips_prep.h -nt "$o" ] || [ s2_style_steps.h -nt "$o" ] || [ ../../include/dge_hip.h -nt "$o" ]; then
     echo "hipcc $f"
     rm -f "$o"
     ( hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$f" -o "$o.tmp.$$" && mv "$o.tmp.$$" "$o" ) &

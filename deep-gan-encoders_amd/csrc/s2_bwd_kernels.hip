@@ -3,6 +3,7 @@
 // The heavy part (conv data gradients) reuses conv_igemm with DGE_PACK_DGRAD /
 // DGE_PACK_UPFOLD_DGRAD weights; the kernels here are the HBM-bound glue around it.
 #include "common.h"
+#include "s2_style_steps.h"
 #include "../../include/dge_hip.h"
 
 // Forward (stylegan2_generator.py:905-921): z = yraw*d + noise*ns + bias ; x = lrelu(z)*gain.
@@ -362,25 +363,7 @@ __global__ __launch_bounds__(512) void s2_style_grads_kernel(S2GradTable tab, fl
     const dge_s2_grad_entry e = tab.e[blockIdx.x];
     const int b = blockIdx.y, tid = threadIdx.x;
     if (e.P) {
-        for (int o = tid; o < e.out_c; o += 512) {
-            const int idx = b * e.out_c + o;
-            const float2 pp = sum_slot_pairs(e.P + (size_t)idx * 2, (size_t)B * e.out_c * 2, e.nslot_p);
-            const float dv = e.d[idx];
-            t[o] = -(pp.x - e.bias[o] * e.bscale * pp.y) * dv * dv;
-        }
-        __syncthreads();
-        for (int c = tid; c < e.in_c; c += 512) {
-            float acc[4] = {0.f, 0.f, 0.f, 0.f};
-            int o = 0;
-            for (; o + 3 < e.out_c; o += 4) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[j] = fmaf(t[o + j], e.wsq[(size_t)(o + j) * e.in_c + c], acc[j]);
-            }
-            for (; o < e.out_c; o++) acc[0] = fmaf(t[o], e.wsq[(size_t)o * e.in_c + c], acc[0]);
-            const int idx = b * e.in_c + c;
-            const float2 ss = sum_slot_pairs(e.st + (size_t)idx * 2, (size_t)B * e.in_c * 2, e.nslot_s);
-            gs[c] = ss.x + e.s[idx] * ((acc[0] + acc[1]) + (acc[2] + acc[3]));
-        }
+        s2_conv_block_gs(e, b, B, t, [&](int c, float v) { gs[c] = v; });
     } else {
         for (int c = tid; c < e.in_c; c += 512) gs[c] = e.gs[b * e.in_c + c];
     }

@@ -3,6 +3,8 @@
 * `reconstruct`   - inferE.py:101-141 / rec_real_img.py / synthesized_IMG.py: G(z) -> E -> G(w2) once, no gradients;
 * `edit_latent`   - embeded_img_edit.py:28-41: w[start:start+end] = (w + bonus*direction)[start:start+end] on a W+ code,
                     then one Gs.forward(w, lod);
+* `style_sigma` / `edit_styles` - StyleSpace edits ("block, channel, + k sigma") on the per-channel style codes of StyleGAN2
+                    (style_codes.StyleCodes.rows, `id{n}-s.pt`): no boundary file is needed;
 * `image_metrics` - comparing-baseline.py:21-45 on device: PSNR / MSE on [0,255], cosine on [-1,1], LPIPS and the skimage SSIM of
                     that script (`ssim_skimage`: 7x7 uniform window, sample covariance, data_range 255 - a different statistic
                     from the training loss's pytorch_ssim, which `losses.space_loss` reports);
@@ -78,6 +80,67 @@ def edit_latent(w, direction, bonus=70.0, start=0, end=3):
     d = torch.as_tensor(direction).float().to(w2.device).expand(w2.shape[0], w2.shape[1])
     w2[start:start + end] = (w2 + bonus * d)[start:start + end]
     return w2.reshape(1, w2.shape[0], w2.shape[1])
+
+
+def style_block_names(nblocks):
+    """The names of the `nblocks` = (L - 1) + L / 2 blocks of a StyleSpace code in file order: layer0 .. layer{L-2}, output0 .. output{L/2-1}."""
+    nl = (2 * nblocks + 2) // 3
+    if nblocks < 2 or nl % 2 or (nl - 1) + nl // 2 != nblocks:
+        raise ValueError(f"{nblocks} blocks are not the StyleSpace code of a StyleGAN2 synthesis network ((L - 1) conv + L / 2 toRGB blocks)")
+    return [f"layer{i}" for i in range(nl - 1)] + [f"output{k}" for k in range(nl // 2)]
+
+
+@torch.no_grad()
+def style_sigma(G, samples=10000, seed=0, chunk=1000):
+    """(mean, sigma) of the StyleSpace codes of `samples` z drawn from a CPU generator seeded with `seed` and mapped without
+    truncation: two lists in block order (style_codes.StyleCodes.names), one [C_g] tensor per block.  The styles of a chunk are
+    written into the matrix [samples, sum C_g], and dge_cols_mean_std takes the columns: sigma = sqrt(sum (s - mean)^2 / samples),
+    the unit of `edit_styles`."""
+    from .autograd_s2 import styles_from_wp
+    from .style_codes import style_layout
+    if samples < 1 or chunk < 1:
+        raise ValueError("style_sigma: samples and chunk must be positive")
+    dev = next(G.parameters()).device
+    syn = G.synthesis
+    _, channels, _, per_row = style_layout(syn, 1)
+    z = torch.randn(samples, G.z_space_dim, generator=torch.Generator().manual_seed(int(seed)))
+    X = torch.empty((samples, per_row), dtype=torch.float32, device=dev)
+    for i in range(0, samples, chunk):
+        w = G.mapping(z[i:i + chunk].to(dev))["w"].float().contiguous()
+        n = w.shape[0]
+        flat = styles_from_wp(syn, ops.w_broadcast(w, syn.num_layers))
+        off = 0
+        for C in channels:          # block g of the chunk [n,C_g] sits at n * off_g: to the columns off_g .. of the chunk's rows
+            X[i:i + n, off:off + C] = flat[n * off:n * (off + C)].view(n, C)
+            off += C
+    mean, std = ops.cols_mean_std(X)
+    return list(mean.split(channels)), list(std.split(channels))
+
+
+def edit_styles(rows, block, channel, amount, sigma=None):
+    """A StyleSpace edit "block, channel, + amount": `rows` is the code of one image, the list of [1,C_g] tensors of `id{n}-s.pt`
+    (StyleCodes.rows); `block` a name (`layer9`, `output3`) or an index; `amount` is added to that channel, times
+    sigma[block][channel] where `sigma` (style_sigma's second list) is given.  Returns new rows; plain tensor arithmetic, on
+    whatever device the rows are."""
+    rows = list(rows)
+    names = style_block_names(len(rows))
+    if isinstance(block, str):
+        if block not in names:
+            raise ValueError(f"edit_styles: no block {block!r}; the blocks are {names[0]} .. {names[-1]}")
+        g = names.index(block)
+    else:
+        g = int(block)
+        if not 0 <= g < len(rows):
+            raise ValueError(f"edit_styles: block index {block} outside the {len(rows)} blocks")
+    C = rows[g].shape[-1]
+    if not 0 <= int(channel) < C:
+        raise ValueError(f"edit_styles: channel {channel} outside the {C} channels of {names[g]}")
+    if sigma is not None and (len(sigma) != len(rows) or sigma[g].numel() != C):
+        raise ValueError("edit_styles: sigma holds one [C_g] tensor per block (style_sigma)")
+    unit = 1.0 if sigma is None else float(sigma[g].reshape(-1)[int(channel)])
+    out = [r.detach().clone() for r in rows]
+    out[g][..., int(channel)] += float(amount) * unit
+    return out
 
 
 @torch.no_grad()

@@ -888,6 +888,43 @@ def s2_style_grads(blocks, g_wp, wscale):
     return g_wp
 
 
+def s2_style_grads_s(blocks, B):
+    """The S-space ending of the synthesis backward (dge_s2_style_grads_s): every block of the list stores its style gradient to
+    `out`, its own contiguous [B,in_c] slice of the style-gradient buffer.  Blocks are dicts - conv block: P, st, d, s, bias, wsq,
+    bscale (as s2_style_grads takes them); finished block: st alone (SlotStats or [B,in_c,2]); toRGB block: gs.  One launch."""
+    from ._lib import S2SGradEntry
+    arr = (S2SGradEntry * len(blocks))()
+    for e, blk in zip(arr, blocks):
+        out = blk["out"]
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.shape[0] != B:
+            raise DgeError("s2_style_grads_s: `out` is a contiguous float32 [B,in_c] slice")
+        e.out, e.in_c = _p(out), out.shape[1]
+        if "gs" in blk:
+            if tuple(blk["gs"].shape) != tuple(out.shape):
+                raise DgeError("s2_style_grads_s: gs and out have one shape")
+            e.gs = _f32(blk["gs"])
+            continue
+        st = blk["st"]
+        e.nslot_p, e.nslot_s = 1, 1
+        if isinstance(st, SlotStats):
+            e.nslot_s, st = st.nslot, st.buf
+        if st.numel() != e.nslot_s * B * e.in_c * 2:
+            raise DgeError("s2_style_grads_s: st holds [nslot][B,in_c,2]")
+        e.st = _f32(st)
+        if "P" not in blk:
+            continue
+        P = blk["P"]
+        if isinstance(P, SlotStats):
+            e.nslot_p, P = P.nslot, P.buf
+        e.out_c = blk["d"].shape[1]
+        if blk["s"].shape[1] != e.in_c or P.numel() != e.nslot_p * B * e.out_c * 2 or blk["wsq"].numel() != e.out_c * e.in_c:
+            raise DgeError("s2_style_grads_s: a conv block's P [nslot][B,out_c,2], d [B,out_c], s [B,in_c], wsq [out_c,in_c] disagree")
+        e.P, e.d, e.s, e.bias, e.wsq = _f32(P), _f32(blk["d"]), _f32(blk["s"]), _f32(blk["bias"]), _f32(blk["wsq"])
+        e.bscale = float(blk["bscale"])
+    check(lib().dge_s2_style_grads_s(arr, len(blocks), int(B), _stream()), "dge_s2_style_grads_s")
+    log_kernel()
+
+
 def torgb_bwd(gimg, x, wrgb, style, wscale):
     B, H, W, Cc = x.shape
     gx = torch.empty_like(x)
@@ -1861,6 +1898,22 @@ def rows_mean_std(x):
     mean = torch.empty(D, dtype=torch.float32, device=x.device)
     std = torch.empty(1, dtype=torch.float32, device=x.device)
     check(lib().dge_rows_mean_std(_f32(x), N, D, _p(mean), _p(std), _p(work), work.numel() * 4, _stream()), "dge_rows_mean_std")
+    log_kernel()
+    return mean, std
+
+
+def cols_mean_std(x):
+    """x [N,D] f32 -> (mean [D], std [D]) over the rows, std = sqrt(sum (x - mean)^2 / N) per column (dge_cols_mean_std)."""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise DgeError("cols_mean_std: x is a contiguous float32 matrix [N,D]")
+    N, D = x.shape
+    nb = lib().dge_cols_mean_std_work_bytes(N, D)
+    if nb < 0:
+        check(nb, "dge_cols_mean_std_work_bytes")
+    work = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+    mean = torch.empty(D, dtype=torch.float32, device=x.device)
+    std = torch.empty(D, dtype=torch.float32, device=x.device)
+    check(lib().dge_cols_mean_std(_f32(x), N, D, _p(mean), _p(std), _p(work), work.numel() * 4, _stream()), "dge_cols_mean_std")
     log_kernel()
     return mean, std
 

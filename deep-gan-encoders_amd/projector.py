@@ -41,7 +41,15 @@ LPIPS.value_and_grad(mask_state=...)).  The pyramid is refilled once per group, 
 without a mask refuses a later mask and the other way round.  Extra files with a mask: blend/{n:05d}.png (the target inside the mask,
 the reconstruction outside: the bytes of quantize_u8(ops.mask_blend(mask, real, rec))), mask/{n:05d}.png (8-bit L), and `cover: ...`
 (the kept share of the image) at the end of every Loss.txt line; the result dict gains `mask_cover` [B].  A short last group pads the
-mask as it pads the image.  Without a mask nothing is written or launched that was not before."""
+mask as it pads the image.  Without a mask nothing is written or launched that was not before.
+
+StyleSpace refinement (`--s_steps N [--s_lr x]`, StyleProjectorStep, project(styles=...)): behind the W run of a group, N iterations
+that optimise the group's StyleSpace codes (style_codes.StyleCodes: the style vector of every conv layer and toRGB block, started at
+the styles of the W result) and go on with its noise maps, against the same loss and under the same learning-rate ramp, without
+latent noise.  rec/{n:05d}.png and id{n}-noise.pt are then those of the S stage, id{n}-w.pt and id{n}-wp.pt stay the W result,
+models/id{n}-s.pt holds the codes (a list of [1,C_g] tensors; with id{n}-noise.pt it reloads into synthesis(styles=..., noises=...)
+and gives the PNG byte for byte), and Loss.txt gets the stage's lines (`id_n_____s_i`).  The default --s_steps 0 changes nothing.
+The base rate --s_lr defaults to 0.01; nobody has tuned that value."""
 import argparse
 import math
 import os
@@ -53,6 +61,7 @@ from .custom_adam import Adam
 from .embed_step import several_processes
 from .graph_step import GraphReplay
 from .noise_maps import NoiseMaps, save_noise_rows
+from .style_codes import save_style_rows
 
 
 def projector_schedule(step, steps, lr=0.1, w_std=1.0, initial_noise_factor=0.05, noise_ramp=0.75, lr_rampdown=0.25, lr_rampup=0.05):
@@ -88,12 +97,68 @@ class _WBroadcast(torch.autograd.Function):
         return ops.w_broadcast_bwd(g.float().contiguous()), None, None, None
 
 
-class ProjectorStep(GraphReplay):
+class _LpipsFit(GraphReplay):
+    """What the two stages of a projection share: the area pooling in front of LPIPS, the group's mask, and the per-row LPIPS value
+    with the gradient of its sum w.r.t. the synthesised images."""
+    POOL_TO = 256          # LPIPS runs on images of at most this side (the projector's area pooling)
+    _mask_state = _mask_cover = _graph_masked = None
+
+    def _pool_k(self, H):
+        k = 1
+        while H // k > self.POOL_TO:
+            k *= 2
+        return k
+
+    def _set_mask(self, target, mask, who):
+        """The group's mask [B,1,H,W] (or None) into the step: pooled by the step's k to the LPIPS resolution, the state refilled in
+        place (one dge_mask_pyramid call outside the captured iteration), mask_cover refreshed in place."""
+        cls = type(self).__name__
+        if self.captured and (mask is not None) != self._graph_masked:
+            raise ValueError(f"{cls}.{who}: the iteration was captured " + ("with a mask, and this group has none" if self._graph_masked
+                             else "without a mask, and this group has one") + "; the masked and the unmasked iteration are different "
+                             "launches: use a step of its own for each")
+        if mask is None:
+            self._mask_state = self._mask_cover = None
+            return
+        B, _, H, W = target.shape
+        if mask.dim() == 3:
+            mask = mask[:, None]
+        if tuple(mask.shape) != (B, 1, H, W):
+            raise ValueError(f"{cls}.{who}: the mask must be [B,1,H,W] = {(B, 1, H, W)} at the target's size, got {tuple(mask.shape)}")
+        m = mask.detach().to(device=target.device, dtype=torch.float32).contiguous()
+        k = self._pool_k(H)
+        if k > 1:
+            m = ops.area_pool(m, k)
+        if self._mask_state is None or self._mask_state.shape != (B, m.shape[2], m.shape[3]):
+            if self.captured:
+                raise ValueError(f"{cls}.{who}: the captured iteration works on a different mask geometry")
+            self._mask_state = self.lpips.mask_state(m)
+            self._mask_cover = torch.empty(B, dtype=torch.float32, device=target.device)
+        else:
+            self._mask_state.set(m)
+        self._mask_cover.copy_(self._mask_state.cover())
+
+    def _dist_and_grad(self, target, imgs):
+        """(dist [B], d sum_b dist_b / d imgs) of the synthesised `imgs` against `target`, both area-pooled to POOL_TO where larger,
+        mask-weighted when the group has a mask."""
+        B, k = target.shape[0], self._pool_k(target.shape[2])
+        with torch.no_grad():
+            a, b = target.float().contiguous(), imgs.detach().float().contiguous()
+            if k > 1:
+                a, b = ops.area_pool(a, k), ops.area_pool(b, k)
+            if self._mask_state is None:
+                dist, gb = self.lpips.value_and_grad(a, b, per_sample=True)
+            else:
+                dist, gb = self.lpips.value_and_grad(a, b, per_sample=True, mask_state=self._mask_state)
+            if B > 1:
+                ops.scale_(gb, B)          # value_and_grad returns d mean / d b; the loss is the sum over the rows
+            return dist, (gb if k == 1 else ops.area_pool_bwd(gb, k))
+
+
+class ProjectorStep(_LpipsFit):
     """One projection step (module docstring).  G is a StyleGAN2Generator in eval mode.  The constructor FREEZES G: every parameter
     gets requires_grad_(False) and keeps it (the synthesis backward then computes the data gradient only); a caller that trains
     the same G afterwards switches the flags back on itself."""
-    POOL_TO = 256          # LPIPS runs on images of at most this side (the projector's area pooling)
-
     def __init__(self, G, lpips_model, steps=1000, lr=0.1, initial_noise_factor=0.05, noise_ramp=0.75, lr_rampdown=0.25, lr_rampup=0.05,
                  noise_reg=1e5, w_avg_samples=10000, seed=0):
         if several_processes():
@@ -132,40 +197,6 @@ class ProjectorStep(GraphReplay):
         return projector_schedule(iteration, self.steps, self.lr, self.w_stats()[1], **self._sched)
 
     # ------------------------------------------------------------------ per image group
-    def _pool_k(self, H):
-        k = 1
-        while H // k > self.POOL_TO:
-            k *= 2
-        return k
-
-    def _set_mask(self, target, mask, who):
-        """The group's mask [B,1,H,W] (or None) into the step: pooled by the step's k to the LPIPS resolution, the state refilled in
-        place (one dge_mask_pyramid call outside the captured iteration), mask_cover refreshed in place."""
-        if self.captured and (mask is not None) != self._graph_masked:
-            raise ValueError(f"ProjectorStep.{who}: the iteration was captured " + ("with a mask, and this group has none" if self._graph_masked
-                             else "without a mask, and this group has one") + "; the masked and the unmasked iteration are different "
-                             "launches: use a step of its own for each")
-        if mask is None:
-            self._mask_state = self._mask_cover = None
-            return
-        B, _, H, W = target.shape
-        if mask.dim() == 3:
-            mask = mask[:, None]
-        if tuple(mask.shape) != (B, 1, H, W):
-            raise ValueError(f"ProjectorStep.{who}: the mask must be [B,1,H,W] = {(B, 1, H, W)} at the target's size, got {tuple(mask.shape)}")
-        m = mask.detach().to(device=target.device, dtype=torch.float32).contiguous()
-        k = self._pool_k(H)
-        if k > 1:
-            m = ops.area_pool(m, k)
-        if self._mask_state is None or self._mask_state.shape != (B, m.shape[2], m.shape[3]):
-            if self.captured:
-                raise ValueError(f"ProjectorStep.{who}: the captured iteration works on a different mask geometry")
-            self._mask_state = self.lpips.mask_state(m)
-            self._mask_cover = torch.empty(B, dtype=torch.float32, device=target.device)
-        else:
-            self._mask_state.set(m)
-        self._mask_cover.copy_(self._mask_state.cover())
-
     def begin_image(self, target, numbers=None, mask=None):
         """Start the group of `target` [B,3,H,W]: w = w_avg in every row, the maps = the generator's buffers in every row, Adam's
         state cleared, the iteration count at 0 - all in place (a captured iteration stays valid).  The maps are initialised from
@@ -204,7 +235,6 @@ class ProjectorStep(GraphReplay):
         and noise_scale (host floats); no host synchronisation."""
         if self.group < 0:
             raise RuntimeError("ProjectorStep.step: call begin_image() first")
-        B, H = target.shape[0], target.shape[2]
         graph = self._ns_dev is not None
         if graph and not self._inputs_fresh:          # an eager iteration behind capture(): it reads the device scalars too
             self._graph_inputs(self.it)
@@ -214,18 +244,7 @@ class ProjectorStep(GraphReplay):
             w_noise = ops.randn_seeded(self._wn, self._seeds(), self._seeds_dev)
         ws = _WBroadcast.apply(self.w, w_noise, self._ns_dev if graph else ns_t, self.G.num_layers)
         imgs = self.G.synthesis(ws, randomize_noise=False, noises=self.noise.maps, noise_grad_out=self.noise.grads)["image"]
-        k = self._pool_k(H)
-        with torch.no_grad():
-            a, b = target.float().contiguous(), imgs.detach().float().contiguous()
-            if k > 1:
-                a, b = ops.area_pool(a, k), ops.area_pool(b, k)
-            if self._mask_state is None:
-                dist, gb = self.lpips.value_and_grad(a, b, per_sample=True)
-            else:
-                dist, gb = self.lpips.value_and_grad(a, b, per_sample=True, mask_state=self._mask_state)
-            if B > 1:
-                ops.scale_(gb, B)          # value_and_grad returns d mean / d b; the loss is the sum over the rows
-            g_img = gb if k == 1 else ops.area_pool_bwd(gb, k)
+        dist, g_img = self._dist_and_grad(target, imgs)
         self.w.grad = None
         imgs.backward(g_img)
         reg = self.noise.add_reg(self.noise_reg)
@@ -299,14 +318,169 @@ class ProjectorStep(GraphReplay):
         return w, wp, maps, self.G.synthesis(wp, randomize_noise=False, noises=maps)["image"]
 
 
-def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=None, keep=None, mask=None):
+class StyleProjectorStep(_LpipsFit):
+    """The second stage of a projection: the StyleSpace codes of the W result (style_codes.StyleCodes: the per-channel style
+    vectors of every conv layer and toRGB block) and the noise maps are refined with Adam against the same loss.  Per iteration:
+
+        lr_t = projector_schedule(i, steps, lr)[0]                        host double; no latent noise: S has no counterpart of w_std
+        imgs = G.synthesis(styles=codes, noises=maps)                     no dge_w_broadcast, no dge_linear_rows
+        dist = LPIPS(target, imgs) per row, area-pooled, mask-weighted when the group has a mask     as ProjectorStep.step
+        one backward ending in S form                                     dge_s2_style_grads_s, dge_s2_noise_grad
+        loss += noise_reg * sum_b reg_b                                   dge_noise_reg
+        one Adam step over [codes.flat, maps] with lr_t                   dge_adam_multi
+        maps to zero mean and unit mean square                            dge_noise_normalize
+
+    The loss is a sum over the rows and every stage is per sample: B rows are B independent refinements.  No step makes a host
+    synchronisation.  The constructor FREEZES G as ProjectorStep does.  The base rate `lr` (--s_lr) defaults to 0.01, a value
+    nobody has tuned."""
+
+    def __init__(self, G, lpips_model, steps=100, lr=0.01, lr_rampdown=0.25, lr_rampup=0.05, noise_reg=1e5):
+        if several_processes():
+            raise ValueError("StyleProjectorStep: the projector runs in one process (WORLD_SIZE > 1 is not supported)")
+        if G.training:
+            raise ValueError("StyleProjectorStep: G must be in eval mode (G.eval()): the refinement runs on fixed noise maps")
+        if steps < 1:
+            raise ValueError("StyleProjectorStep: steps must be positive")
+        self.G, self.lpips = G, lpips_model
+        for p in G.parameters():
+            p.requires_grad_(False)
+        self.steps, self.lr, self.noise_reg = int(steps), float(lr), float(noise_reg)
+        self._sched = dict(lr_rampdown=lr_rampdown, lr_rampup=lr_rampup)
+        self.codes = self.noise = self.opt = None
+        self._graph_mode = self._inputs_fresh = False
+        self.group, self.it, self.numbers, self.last = -1, 0, [], {}
+
+    def schedule(self, iteration):
+        """lr of iteration `iteration`: projector_schedule's ramp on the base rate."""
+        return projector_schedule(iteration, self.steps, self.lr, **self._sched)[0]
+
+    # ------------------------------------------------------------------ per image group
+    def begin_image(self, target, wp, noises=None, numbers=None, mask=None):
+        """Start the group of `target` [B,3,H,W] from the W stage's result: the codes = the styles of wp [B,L,512] (one
+        dge_linear_rows launch: synthesis(styles=codes) starts at the bits of synthesis(wp)); the maps = `noises` - a NoiseMaps
+        (the W stage's own: the stage goes on with it, in place), a list of maps [B,res,res] (copied), or None: the generator's
+        buffers in every row; Adam's state cleared, the count at 0 - all in place (a captured iteration stays valid)."""
+        B, dev = target.shape[0], target.device
+        self._set_mask(target, mask, "begin_image")
+        shared = noises if isinstance(noises, NoiseMaps) else None
+        if shared is not None and not shared.fits(B, dev):
+            raise ValueError("StyleProjectorStep.begin_image: the NoiseMaps given holds another batch than the target")
+        fresh = self.codes is None or not self.codes.fits(B, dev) or (shared is not None and shared is not self.noise)
+        if fresh:
+            if self.captured:
+                raise ValueError("StyleProjectorStep.begin_image: the captured iteration works on a different batch or on other noise maps")
+            from .style_codes import StyleCodes
+            self.codes = StyleCodes(self.G.synthesis, B, dev)
+            self.noise = shared if shared is not None else NoiseMaps(self.G.synthesis, B, dev)
+            self._own_noise = shared is None
+            self.opt = Adam([self.codes.flat, self.noise.flat], lr=self.lr, betas=(0.9, 0.999), eps=1e-8)
+        elif shared is None and not self._own_noise:
+            raise ValueError("StyleProjectorStep.begin_image: this step runs on a shared NoiseMaps; pass it again")
+        self.group += 1
+        self.numbers = [self.group * B + b for b in range(B)] if numbers is None else [int(n) for n in numbers]
+        if len(self.numbers) != B:
+            raise ValueError("StyleProjectorStep.begin_image: one image number per row")
+        self.codes.set_from_wp(wp)
+        if shared is None:
+            if noises is None:
+                self.noise.reset()
+            else:
+                from .autograd_s2 import check_noises
+                with torch.no_grad():
+                    for m, n in zip(self.noise.maps, check_noises(self.G.synthesis, [n.detach() for n in noises], B, dev)):
+                        m.copy_(n.expand_as(m))
+        self.opt.graph_reset()
+        self.it = 0
+
+    # ------------------------------------------------------------------ one iteration
+    def step(self, target):
+        """One iteration on target [B,3,H,W] in [-1,1].  Returns styles (the flat codes behind the step), imgs, dist [B], reg [B],
+        style_grad (flat), noise_grads, noises, lr; no host synchronisation."""
+        if self.group < 0:
+            raise RuntimeError("StyleProjectorStep.step: call begin_image() first")
+        if self._graph_mode and not self._inputs_fresh:          # an eager iteration behind capture(): it reads the device scalars too
+            self._graph_inputs(self.it)
+        self._inputs_fresh = False
+        lr_t = self.schedule(self.it)
+        imgs = self.G.synthesis(styles=self.codes, randomize_noise=False, noises=self.noise.maps, noise_grad_out=self.noise.grads,
+                                style_grad_out=self.codes.grads)["image"]
+        dist, g_img = self._dist_and_grad(target, imgs)
+        imgs.backward(g_img)
+        reg = self.noise.add_reg(self.noise_reg)
+        self.codes.flat.grad = self.codes.grads
+        self.noise.hand_grad()
+        self.opt.step(lr=lr_t)
+        self.noise.normalize()
+        self.it += 1
+        self.last = dict(styles=self.codes.detached(), imgs=imgs.detach(), dist=dist, reg=reg, style_grad=self.codes.grads,
+                         noise_grads=self.noise.grads, noises=self.noise.detached(), lr=lr_t)
+        if self._mask_state is not None:
+            self.last["mask_cover"] = self._mask_cover
+        return self.last
+
+    # ------------------------------------------------------------------ hipGraph replay of the iteration
+    def capture(self, target, warmup=GraphReplay.WARMUP):
+        """`warmup` real iterations, then one recorded (not executed) iteration (GraphReplay._capture); begin_image() must have run
+        for the group.  From here on step() reads Adam's scalars from the device."""
+        if warmup < 1:
+            raise ValueError("StyleProjectorStep.capture: warmup must be at least 1: the first real iteration allocates Adam's state, "
+                             "which a recorded iteration must find in place, and its results are what the loop reads before the first replay")
+        self._graph_masked = self._mask_state is not None
+        self._g_target = target.detach().clone()
+        for opt, calls in self._graph_opts():
+            opt.graph_begin(calls, target.device)
+        self._graph_mode = True
+        self.graph_iteration = 0
+
+        def keep_it():          # the count of the last executed iteration (the captured one is only recorded)
+            self._it_snap = self.it
+        out = self._capture_keeping_last(lambda: self.step(self._g_target), warmup, after_warmup=keep_it)
+        self.it = self._it_snap
+        return out
+
+    def _graph_opts(self):
+        return [(self.opt, 1)]          # one Adam over [codes, maps], one call per iteration
+
+    def _graph_inputs(self, iteration):
+        """The learning rate of iteration `self.it` of the group into Adam's device scalars (GraphReplay's own count runs across groups)."""
+        self.opt.param_groups[0]["lr"] = self.schedule(self.it)
+        self.opt.graph_advance()
+        self._inputs_fresh = True
+
+    def set_image(self, target, mask=None):
+        """Copies a new group's images into the static input of the captured iteration (call begin_image() for the group too)."""
+        self._set_static("_g_target", target)
+        if mask is not None:
+            self._set_mask(target, mask, "set_image")
+
+    def replay(self):
+        lr_t = self.schedule(self.it)
+        out = super().replay()
+        self._inputs_fresh = False
+        self.it += 1
+        self.last = dict(out, lr=lr_t)
+        return self.last
+
+    # ------------------------------------------------------------------ the result of a group
+    @torch.no_grad()
+    def result(self):
+        """(codes: the StyleCodes, maps, image): the refinement as it stands."""
+        maps = self.noise.detached()
+        return self.codes, maps, self.G.synthesis(styles=self.codes.detached(), randomize_noise=False, noises=maps)["image"]
+
+
+def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=None, keep=None, mask=None, styles=None):
     """`st.steps` iterations on the group `target` [B,3,H,W]; launch="graph" captures the iteration once (its warm-up iteration is a
     real one) and replays it, later groups go through set_image.  With `out_dir`: a Loss.txt line per kept row at every
     `save_every`-th iteration and at the end (one host read each), and the files of the module docstring for the first `keep` rows
     (default: all), numbered by `numbers`.  Returns the last result dict with `w`, `wp`, `noises` and `rec` of ProjectorStep.result().
     mask [B,1,H,W] f32 in [0,1] at the target's size: the masked projection (ProjectorStep.begin_image); the Loss.txt lines then end
     in `cover: ...`, and blend/{n:05d}.png (the target where the mask is 1, the reconstruction where it is 0:
-    quantize_u8(ops.mask_blend(mask, real, rec))) and mask/{n:05d}.png (8-bit L) are written next to real/ and rec/."""
+    quantize_u8(ops.mask_blend(mask, real, rec))) and mask/{n:05d}.png (8-bit L) are written next to real/ and rec/.
+    styles: a StyleProjectorStep - behind the W run its `steps` iterations refine the group in StyleSpace, from this group's wp and
+    on its maps (in place, the W step's NoiseMaps); rec/, blend/ and id{n}-noise.pt are then those of the S stage, id{n}-w.pt and
+    id{n}-wp.pt stay the W result, models/id{n}-s.pt (StyleCodes.rows) is written, Loss.txt gets the stage's lines (`id_n_____s_i`),
+    and the result dict carries the S stage's `dist` / `reg` and `styles` (the StyleCodes)."""
     from .embedding import iterate
     from .infer import quantize_u8, save_u8
     iterations = iterate(st, target, st.steps, launch)          # (validates `launch` here; starts behind begin_image, in the loop)
@@ -321,17 +495,26 @@ def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=No
         st.begin_image(target, numbers=numbers, mask=mask)
     nums = st.numbers
 
-    def log(i, r):
+    def log(i, r, stage="i"):
         vals = torch.stack((r["dist"], r["reg"]) + ((r["mask_cover"],) if mask is not None else ())).cpu()
         with open(os.path.join(out_dir, "Loss.txt"), "a+") as f:
             for b in range(keep):
-                line = "id_%d_____i_%d  dist: %s  noise_reg: %s  lr: %s  noise_scale: %s" % (nums[b], i, float(vals[0, b]), float(vals[1, b]),
-                                                                                        r["lr"], r["noise_scale"])
+                line = "id_%d_____%s_%d  dist: %s  noise_reg: %s  lr: %s  noise_scale: %s" % (nums[b], stage, i, float(vals[0, b]),
+                                                                                         float(vals[1, b]), r["lr"], r["noise_scale"])
                 print(line if mask is None else line + "  cover: %s" % float(vals[2, b]), file=f)
     for i, r in iterations:          # (st.steps >= 1: the loop runs and leaves the last result in r)
         if out_dir is not None and save_every and (i % save_every == 0 or i == st.steps - 1):
             log(i, r)
     w, wp, maps, rec = st.result()
+    codes = None
+    if styles is not None:
+        s_iterations = iterate(styles, target, styles.steps, launch)
+        styles.begin_image(target, wp, noises=st.noise, numbers=nums, mask=mask)
+        for i, rs in s_iterations:
+            if out_dir is not None and save_every and (i % save_every == 0 or i == styles.steps - 1):
+                log(i, dict(rs, noise_scale=0.0), "s")
+        codes, maps, rec = styles.result()
+        r = dict(r, dist=rs["dist"], reg=rs["reg"], styles=codes)
     if out_dir is not None:
         for sub in ("real", "rec", "models") + (("blend", "mask") if mask is not None else ()):
             os.makedirs(os.path.join(out_dir, sub), exist_ok=True)
@@ -350,6 +533,8 @@ def project(st, target, out_dir=None, save_every=100, launch="graph", numbers=No
             torch.save(wc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-w.pt" % n))
             torch.save(wpc[b:b + 1].clone(), os.path.join(out_dir, "models", "id%d-wp.pt" % n))
         save_noise_rows(mc, range(keep), nums[:keep], os.path.join(out_dir, "models"))
+        if codes is not None:
+            save_style_rows(codes, range(keep), nums[:keep], os.path.join(out_dir, "models"))
     return dict(r, w=w, wp=wp, noises=maps, rec=rec)
 
 
@@ -407,6 +592,9 @@ def make_parser():
     p.add_argument("--lr_rampup", type=float, default=0.05)
     p.add_argument("--noise_reg", type=float, default=1e5, help="weight of the noise regulariser")
     p.add_argument("--w_avg_samples", type=int, default=10000)
+    p.add_argument("--s_steps", type=int, default=0, help="iterations of the StyleSpace refinement behind every W run (0: none): the "
+                   "style codes of the W result and the noise maps are optimised further; writes models/id{n}-s.pt")
+    p.add_argument("--s_lr", type=float, default=0.01, help="base learning rate of the StyleSpace refinement (an untuned default)")
     p.add_argument("--launch", choices=("eager", "graph"), default="graph")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--save_every", type=int, default=100)
@@ -423,6 +611,10 @@ def parse_args(argv=None):
         raise SystemExit("projector: runs in one process (WORLD_SIZE > 1 is not supported)")
     if args.steps < 1 or args.batch_size < 1:
         raise SystemExit("projector: --steps and --batch_size must be positive")
+    if args.s_steps < 0:
+        raise SystemExit("projector: --s_steps must be 0 (no StyleSpace refinement) or positive")
+    if args.s_steps and not args.s_lr > 0.0:
+        raise SystemExit("projector: --s_lr must be positive")
     return args
 
 
@@ -450,12 +642,15 @@ def main(argv=None):
     st = ProjectorStep(G, LP, steps=args.steps, lr=args.lr, initial_noise_factor=args.initial_noise_factor, noise_ramp=args.noise_ramp,
                        lr_rampdown=args.lr_rampdown, lr_rampup=args.lr_rampup, noise_reg=args.noise_reg, w_avg_samples=args.w_avg_samples,
                        seed=args.seed)
+    sst = StyleProjectorStep(G, LP, steps=args.s_steps, lr=args.s_lr, lr_rampdown=args.lr_rampdown, lr_rampup=args.lr_rampup,
+                             noise_reg=args.noise_reg) if args.s_steps else None
     for first, keep, idx, _ in rows_plan(imgs.shape[0], args.batch_size):
         r = project(st, imgs[idx].contiguous(), out, args.save_every, args.launch, numbers=idx, keep=keep,
-                    mask=None if masks is None else masks[idx].contiguous())
+                    mask=None if masks is None else masks[idx].contiguous(), styles=sst)
         vals = torch.stack((r["dist"], r["reg"])).cpu()
         for b in range(keep):
             print("image %d: dist %.5f  noise_reg %.3e" % (first + b, float(vals[0, b]), float(vals[1, b])))
+    st.style_stage = sst          # (the StyleProjectorStep of --s_steps, or None)
     return st
 
 

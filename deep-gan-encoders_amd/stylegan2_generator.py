@@ -297,11 +297,19 @@ class SynthesisModule(nn.Module):
     def get_nf(self, res):
         return min(self.fmaps_base // res, self.fmaps_max)
 
-    def forward(self, wp, randomize_noise=False, noises=None, noise_grad_out=None):
+    def forward(self, wp=None, randomize_noise=False, noises=None, noise_grad_out=None, styles=None, style_grad_out=None):
         """Extra keywords: `noises`, one f32 map [1,res,res] (shared by the batch) or [B,res,res] per conv layer in layer order,
         replacing the `layer{i}.noise` buffers; a map that requires grad receives its gradient (dge_s2_noise_grad).  Where the
         list `noise_grad_out` names a buffer of the map's shape, the gradient is written there INSTEAD of reaching the map's
-        .grad (static storage for a captured iteration, no accumulation pass)."""
+        .grad (static storage for a captured iteration, no accumulation pass).
+        `styles`: a style_codes.StyleCodes or its flat tensor, in place of wp (which must then be None): the pass starts from the
+        StyleSpace codes; the result dict has the image and the style views and no `wp`.  A flat tensor that requires grad receives
+        the style gradient (dge_s2_style_grads_s), or the flat buffer `style_grad_out` does in its place."""
+        if styles is not None or style_grad_out is not None:
+            from .autograd_s2 import synthesis_forward
+            return synthesis_forward(self, wp, randomize_noise, noises, noise_grad_out, styles, style_grad_out)
+        if wp is None:
+            raise ValueError("synthesis: give wp [batch_size, num_layers, w_space_dim], or `styles`")
         if wp.ndim != 3 or tuple(wp.shape[1:]) != (self.num_layers, self.w_space_dim):
             raise ValueError(f"Input tensor should be with shape [batch_size, num_layers, w_space_dim], where "
                              f"`num_layers` equals to {self.num_layers}, and `w_space_dim` equals to "

@@ -906,6 +906,32 @@ int dge_lpips_head_w_finalize(const float* slots, const long long* host_off5, co
  * torch's expression.  dge_last_kernel: "mask_blend". */
 int dge_mask_blend(const float* m, const float* a, const float* b, float* out, int B, int HW, dge_stream_t stream);
 
+/* ---- StyleSpace codes of StyleGAN2 (dge_amd.style_codes, synthesis(styles=...)) ---------------------------------------------- */
+/* The S-space ending of the synthesis backward: dge_s2_style_grads without its last step, the contraction with the style DenseBlock.
+ * Every block stores its style gradient to `out`, its own [B,in_c] slice of the caller's style-gradient buffer, with plain stores:
+ * every (block, b, c) has one writer, nothing is pre-zeroed, and the same operands give the same bits.  Three kinds of block:
+ *   conv block (P != NULL): the operands of dge_s2_grad_entry;  out[b,c] = st[b,c,0] + s[b,c] * sum_o t[b,o] * wsq[o,c]  with
+ *     t[b,o] = -(P0 - bias[o]*bscale*P1) * d[b,o]^2, the nslot_p / nslot_s copies of P / st added first;
+ *   finished block (P == NULL, st != NULL): out[b,c] = st[b,c,0], its nslot_s copies added (a layer whose tail backward ran as a
+ *     pass of its own and that has added the demodulation part into st already);
+ *   toRGB block (P == NULL, st == NULL): out[b,c] = gs[b,c].
+ * n <= 32, channels <= 512.  A struct of its own: dge_s2_grad_entry is passed by value 32 at a time and does not grow.
+ * dge_last_kernel: "s2_style_grads_s". */
+typedef struct dge_s2_sgrad_entry {
+    const float* P; const float* st; const float* d; const float* s; const float* bias; const float* wsq;
+    const float* gs; float* out;
+    int nslot_p, nslot_s, in_c, out_c;
+    float bscale; int pad;
+} dge_s2_sgrad_entry;
+int dge_s2_style_grads_s(const dge_s2_sgrad_entry* entries, int n, int B, dge_stream_t stream);
+/* x [N,D] -> mean [D] and std [D] over the rows, std[d] = sqrt(sum_n (x[n,d] - mean[d])^2 / N): the sigma unit of a StyleSpace edit.
+ * Two passes over chunks of 64 rows, the scheme of dge_rows_mean_std: a chunk's column sums (then its columns' squared deviations)
+ * go to the chunk's slot and the slots are added in slot order.  No atomics; the same bits run to run.  Any D (scalar loads).
+ * work: dge_cols_mean_std_work_bytes(N, D) bytes (-1: sizes it refuses).  dge_last_kernel: "cols_mean_std". */
+int dge_cols_mean_std_work_bytes(long long N, int D);
+int dge_cols_mean_std(const float* x, long long N, int D, float* mean, float* std, void* work, long long work_bytes,
+                      dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,11 @@ seeded stand-in LPIPS, one process.  Configurations alternate round by round; me
   * --mask: only the masked against the unmasked iteration (README, "Masked projection"): hipGraph replay at every batch of
     --batches, a soft-edged half-plane mask, the two alternating round by round in one process; the difference of the medians
     is what the mask costs per iteration (one more f32 plane read in each prep, one m_k read per head, six head launches for
-    five)."""
+    five).
+  * --styles: only the S iteration (StyleProjectorStep: the StyleSpace codes and the maps under Adam; README, "StyleSpace codes")
+    against the W iteration, hipGraph replay at every batch of --batches, the two alternating round by round in one process.
+    The S iteration drops dge_w_broadcast (and the dge_randn draw in front of it), dge_linear_rows and the contraction of the
+    style gradients with the style weights, and steps 9088 floats per image for 512."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,7 +22,7 @@ import dge_amd  # noqa: F401
 from dge_amd import ops
 from dge_amd.custom_adam import Adam
 from dge_amd.lpips import LPIPS
-from dge_amd.projector import ProjectorStep
+from dge_amd.projector import ProjectorStep, StyleProjectorStep
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--img-size", type=int, default=1024); ap.add_argument("--dtype", default="bf16")
@@ -26,6 +30,7 @@ ap.add_argument("--fmaps-base", type=int, default=None); ap.add_argument("--fmap
 ap.add_argument("--batches", default="1,8"); ap.add_argument("--iters", type=int, default=20); ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--w-avg-samples", type=int, default=10000)
 ap.add_argument("--mask", action="store_true", help="time the masked against the unmasked replay and nothing else")
+ap.add_argument("--styles", action="store_true", help="time the S iteration against the W iteration (replay) and nothing else")
 a = ap.parse_args()
 assert torch.cuda.is_available(), "bench_projector needs the GPU"
 res = {}
@@ -96,6 +101,34 @@ if a.mask:
         d = res[f"B{B}_masked"]["ms"] - res[f"B{B}_plain"]["ms"]
         res[f"B{B}_mask_cost_ms"] = round(d, 4)
         print(f"B{B}: the mask costs {d:+.3f} ms per iteration ({100 * d / res[f'B{B}_plain']['ms']:+.2f} %)", flush=True)
+    print(json.dumps(res))
+    sys.exit(0)
+
+# ---- --styles: the S iteration against the W iteration
+if a.styles:
+    runs, per = {}, {}
+    for B in batches:
+        x = imgs[:B].contiguous()
+        st = ProjectorStep(G, LP, w_avg_samples=a.w_avg_samples)
+        st.begin_image(x)
+        st.capture(x, warmup=1)
+        sst = StyleProjectorStep(G, LP)
+        sst.begin_image(x, st.result()[1])          # (maps of its own: the two replays alternate and must not share state)
+        sst.capture(x, warmup=1)
+        for name, run in (("W", st.replay), ("S", sst.replay)):
+            for _ in range(3):
+                run()
+            runs[f"B{B}_{name}"], per[f"B{B}_{name}"] = run, B
+    ms = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for name, run in runs.items():
+            ms[name].append(timed(run, a.iters))
+    report(f"projector replay, W iteration and S iteration, StyleGAN2-{a.img_size}, {a.dtype}", ms, per)
+    for B in batches:
+        d = res[f"B{B}_S"]["ms"] - res[f"B{B}_W"]["ms"]
+        res[f"B{B}_S_minus_W_ms"] = round(d, 4)
+        print(f"B{B}: the S iteration takes {d:+.3f} ms against the W iteration ({100 * d / res[f'B{B}_W']['ms']:+.2f} %); "
+              f"round spreads W {res[f'B{B}_W']['spread']:.3f}, S {res[f'B{B}_S']['spread']:.3f}", flush=True)
     print(json.dumps(res))
     sys.exit(0)
 
