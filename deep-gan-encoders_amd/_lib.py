@@ -252,6 +252,10 @@ SIGNATURES = {
     "dge_s2_style_grads_s": [C.POINTER(S2SGradEntry), _I, _I, _P],
     "dge_cols_mean_std_work_bytes": [C.c_longlong, _I],
     "dge_cols_mean_std": [_P, C.c_longlong, _I, _P, _P, _P, C.c_longlong, _P],
+    "dge_gram_work_bytes": [C.c_longlong, _I],
+    "dge_gram": [_P, C.c_longlong, _I, C.c_longlong, _P, _I, _F, _P, _P, C.c_longlong, _P],
+    "dge_eigh_sym_work_bytes": [_I],
+    "dge_eigh_sym": [_P, _I, _P, _P, C.POINTER(C.c_double), _P, C.c_longlong, _I, _P],
 }
 
 _lib = None

@@ -2,7 +2,8 @@
 
 * `reconstruct`   - inferE.py:101-141 / rec_real_img.py / synthesized_IMG.py: G(z) -> E -> G(w2) once, no gradients;
 * `edit_latent`   - embeded_img_edit.py:28-41: w[start:start+end] = (w + bonus*direction)[start:start+end] on a W+ code,
-                    then one Gs.forward(w, lod);
+                    then one Gs.forward(w, lod); directions for StyleGAN2, which ships no boundary file, come from
+                    `dge_amd.directions` (SeFa, W-space PCA), whose `edit_direction` calls this function;
 * `style_sigma` / `edit_styles` - StyleSpace edits ("block, channel, + k sigma") on the per-channel style codes of StyleGAN2
                     (style_codes.StyleCodes.rows, `id{n}-s.pt`): no boundary file is needed;
 * `image_metrics` - comparing-baseline.py:21-45 on device: PSNR / MSE on [0,255], cosine on [-1,1], LPIPS and the skimage SSIM of

@@ -1918,6 +1918,52 @@ def cols_mean_std(x):
     return mean, std
 
 
+# ---- dense linear algebra of the semantic directions (include/dge_hip.h dge_gram / dge_eigh_sym)
+def gram(x, mean=None, row_norm=False, scale=1.0):
+    """x [N,D] f32 (rows may be strided: a column slice of a wider matrix) -> out [D,D] = scale * sum_n u_n u_n^T with u_n = x_n / |x_n|
+    (row_norm), x_n - mean (mean [D]) or x_n; out == out^T to the bit (dge_gram)."""
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise DgeError("gram: x is a float32 device matrix [N,D] whose rows are contiguous")
+    N, D = x.shape
+    ldx = x.stride(0) if N > 1 else max(x.stride(0), D)
+    if mean is not None and (mean.numel() != D or not mean.is_cuda):
+        raise DgeError(f"gram: mean holds D = {D} device floats")
+    nb = lib().dge_gram_work_bytes(N, D)
+    if nb < 0:
+        check(nb, "dge_gram_work_bytes")
+    work = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+    out = torch.empty((D, D), dtype=torch.float32, device=x.device)
+    check(lib().dge_gram(C.c_void_p(x.data_ptr()), N, D, ldx, _f32(mean), 1 if row_norm else 0, float(scale), _p(out), _p(work),
+                         work.numel() * 4, _stream()), "dge_gram")
+    log_kernel()
+    return out
+
+
+def eigh_sym(a, max_sweeps=30):
+    """a [D,D] f32, symmetric (the upper triangle is read) -> (evals [D] descending, evecs [D,D] with the unit eigenvector of
+    evals[k] in row k, its largest component positive, (sweeps, off(A))) (dge_eigh_sym).  One host read per sweep.  Not converged
+    after max_sweeps: DgeError, whose `partial` attribute holds the same triple of the last iterate."""
+    if a.dim() != 2 or a.shape[0] != a.shape[1]:
+        raise DgeError(f"eigh_sym: a is a square matrix, got {tuple(a.shape)}")
+    D = a.shape[0]
+    nb = lib().dge_eigh_sym_work_bytes(D)
+    if nb < 0:
+        check(nb, "dge_eigh_sym_work_bytes")
+    work = torch.empty((nb + 7) // 8, dtype=torch.float64, device=a.device)
+    evals = torch.empty(D, dtype=torch.float32, device=a.device)
+    evecs = torch.empty((D, D), dtype=torch.float32, device=a.device)
+    status = (C.c_double * 2)(0.0, 0.0)
+    rc = lib().dge_eigh_sym(_f32(a), D, _p(evals), _p(evecs), status, _p(work), work.numel() * 8, int(max_sweeps), _stream())
+    result = evals, evecs, (int(status[0]), float(status[1]))
+    if rc == -2:
+        err = DgeError(f"dge_eigh_sym failed ({rc}): {lib().dge_last_error().decode()}")
+        err.partial = result
+        raise err
+    check(rc, "dge_eigh_sym")
+    log_kernel()
+    return result
+
+
 def area_pool_bwd(g_pooled, k, out=None):
     """g_pooled [B,C,h,w] f32 -> [B,C,h*k,w*k]: the adjoint of the k x k area pooling (each value / k^2 to its k x k pixels)."""
     B, Cc, h, w = g_pooled.shape

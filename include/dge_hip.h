@@ -932,6 +932,31 @@ int dge_cols_mean_std_work_bytes(long long N, int D);
 int dge_cols_mean_std(const float* x, long long N, int D, float* mean, float* std, void* work, long long work_bytes,
                       dge_stream_t stream);
 
+/* ---- Dense linear algebra of the semantic directions (dge_amd.directions: SeFa, W-space PCA) ---------------------------------- */
+/* All operands and results f32; no atomics, nothing pre-zeroed, partial sums in slots of the caller's workspace added in a fixed
+ * order: the same bits from run to run and in both reduction modes.
+ * dge_gram: out [D,D] = scale * sum_n u_n u_n^T over the rows x_n of x [N,D] (row stride ldx >= D floats), with u_n = x_n / |x_n|_2
+ * when row_norm is set (the f32 norm, a correctly rounded division; a zero row contributes nothing), u_n = x_n - mean when mean [D]
+ * is given, u_n = x_n otherwise; row_norm together with mean is refused.  N >= 1, 1 <= D <= 1024, any D.  f32 VALU: the products are
+ * f32 fmas, never rounded to bf16; a 64 x 64 tile of the upper triangle per workgroup, the rows of a 512-row chunk ascending in one
+ * f32 accumulator per element, the chunks added in chunk order; the lower triangle is the mirror of the upper (out == out^T to the
+ * bit).  work: dge_gram_work_bytes(N, D) bytes, 16-byte aligned (-1: sizes it refuses).  dge_last_kernel: "gram". */
+int dge_gram_work_bytes(long long N, int D);
+int dge_gram(const float* x, long long N, int D, long long ldx, const float* mean, int row_norm, float scale, float* out, void* work,
+             long long work_bytes, dge_stream_t stream);
+/* Eigendecomposition of the symmetric matrix a [D,D], 1 <= D <= 1024, of which only the upper triangle is read.  evals [D] in
+ * descending order; row k of evecs [D,D] is the unit eigenvector of evals[k], its component of largest magnitude positive (ties to
+ * the lowest index).  Parallel-ordered two-sided Jacobi on an f64 working copy: round-robin pairs (a bye for odd D), the disjoint
+ * rotations of a round applied by one launch, out of place; D - 1 (D even) or D (D odd) launches a sweep plus two for off(A), which
+ * the host reads once per sweep - the call synchronises the stream and cannot be captured into a graph.  The sweeps end when
+ * off(A) = sqrt(sum_{i != j} a_ij^2) <= 2^-40 |A|_F.  host_status (HOST, two doubles): the sweeps taken and the final off(A).  Not
+ * converged after max_sweeps (1 .. 1000): returns -2 with a message, and evals / evecs / host_status hold the last iterate.
+ * No workgroup waits for another one.  work: dge_eigh_sym_work_bytes(D) bytes, 8-byte aligned (-1: a D it refuses).
+ * dge_last_kernel: "eigh_sym". */
+int dge_eigh_sym_work_bytes(int D);
+int dge_eigh_sym(const float* a, int D, float* evals, float* evecs, double* host_status, void* work, long long work_bytes, int max_sweeps,
+                 dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
