@@ -256,7 +256,14 @@ SIGNATURES = {
     "dge_gram": [_P, C.c_longlong, _I, C.c_longlong, _P, _I, _F, _P, _P, C.c_longlong, _P],
     "dge_eigh_sym_work_bytes": [_I],
     "dge_eigh_sym": [_P, _I, _P, _P, C.POINTER(C.c_double), _P, C.c_longlong, _I, _P],
+    "dge_gram_cols_chunk": [C.c_longlong],
+    "dge_gram_cols_work_bytes": [_I, C.c_longlong],
+    "dge_gram_cols": [_P, _I, C.c_longlong, C.c_longlong, _P, C.c_longlong, _F, _P, _P, _P, C.c_longlong, _P],
+    "dge_fd_pool_diff": [_P, _I, _I, _I, _I, _I, _F, _P, C.c_longlong, _P],
+    "dge_wp_axis_pairs": [_P, _P, C.c_longlong, _I, _I, _I, _I, _I, _F, _P, _P],
+    "dge_matmul_f64acc": [_P, C.c_longlong, _P, C.c_longlong, _I, _P, C.c_longlong, _I, _I, _I, _P],
 }
+RETURNS_LONGLONG = ("dge_gram_cols_chunk", "dge_gram_cols_work_bytes")          # every other entry point returns int
 
 _lib = None
 
@@ -271,7 +278,7 @@ def lib():
         for name, args in SIGNATURES.items():
             fn = getattr(_lib, name)
             fn.argtypes = args
-            fn.restype = C.c_int
+            fn.restype = C.c_longlong if name in RETURNS_LONGLONG else C.c_int
         for name in ("dge_last_error", "dge_last_kernel"):
             getattr(_lib, name).restype = C.c_char_p
             getattr(_lib, name).argtypes = []

@@ -2114,3 +2114,98 @@ def mask_blend(m, a, b, out=None):
     check(lib().dge_mask_blend(_f32(m.contiguous()), _f32(a.contiguous()), _f32(b.contiguous()), _f32(out), B, H * W, _stream()), "dge_mask_blend")
     _log_dense("dge_mask_blend")
     return out
+
+
+# ---- region directions (include/dge_hip.h dge_gram_cols / dge_fd_pool_diff / dge_wp_axis_pairs / dge_matmul_f64acc)
+def _matrix_view(t, what):
+    """(rows, columns, row stride) of a float32 device matrix whose rows are contiguous (a row or column slice of a wider one)"""
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda or t.shape[0] < 1 or t.shape[1] < 1 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise DgeError(f"{what}: a non-empty float32 device matrix whose rows are contiguous")
+    R, Cn = t.shape
+    return R, Cn, (t.stride(0) if R > 1 else max(t.stride(0), Cn))
+
+
+def gram_cols_chunk(N):
+    """the columns of one chunk of dge_gram_cols at N columns (one partial tile per chunk and tile, added in chunk order)"""
+    c = lib().dge_gram_cols_chunk(int(N))
+    if c < 0:
+        check(int(c), "dge_gram_cols_chunk")
+    return int(c)
+
+
+def gram_cols(x, wgt=None, scale=1.0, both=None):
+    """x [K,N] f32, K-major with contiguous rows (rows may be strided) -> out_a [K,K] = scale * sum_n w_n x_n x_n^T over the columns,
+    w_n = wgt[n mod P] for wgt of P floats (P divides N); with a weight also out_b = scale * sum_n (1 - w_n) x_n x_n^T from the same
+    read (both=False: out_a alone).  wgt=None: w = 1, one output.  Both are symmetric to the bit (dge_gram_cols).  Returns out_a or
+    (out_a, out_b)."""
+    K, N, ldx = _matrix_view(x, "gram_cols: x")
+    both = wgt is not None if both is None else bool(both)
+    if both and wgt is None:
+        raise DgeError("gram_cols: the complement output needs a weight")
+    P = 1
+    if wgt is not None:
+        if wgt.dtype != torch.float32 or not wgt.is_cuda or wgt.numel() < 1 or N % wgt.numel():
+            raise DgeError(f"gram_cols: wgt holds P device floats with P dividing N = {N}")
+        P = wgt.numel()
+    nb = lib().dge_gram_cols_work_bytes(K, N)
+    if nb < 0:
+        check(int(nb), "dge_gram_cols_work_bytes")
+    work = torch.empty(nb // 4, dtype=torch.float32, device=x.device)
+    out_a = torch.empty((K, K), dtype=torch.float32, device=x.device)
+    out_b = torch.empty((K, K), dtype=torch.float32, device=x.device) if both else None
+    check(lib().dge_gram_cols(C.c_void_p(x.data_ptr()), K, N, ldx, _f32(wgt), P, float(scale), _p(out_a), _p(out_b), _p(work), nb, _stream()),
+          "dge_gram_cols")
+    log_kernel()
+    return (out_a, out_b) if both else out_a
+
+
+def fd_pool_diff(img, s, scale, x):
+    """img [2n,C,H,W] f32 -> row j of x [n, >= C*(H/s)*(W/s)] (a row slice of the Jacobian operand) = scale * the s x s window sums of
+    img[2j] - img[2j+1] (dge_fd_pool_diff)."""
+    if img.dim() != 4 or img.shape[0] % 2 or img.shape[0] < 2:
+        raise DgeError(f"fd_pool_diff: img holds an even number of images [2n,C,H,W], got {tuple(img.shape)}")
+    B, Cc, H, W = img.shape
+    n, _, ldx = _matrix_view(x, "fd_pool_diff: x")
+    if n != B // 2 or int(s) < 1 or H % int(s) or W % int(s) or x.shape[1] != Cc * (H // int(s)) * (W // int(s)):
+        raise DgeError(f"fd_pool_diff: x is {tuple(x.shape)} for {B // 2} image pairs of {Cc} x {H} x {W} pooled by {s}")
+    check(lib().dge_fd_pool_diff(_f32(img), n, Cc, H, W, int(s), float(scale), C.c_void_p(x.data_ptr()), ldx, _stream()), "dge_fd_pool_diff")
+    log_kernel()
+    return x
+
+
+def wp_axis_pairs(wp, q, r0, r1, h, out=None):
+    """wp [L,D], q [n,D] (rows may be strided) -> out [2n,L,D]: code 2j = fma(h, q_j, wp), code 2j+1 = fma(-h, q_j, wp) on W+ rows
+    r0 .. r1 - 1, bit copies of wp elsewhere (dge_wp_axis_pairs)."""
+    if wp.dim() != 2:
+        raise DgeError(f"wp_axis_pairs: wp is one code [L,D], got {tuple(wp.shape)}")
+    L, D = wp.shape
+    n, Dq, ldq = _matrix_view(q, "wp_axis_pairs: q")
+    if Dq != D:
+        raise DgeError(f"wp_axis_pairs: q has {Dq} columns, the code {D}")
+    if out is None:
+        out = torch.empty((2 * n, L, D), dtype=torch.float32, device=wp.device)
+    elif tuple(out.shape) != (2 * n, L, D):
+        raise DgeError(f"wp_axis_pairs: out must be {(2 * n, L, D)}")
+    check(lib().dge_wp_axis_pairs(_f32(wp), C.c_void_p(q.data_ptr()), ldq, n, L, D, int(r0), int(r1), float(h), _f32(out), _stream()),
+          "dge_wp_axis_pairs")
+    log_kernel()
+    return out
+
+
+def matmul_f64acc(a, b, trans_b=False, out=None):
+    """a [M,Kk] times b [Kk,N] (trans_b: b [N,Kk], its transpose taken) -> out [M,N], every dimension <= 1024: f32 operands, the
+    products and the ascending-k sum in f64, rounded once (dge_matmul_f64acc).  Rows may be strided."""
+    M, Kk, lda = _matrix_view(a, "matmul_f64acc: a")
+    Rb, Cb, ldb = _matrix_view(b, "matmul_f64acc: b")
+    N, Kb = (Rb, Cb) if trans_b else (Cb, Rb)
+    if Kb != Kk:
+        raise DgeError(f"matmul_f64acc: a is {tuple(a.shape)}, b {tuple(b.shape)}{' transposed' if trans_b else ''}")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+    Mo, No, ldo = _matrix_view(out, "matmul_f64acc: out")
+    if (Mo, No) != (M, N):
+        raise DgeError(f"matmul_f64acc: out must be {(M, N)}")
+    check(lib().dge_matmul_f64acc(C.c_void_p(a.data_ptr()), lda, C.c_void_p(b.data_ptr()), ldb, 1 if trans_b else 0, C.c_void_p(out.data_ptr()),
+                                  ldo, M, N, Kk, _stream()), "dge_matmul_f64acc")
+    log_kernel()
+    return out

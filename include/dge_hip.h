@@ -957,6 +957,38 @@ int dge_eigh_sym_work_bytes(int D);
 int dge_eigh_sym(const float* a, int D, float* evals, float* evecs, double* host_status, void* work, long long work_bytes, int max_sweeps,
                  dge_stream_t stream);
 
+/* ---- Region directions (dge_amd.region_directions: ReSeFa) ------------------------------------------------------------------- */
+/* All f32 in and out; no atomics, nothing pre-zeroed, no workgroup waits for another one; the same bits from run to run and in
+ * both reduction modes.
+ * dge_gram_cols: the weighted Gram matrices of a K-major operand x [K,N] (row stride ldx >= N floats, long contiguous rows):
+ * out_a [K,K] = scale * sum_n w_n x_n x_n^T and out_b [K,K] = scale * sum_n (1 - w_n) x_n x_n^T over the columns x_n, with
+ * w_n = wgt[n mod P] (P divides N) and 1 - w formed once as 1.0f - w; x is read once for both.  wgt = NULL: w = 1, and out_b must
+ * then be NULL.  1 <= K <= 1024, 1 <= N < 2^31.  f32 VALU: the weight is multiplied into the j-side operand (one rounding), the
+ * products are f32 fmas, never rounded to bf16.  A 64 x 64 tile of the upper triangle per workgroup over a chunk of
+ * dge_gram_cols_chunk(N) columns (4096 up to N = 2^20, N / 256 rounded up to a multiple of 32 beyond), the columns ascending in
+ * one f32 accumulator per element and output; the partial tiles go to their slots of work, and a second launch adds the chunks in
+ * chunk order, applies scale and writes (i,j) and (j,i) from the one sum (out == out^T to the bit).  work:
+ * dge_gram_cols_work_bytes(K, N) bytes, 16-byte aligned (-1: sizes it refuses).  dge_last_kernel: "gram_cols". */
+long long dge_gram_cols_chunk(long long N);
+long long dge_gram_cols_work_bytes(int K, long long N);
+int dge_gram_cols(const float* x, int K, long long N, long long ldx, const float* wgt, long long P, float scale, float* out_a, float* out_b,
+                  void* work, long long work_bytes, dge_stream_t stream);
+/* Row j of x (row stride ldx >= C * (H/s) * (W/s)), j < n, = scale * the s x s window sums of img[2j] - img[2j+1] (img [2n,C,H,W],
+ * s divides H and W), in (c, y, x) order: the differences of a window in row-major order in one f32 accumulator that starts from
+ * the first, then one multiplication by scale (s = 1: (a - b) * scale, each operation rounded).  The caller forms
+ * scale = 1 / (2 h s^2) in double and rounds it once.  The padding of x beyond a row is not written.
+ * dge_last_kernel: "fd_pool_diff". */
+int dge_fd_pool_diff(const float* img, int n, int C, int H, int W, int s, float scale, float* x, long long ldx, dge_stream_t stream);
+/* out [2n,L,D]: code 2j = fma(h, q_j, wp) and code 2j+1 = fma(-h, q_j, wp) on the W+ rows r0 .. r1 - 1 of wp [L,D]
+ * (0 <= r0 <= r1 <= L; q [n,D], row stride ldq >= D); the other rows are bit copies of wp.  dge_last_kernel: "wp_axis_pairs". */
+int dge_wp_axis_pairs(const float* wp, const float* q, long long ldq, int n, int L, int D, int r0, int r1, float h, float* out,
+                      dge_stream_t stream);
+/* out [M,N] (row stride ldo) = a [M,Kk] (row stride lda) times b: b [Kk,N] (row stride ldb >= N) or, with trans_b, the transpose
+ * of b [N,Kk] (row stride ldb >= Kk).  Every dimension 1 .. 1024.  f32 operands; the products and the ascending-k sum in f64,
+ * rounded once to f32.  dge_last_kernel: "matmul_f64acc". */
+int dge_matmul_f64acc(const float* a, long long lda, const float* b, long long ldb, int trans_b, float* out, long long ldo, int M, int N,
+                      int Kk, dge_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
